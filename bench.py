@@ -12,8 +12,8 @@ matches Sponza.gltf's statistics: 103 submeshes, 262 k triangles, 25 materials, 
 The G-buffer is produced once, outside the timed region, by neb_gbuffer_raycast (static camera).
 
 N > 1 (`value`, strong scaling = the metric's own curve): the SAME 1920x1080 frame cut into N row strips, one per GPU,
-which exchange a-trous halo rows over RCCL (nebulae_amd/strips.py); `value` = frames/s of that frame.  Two more legs ride in
-the same JSON line for N > 1:
+which exchange a-trous halo rows over RCCL (nebulae_amd/strips.py); `value` = frames/s of that frame.  With --full, two more
+legs ride in the same JSON line for N > 1:
   "weak_scaling"  the frame grows with N -- rank r owns a 1080p-equivalent row strip of a (1920*a) x (1080*b) image,
                   a*b = N (N=4 is BASELINE.json configs[3], 3840x2160) -- in 1080p-frame equivalents per second;
   "config5"       (N = 8, or --config5) BASELINE.json configs[4]: 3840x2160 in N strips, 4 spp, the camera
@@ -26,8 +26,10 @@ and SVGF chain (neb_gi_trace_begin / _finish; strips of at most 0.3 M pixels: th
 frames bit for bit; `config.frames_in_flight` says which, `value_one_frame_in_flight` is the rate of the same K steps run serially.
 (NEB_BENCH_PIPELINE=split|defer forces a form: experiments.)
 
-Prints ONE JSON line (rank 0) with "roofline" (dominant SVGF kernel = a-trous level, HBM bound,
-algorithmic 46 B/px/level) and "cpu_baseline" (the scalar C/C++ oracle on the host cores).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K steps and reports them (`value`, `ms_per_step`);
+--dump-outputs DIR also writes the frame the last timed step denoised.  --full measures the rest after the timed region and adds
+it to the line: the settled rate and the rate with one frame in flight, per-kernel times, "roofline" (dominant SVGF kernel =
+a-trous level, HBM bound, algorithmic 46 B/px/level), "cpu_baseline" (the scalar C/C++ oracle on the host cores) and the N > 1 legs.
 """
 import argparse
 import json
@@ -43,6 +45,7 @@ TEMPORAL_BYTES_PX = 82  # 60 B read + 22 B written
 ATROUS_BYTES_PX = 46    # per level: 30 B read + 16 B written
 GI_STREAM_BYTES_PX = 56  # 24 B G-buffer read + 32 B radiance read-modify-write
 PROFILE_ROUND = "r05"   # only PMC summaries of this round's kernels are quoted (profiles/r05*_*.json), and only of this very build
+DUMP_CAP_BYTES = 64 << 20  # --dump-outputs: at most this much in all
 
 
 def parse(argv=None):
@@ -79,7 +82,34 @@ def parse(argv=None):
     ap.add_argument("--config5-frames", type=int, default=32, help="frames of the config-5 sequence (half moving, half still)")
     ap.add_argument("--config5-size", type=int, nargs=2, default=(3840, 2160), metavar=("W", "H"),
                     help="frame of the config-5 leg (BASELINE.json configs[4]: 3840 2160; the CPU dry run shrinks it)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the settled rate, the rate with one frame in flight, per-kernel times and "
+                         "rooflines, the CPU oracle baseline (--cpu-frames), and for N > 1 the weak-scaling leg, config 5 and --gather.  Without it "
+                         "a run sets up, warms up, times the K steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed -- the denoised frame, float32 -- as DIR/<name>.npy "
+                         f"(at most {DUMP_CAP_BYTES >> 20} MB: a larger frame is cut to a fixed, seeded sample of its pixels)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if (args.gather or args.config5) and not args.full:
+        ap.error("--gather and --config5 are legs of --full")
+    return args
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float32.  Past DUMP_CAP_BYTES in all, each array keeps a fixed, seeded
+    sample of its pixels (rows of the [H*W, C] view, in order): the same arguments give the same file, so two builds compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_CAP_BYTES:
+            flat = a.reshape(a.shape[0] * a.shape[1], -1)
+            keep = int(flat.shape[0] * (DUMP_CAP_BYTES / total))
+            a = flat[np.sort(np.random.default_rng(0).choice(flat.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def _free_port():
@@ -630,7 +660,6 @@ def main(argv=None, rt=None, emit=None):
     if rt is None and args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # typed as `python3 bench.py --gpus N` with no launcher around it: be the launcher (before anything touches a GPU)
         raise SystemExit(launch_ranks(args.gpus, sys.argv[1:] if argv is None else list(argv)))
-    import numpy as np
     import torch
     import torch.distributed as dist
     rt = rt or GpuRuntime()
@@ -656,7 +685,6 @@ def main(argv=None, rt=None, emit=None):
     link = None
     if world > 1:
         link = strips.measure_link(rank, world, group, lambda n: rt.to_device(torch.zeros(n, dtype=torch.uint8)), rt.synchronize)
-    from nebulae_amd.svgf import PLANE_ALBEDO, PLANE_DEPTH, PLANE_NORMAL, PLANE_ROUGH_METAL, PLANE_WORLDPOS
 
     L = args.levels
     do_gi = not args.svgf_only
@@ -693,26 +721,78 @@ def main(argv=None, rt=None, emit=None):
     dt, rays_total = w.timed(args.steps, warmup_run)
     answered_total = w.last_answered
     assert all(w.ran_svgf), "SVGF was skipped inside the timed region"
+    if args.dump_outputs:  # the frame the last timed step denoised, before any later frame overwrites it (N > 1: the strips gathered to rank 0)
+        frame = r.gather_frame(dst=0)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"radiance": frame.cpu().numpy()})
     if do_gi:  # (as of the ray count that ended the timed region: sides proven lit, shadow rays the table answered in those K frames)
         bvh["sun_table"] = r.sun_table_stats()
         ms = r.sun_table_build_ms()
         bvh["sun_table"]["build_ms"] = None if ms is None else round(ms, 2)
         mode, (us_lists, us_sorted) = r.shadow_tail_mode()  # which pass takes the rays the table leaves: measured by the library once per table build
         bvh["sun_table"]["tail"] = {"mode": {0: "lists", 1: "sorted pass", -1: "undecided"}[mode], "timed_us": {"lists": round(us_lists, 1), "sorted_pass": round(us_sorted, 1)}}
+    own_px = (w.own[1] - w.own[0]) * GW                      # pixels a rank owns
+    parallelism = w.parallelism_label()
+    halo_rows = part.halo
+    extra = measure_beside(rt, args, w, rank, world, do_gi) if args.full else None
+    w.destroy()
+    if args.full:
+        extra.update(measure_other_legs(rt, args, sc, cam, rank, world, local_rank, group, scheme, link, do_gi))
+
+    if rank == 0:
+        fps = args.steps / dt                                 # whole-job frames per second of the ONE frame
+        out = {
+            "metric": ("denoised frames/s (1920x1080: GI 1 spp + SVGF temporal + a-trous)" if do_gi else
+                       "denoised frames/s (1920x1080: SVGF temporal + a-trous only)"),
+            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_run": warmup_run,
+            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic" if not args.scene else f"scene file {os.path.basename(args.scene)}; synthetic camera",
+            "config": {"workload": workload_label(GW, GH, args.spp, L, do_gi),
+                       "global_width": GW, "global_height": GH, "atrous_levels": L, "spp": args.spp,
+                       "parallelism": parallelism, "link": (link.label() if link is not None else None), "halo_rows": halo_rows, "rows_per_strip": GH // world,
+                       "frames_in_flight": frames_in_flight,
+                       # what the metric's own strong-scaling curve cannot exceed at N strips, before a byte is exchanged: one strip's frame alone on
+                       # a GPU (measured with the exchange stubbed, strips.STRIP_FRAME_US_1080P) -- to read a SCALE_rNN.json against
+                       "strong_scaling_ceiling": (strips.strong_scaling_ceilings() if (GW, GH) == (1920, 1080) else None),
+                       "scene_device_bytes": scene_bytes, "bvh": bvh, "library_build_id": library_build_id()},
+            # rays = W H spp (1 + hit fraction) per frame (SURVEY 8d): one bounce ray per pixel + one sun-visibility QUERY per hit.  Most of the
+            # queries are answered by the sun table inside the shade pass; `traced_*` counts only the rays a traverser walked (bounce rays + the
+            # shadow rays left in the lists) -- the figure to read as traverser throughput
+            "mrays_per_s": (rays_total / dt / 1e6) if do_gi else None,
+            "traced_mrays_per_s": ((rays_total - answered_total) / dt / 1e6) if do_gi else None,
+            "rays_per_frame": {"queries": rays_total / args.steps, "traced": (rays_total - answered_total) / args.steps,
+                               "answered_by_sun_table": answered_total / args.steps} if do_gi else None,
+        }
+        if extra is not None:
+            out.update(full_report(args, extra, fps, own_px, GW, GH, L, world, do_gi, sc))
+        (emit or (lambda line: print(line, flush=True)))(json.dumps(out))
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def measure_beside(rt, args, w, rank, world, do_gi):
+    """--full: what is measured on the headline's own workload `w` after its timed region -> the raw figures full_report turns into fields"""
+    import numpy as np
+    from nebulae_amd.svgf import PLANE_ALBEDO, PLANE_DEPTH, PLANE_NORMAL, PLANE_ROUGH_METAL, PLANE_WORLDPOS
+    r, L = w.r, w.L
+    warmup_run = max(args.warmup, 1)
+    m = {"warmup_run": warmup_run}
     # the settled rate: the same K steps, timed the same way, once the context has run SETTLE_FRAMES frames in all
     settle_run = max(Workload.SETTLE_FRAMES - warmup_run - args.steps, 0)
-    dt_settled, _ = w.timed(args.steps, settle_run)
-    dt_serial = None
+    m["settle_run"] = settle_run
+    m["dt_settled"], _ = w.timed(args.steps, settle_run)
+    m["dt_serial"] = None
     if w.overlap:  # the same K steps with ONE frame in flight (every stage of a frame on the main stream, in order)
         w.force_serial = True
-        dt_serial, _ = w.timed(args.steps, 2)
+        m["dt_serial"], _ = w.timed(args.steps, 2)
         w.force_serial = False
 
     # ---- optional: the same loop with SURVEY.md 8e's final gather of the strips to rank 0 after every frame ----
-    fps_with_gather = None
+    m["fps_with_gather"] = None
     if args.gather and world > 1:
         dtg, _ = w.timed(args.steps, 0, lambda k: (w.step(), r.gather_frame(dst=0)))
-        fps_with_gather = args.steps / dtg
+        m["fps_with_gather"] = args.steps / dtg
 
     # ---- per-kernel durations: HIP events on the launch stream, 8 extra frames with an event pair per pass, and 8 more in
     # which the SVGF chain is bracketed by ONE pair (every event is a packet of its own between two launches).  One GPU: the
@@ -725,6 +805,7 @@ def main(argv=None, rt=None, emit=None):
         return float(np.mean(v[1:-1] if len(v) > 4 else v))
 
     NPROF = 16
+    m["nprof"] = NPROF
     ev, ev2, lt = [], [], []
     if world == 1:
         r.svgf.set_option("svgf_profile", 1)
@@ -750,9 +831,9 @@ def main(argv=None, rt=None, emit=None):
             lt2.append(r.svgf.level_times())
         r.svgf.set_option("svgf_profile", 0)
     rt.synchronize()
-    rays_ev = (r.ray_count(reset=True) if do_gi else 0) // (3 if world == 1 else 2)  # (batches of NPROF frames)
-    answered_ev = (r.sun_table_stats()["rays_answered"] if do_gi else 0) // (3 if world == 1 else 2)
-    t_gi = avg([e["gi0"].elapsed_time(e["gi1"]) for e in ev]) * 1e-3
+    m["rays_ev"] = (r.ray_count(reset=True) if do_gi else 0) // (3 if world == 1 else 2)  # (batches of NPROF frames)
+    m["answered_ev"] = (r.sun_table_stats()["rays_answered"] if do_gi else 0) // (3 if world == 1 else 2)
+    m["t_gi"] = avg([e["gi0"].elapsed_time(e["gi1"]) for e in ev]) * 1e-3
     fused = bracketed = False
     atrous_samples = None
     if world == 1:
@@ -776,121 +857,109 @@ def main(argv=None, rt=None, emit=None):
         # filters a few extra rows: the roofline line is then taken over the levels after the first)
         t_atrous = float(np.mean(per_level if L == 1 else per_level[1:]))
         t_svgf_chain = t_temporal + sum(per_level)
-    own_px = (w.own[1] - w.own[0]) * GW                      # pixels a rank owns
-    gb = noisy = consts = None
+    m.update(fused=fused, bracketed=bracketed, atrous_samples=atrous_samples, per_level=per_level, t_temporal=t_temporal,
+             t_svgf_chain=t_svgf_chain, t_atrous=t_atrous)
+    m["cpu_baseline"] = None
     if rank == 0 and args.cpu_frames > 0 and world == 1:
         gb = {"albedo": r.svgf.download(PLANE_ALBEDO, 0), "rough_metal": r.svgf.download(PLANE_ROUGH_METAL, 0),
               "world_pos": r.svgf.download(PLANE_WORLDPOS, 0), "normal": r.svgf.download(PLANE_NORMAL, 0),
               "depth": r.svgf.download(PLANE_DEPTH, 0)}
         noisy = w.noisy_dev[0].cpu().numpy() if not do_gi else None
         consts = r.global_constants()
-    parallelism = w.parallelism_label()
-    halo_rows = part.halo
-    w.destroy()
+        m["cpu_baseline"] = (gb, consts, noisy)  # (the oracle runs once the GPU work is over)
+    return m
 
+
+def measure_other_legs(rt, args, sc, cam, rank, world, local_rank, group, scheme, link, do_gi):
+    """--full, once the headline's workload is gone: the legs that take workloads of their own"""
+    from nebulae_amd import strips
+    L = args.levels
+    m = {}
     # ---- N > 1: the weak-scaling frame (per-GPU work fixed) and BASELINE.json configs[4] ----
-    weak = None
+    m["weak"] = None
     if world > 1 and not args.no_weak and do_gi:
         a, b = strips.frame_factors(world)
         ww = Workload(rt, args, args.width * a, args.height * b, L, args.spp, sc, cam, rank, world, local_rank, group, scheme=scheme, link=link)
         dtw, rays_w = ww.timed(args.steps, max(args.warmup, 1))
-        weak = {"frames_per_s_1080p_equivalents": args.steps / dtw * world, "global_frames_per_s": args.steps / dtw, "ms_per_frame": dtw / args.steps * 1e3,
-                "mrays_per_s": rays_w / dtw / 1e6, "global_width": args.width * a, "global_height": args.height * b,
-                "rows_per_strip": args.height * b // world, "parallelism": ww.parallelism_label(), "frames_in_flight": ww.frames_in_flight()}
+        m["weak"] = {"frames_per_s_1080p_equivalents": args.steps / dtw * world, "global_frames_per_s": args.steps / dtw, "ms_per_frame": dtw / args.steps * 1e3,
+                     "mrays_per_s": rays_w / dtw / 1e6, "global_width": args.width * a, "global_height": args.height * b,
+                     "rows_per_strip": args.height * b // world, "parallelism": ww.parallelism_label(), "frames_in_flight": ww.frames_in_flight()}
         ww.destroy()
-    config5 = None
+    m["config5"] = None
     if do_gi and (args.config5 or world == 8):
-        config5 = run_config5(rt, args, sc, rank, world, local_rank, group, scheme, link)
+        m["config5"] = run_config5(rt, args, sc, rank, world, local_rank, group, scheme, link)
+    return m
 
-    if rank == 0:
-        fps = args.steps / dt                                 # whole-job frames per second of the ONE frame
-        achieved = ATROUS_BYTES_PX * own_px / t_atrous / 1e9 if t_atrous > 0 else 0.0
-        traffic = measured_traffic(GW, GH, L) if world == 1 else None
-        valu = measured_valu(GW, GH, L) if world == 1 else None
-        if valu and t_atrous > 0:
-            valu["busy_frac"] = valu["issue_us_per_launch"] / (t_atrous * 1e6)
-        svgf_bytes = (TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * L) * own_px
-        # the fused chain's own byte model: temporal reads 60 B + moments / variance writes 6 B + level 0's output 16 B = 82 B/px for
-        # temporal + level 0 together (the accumulated radiance is neither written nor re-read: 46 B/px less), then 46 B/px per level
-        fused_bytes = (TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * max(L - 1, 0)) * own_px
-        frame_gbps = svgf_bytes * world * fps / 1e9
-        out = {
-            "metric": ("denoised frames/s (1920x1080: GI 1 spp + SVGF temporal + a-trous)" if do_gi else
-                       "denoised frames/s (1920x1080: SVGF temporal + a-trous only)"),
-            "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "warmup_run": warmup_run,
-            # a second timed region of the same K steps after `settled_after_frames` frames of this context (value: after W only)
-            "value_settled": args.steps / dt_settled, "ms_per_step_settled": dt_settled / args.steps * 1e3,
-            # ... and with one frame in flight (None when `value` already is that): value's frames overlap the next frame's closest-hit walk
-            "value_one_frame_in_flight": (args.steps / dt_serial) if dt_serial else None,
-            "settled_after_frames": warmup_run + args.steps + settle_run,
-            "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic" if not args.scene else f"scene file {os.path.basename(args.scene)}; synthetic camera",
-            "config": {"workload": workload_label(GW, GH, args.spp, L, do_gi),
-                       "global_width": GW, "global_height": GH, "atrous_levels": L, "spp": args.spp,
-                       "parallelism": parallelism, "link": (link.label() if link is not None else None), "halo_rows": halo_rows, "rows_per_strip": GH // world,
-                       "frames_in_flight": frames_in_flight,
-                       # what the metric's own strong-scaling curve cannot exceed at N strips, before a byte is exchanged: one strip's frame alone on
-                       # a GPU (measured with the exchange stubbed, strips.STRIP_FRAME_US_1080P) -- to read a SCALE_rNN.json against
-                       "strong_scaling_ceiling": (strips.strong_scaling_ceilings() if (GW, GH) == (1920, 1080) else None),
-                       "scene_device_bytes": scene_bytes, "bvh": bvh, "library_build_id": library_build_id()},
-            "frames_per_s_with_final_gather": fps_with_gather,
-            # rays = W H spp (1 + hit fraction) per frame (SURVEY 8d): one bounce ray per pixel + one sun-visibility QUERY per hit.  Most of the
-            # queries are answered by the sun table inside the shade pass; `traced_*` counts only the rays a traverser walked (bounce rays + the
-            # shadow rays left in the lists) -- the figure to read as traverser throughput
-            "mrays_per_s": (rays_total / dt / 1e6) if do_gi else None,
-            "traced_mrays_per_s": ((rays_total - answered_total) / dt / 1e6) if do_gi else None,
-            "gi_kernel_mrays_per_s": (rays_ev / NPROF / t_gi / 1e6) if do_gi else None,
-            "gi_kernel_traced_mrays_per_s": ((rays_ev - answered_ev) / NPROF / t_gi / 1e6) if do_gi else None,
-            "rays_per_frame": {"queries": rays_total / args.steps, "traced": (rays_total - answered_total) / args.steps,
-                               "answered_by_sun_table": answered_total / args.steps} if do_gi else None,
-            "weak_scaling": weak,
-            "config5": config5,
-            "kernel_us": {"gi_trace": t_gi * 1e6, "temporal": None if fused else t_temporal * 1e6,
-                          "fused_temporal_level0": per_level[0] * 1e6 if (fused and L > 0) else None,
-                          "atrous_levels": [t * 1e6 for t in per_level], "svgf_chain": t_svgf_chain * 1e6},
-            "roofline": {"bound": "hbm",
-                         "kernel": (("svgf_atrous_lds_kernel, a pure level (levels 1.. of the fused chain timed as ONE interval of the library's own HIP events on the "
-                                     "launch stream, divided by their number; kernel_us.atrous_levels has an event pair per level, ~2 us of packets each)"
-                                     if bracketed else
-                                     "svgf_atrous_lds_kernel, a pure level (mean over levels 1.. of the fused chain: the library's own HIP events on the launch stream)")
-                                    if fused else "svgf_atrous_lds_kernel (mean over the levels of a frame)"),
-                         "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "algorithmic_bytes_per_launch": ATROUS_BYTES_PX * own_px,
-                         # the per-frame samples behind `achieved` (us per pure level; the average leaves out the largest and the smallest)
-                         "launch_us_samples": atrous_samples,
-                         "traffic": traffic[0] if traffic else None, "traffic_source": traffic[1] if traffic else None,
-                         # the contract prices this kernel against HBM; what binds it in fact is instruction issue
-                         "limiter": "VALU issue: 25 taps x (12 fp32 operations -- ten of them as packed pairs in four taps of five -- + v_log + v_exp) per pixel; the 30 ds_read_b128 per pixel keep the LDS pipe ~75 % busy beside it" if valu else None, "valu": valu},
-            "temporal_roofline": (None if (fused or t_temporal <= 0) else
-                                  {"achieved": TEMPORAL_BYTES_PX * own_px / t_temporal / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                                   "frac": TEMPORAL_BYTES_PX * own_px / t_temporal / 1e9 / HBM_PEAK_GBPS}),
-            # the same byte model over longer intervals: all of SVGF (temporal + L levels: SURVEY 8d's (82 + 46 L) B/px over the
-            # chain's time), the chain's own fused byte model beside it, and the whole frame (GI included in the time, SVGF's
-            # algorithmic bytes only -- the GI stage is not HBM-priced)
-            "svgf_roofline": {"achieved": svgf_bytes / t_svgf_chain / 1e9, "frac": svgf_bytes / t_svgf_chain / 1e9 / HBM_PEAK_GBPS, "unit": "GB/s",
-                              "bytes_per_px": TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * L, "us": t_svgf_chain * 1e6},
-            "svgf_fused_model": ({"bytes_per_px": TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * max(L - 1, 0), "achieved": fused_bytes / t_svgf_chain / 1e9,
-                                  "frac": fused_bytes / t_svgf_chain / 1e9 / HBM_PEAK_GBPS, "unit": "GB/s",
-                                  "fused_launch": {"bytes_per_px": TEMPORAL_BYTES_PX, "us": per_level[0] * 1e6,
-                                                   "frac": TEMPORAL_BYTES_PX * own_px / per_level[0] / 1e9 / HBM_PEAK_GBPS,
-                                                   # the same launch under SURVEY 8d's unfused model: it does the work of the temporal
-                                                   # pass (82 B/px) and of level 0 (46 B/px)
-                                                   "bytes_per_px_8d": TEMPORAL_BYTES_PX + ATROUS_BYTES_PX,
-                                                   "frac_8d": (TEMPORAL_BYTES_PX + ATROUS_BYTES_PX) * own_px / per_level[0] / 1e9 / HBM_PEAK_GBPS,
-                                                   "traffic": traffic[2] if traffic else None},
-                                  "note": "temporal + level 0 as one launch: 60 B read + 6 B moments / variance + 16 B level-0 output = 82 B/px; "
-                                          "the accumulated radiance is never written or re-read"} if (fused and L > 0) else None),
-            "frame_roofline": {"achieved": frame_gbps, "frac": frame_gbps / HBM_PEAK_GBPS, "unit": "GB/s",
-                               "note": "SVGF algorithmic bytes / whole-frame time (GI included)"},
-            "frame_algorithmic_GBps": frame_gbps,
-        }
-        if gb is not None:
-            out["cpu_baseline"] = cpu_baseline(GW, GH, L, args.cpu_frames, gb, consts, sc, noisy, do_gi)
-        (emit or (lambda line: print(line, flush=True)))(json.dumps(out))
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
 
+def full_report(args, m, fps, own_px, GW, GH, L, world, do_gi, sc):
+    """--full: the fields that measure_beside's and measure_other_legs' figures add to rank 0's line"""
+    t_atrous, t_temporal, t_svgf_chain, per_level, fused = m["t_atrous"], m["t_temporal"], m["t_svgf_chain"], m["per_level"], m["fused"]
+    t_gi, rays_ev, answered_ev, NPROF = m["t_gi"], m["rays_ev"], m["answered_ev"], m["nprof"]
+    dt_settled, dt_serial, settle_run = m["dt_settled"], m["dt_serial"], m["settle_run"]
+    achieved = ATROUS_BYTES_PX * own_px / t_atrous / 1e9 if t_atrous > 0 else 0.0
+    traffic = measured_traffic(GW, GH, L) if world == 1 else None
+    valu = measured_valu(GW, GH, L) if world == 1 else None
+    if valu and t_atrous > 0:
+        valu["busy_frac"] = valu["issue_us_per_launch"] / (t_atrous * 1e6)
+    svgf_bytes = (TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * L) * own_px
+    # the fused chain's own byte model: temporal reads 60 B + moments / variance writes 6 B + level 0's output 16 B = 82 B/px for
+    # temporal + level 0 together (the accumulated radiance is neither written nor re-read: 46 B/px less), then 46 B/px per level
+    fused_bytes = (TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * max(L - 1, 0)) * own_px
+    frame_gbps = svgf_bytes * world * fps / 1e9
+    out = {
+        # a second timed region of the same K steps after `settled_after_frames` frames of this context (value: after W only)
+        "value_settled": args.steps / dt_settled, "ms_per_step_settled": dt_settled / args.steps * 1e3,
+        # ... and with one frame in flight (None when `value` already is that): value's frames overlap the next frame's closest-hit walk
+        "value_one_frame_in_flight": (args.steps / dt_serial) if dt_serial else None,
+        "settled_after_frames": m["warmup_run"] + args.steps + settle_run,
+        "frames_per_s_with_final_gather": m["fps_with_gather"],
+        "gi_kernel_mrays_per_s": (rays_ev / NPROF / t_gi / 1e6) if do_gi else None,
+        "gi_kernel_traced_mrays_per_s": ((rays_ev - answered_ev) / NPROF / t_gi / 1e6) if do_gi else None,
+        "weak_scaling": m["weak"],
+        "config5": m["config5"],
+        "kernel_us": {"gi_trace": t_gi * 1e6, "temporal": None if fused else t_temporal * 1e6,
+                      "fused_temporal_level0": per_level[0] * 1e6 if (fused and L > 0) else None,
+                      "atrous_levels": [t * 1e6 for t in per_level], "svgf_chain": t_svgf_chain * 1e6},
+        "roofline": {"bound": "hbm",
+                     "kernel": (("svgf_atrous_lds_kernel, a pure level (levels 1.. of the fused chain timed as ONE interval of the library's own HIP events on the "
+                                 "launch stream, divided by their number; kernel_us.atrous_levels has an event pair per level, ~2 us of packets each)"
+                                 if m["bracketed"] else
+                                 "svgf_atrous_lds_kernel, a pure level (mean over levels 1.. of the fused chain: the library's own HIP events on the launch stream)")
+                                if fused else "svgf_atrous_lds_kernel (mean over the levels of a frame)"),
+                     "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                     "algorithmic_bytes_per_launch": ATROUS_BYTES_PX * own_px,
+                     # the per-frame samples behind `achieved` (us per pure level; the average leaves out the largest and the smallest)
+                     "launch_us_samples": m["atrous_samples"],
+                     "traffic": traffic[0] if traffic else None, "traffic_source": traffic[1] if traffic else None,
+                     # the contract prices this kernel against HBM; what binds it in fact is instruction issue (DESIGN.md 3.2)
+                     "limiter": "VALU issue: 25 taps x (12 fp32 operations -- ten of them as packed pairs in four taps of five -- + v_log + v_exp) per pixel; the 30 ds_read_b128 per pixel keep the LDS pipe ~75 % busy beside it" if valu else None, "valu": valu},
+        "temporal_roofline": (None if (fused or t_temporal <= 0) else
+                              {"achieved": TEMPORAL_BYTES_PX * own_px / t_temporal / 1e9, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": TEMPORAL_BYTES_PX * own_px / t_temporal / 1e9 / HBM_PEAK_GBPS}),
+        # the same byte model over longer intervals: all of SVGF (temporal + L levels: SURVEY 8d's (82 + 46 L) B/px over the
+        # chain's time), the chain's own fused byte model beside it, and the whole frame (GI included in the time, SVGF's
+        # algorithmic bytes only -- the GI stage is not HBM-priced, SURVEY.md 8d)
+        "svgf_roofline": {"achieved": svgf_bytes / t_svgf_chain / 1e9, "frac": svgf_bytes / t_svgf_chain / 1e9 / HBM_PEAK_GBPS, "unit": "GB/s",
+                          "bytes_per_px": TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * L, "us": t_svgf_chain * 1e6},
+        "svgf_fused_model": ({"bytes_per_px": TEMPORAL_BYTES_PX + ATROUS_BYTES_PX * max(L - 1, 0), "achieved": fused_bytes / t_svgf_chain / 1e9,
+                              "frac": fused_bytes / t_svgf_chain / 1e9 / HBM_PEAK_GBPS, "unit": "GB/s",
+                              "fused_launch": {"bytes_per_px": TEMPORAL_BYTES_PX, "us": per_level[0] * 1e6,
+                                               "frac": TEMPORAL_BYTES_PX * own_px / per_level[0] / 1e9 / HBM_PEAK_GBPS,
+                                               # the same launch under SURVEY 8d's unfused model: it does the work of the temporal
+                                               # pass (82 B/px) and of level 0 (46 B/px)
+                                               "bytes_per_px_8d": TEMPORAL_BYTES_PX + ATROUS_BYTES_PX,
+                                               "frac_8d": (TEMPORAL_BYTES_PX + ATROUS_BYTES_PX) * own_px / per_level[0] / 1e9 / HBM_PEAK_GBPS,
+                                               "traffic": traffic[2] if traffic else None},
+                              "note": "temporal + level 0 as one launch: 60 B read + 6 B moments / variance + 16 B level-0 output = 82 B/px; "
+                                      "the accumulated radiance is never written or re-read"} if (fused and L > 0) else None),
+        "frame_roofline": {"achieved": frame_gbps, "frac": frame_gbps / HBM_PEAK_GBPS, "unit": "GB/s",
+                           "note": "SVGF algorithmic bytes / whole-frame time (GI included)"},
+        "frame_algorithmic_GBps": frame_gbps,
+    }
+    if m["cpu_baseline"] is not None:
+        gb, consts, noisy = m["cpu_baseline"]
+        out["cpu_baseline"] = cpu_baseline(GW, GH, L, args.cpu_frames, gb, consts, sc, noisy, do_gi)
+    return out
 
 if __name__ == "__main__":
     main()

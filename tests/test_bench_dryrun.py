@@ -184,7 +184,7 @@ def test_multi_gpu_control_flow_on_cpu(tmp_path, world, scheme):
     # (shrunk) size with its moving-then-still camera; --gather adds the final gather after every frame
     out = tmp_path / "line.json"
     argv = ["--gpus", str(world), "--steps", "2", "--warmup", "2", "--width", "64", "--height", "512", "--cpu-frames", "0", "--triangles", "2000",
-            "--tex-size", "16", "--gather", "--scheme", scheme, "--config5", "--config5-frames", "4", "--config5-size", "64", "512"]
+            "--tex-size", "16", "--full", "--gather", "--scheme", scheme, "--config5", "--config5-frames", "4", "--config5-size", "64", "512"]
     port = 29900 + (os.getpid() % 1500) + world
     # strips this small take the "defer" form of frames in flight (three: two record sets); world 2 is made to take the "split" form a
     # whole frame or a big strip takes (two: neb_gi_trace_begin of the next frame on a side stream)
@@ -228,6 +228,64 @@ def test_multi_gpu_control_flow_on_cpu(tmp_path, world, scheme):
 
 _ARGV = ["--steps", "2", "--warmup", "1", "--width", "64", "--height", "256", "--cpu-frames", "0", "--triangles", "2000", "--tex-size", "16",
          "--no-weak", "--levels", "3"]
+
+# what only --full measures: a plain run must not spend time on any of it
+_FULL_ONLY = ("value_settled", "ms_per_step_settled", "value_one_frame_in_flight", "settled_after_frames", "frames_per_s_with_final_gather",
+              "gi_kernel_mrays_per_s", "weak_scaling", "config5", "kernel_us", "roofline", "temporal_roofline", "svgf_roofline", "svgf_fused_model",
+              "frame_roofline", "frame_algorithmic_GBps", "cpu_baseline")
+
+
+def _dry_run(tmp_path, tag, argv, world=2):
+    out = tmp_path / f"{tag}.json"
+    port = 29900 + (os.getpid() % 1500) + 20 + len(tag)
+    mp.spawn(_rank_main, args=(world, port, argv, str(out)), nprocs=world, join=True)
+    return json.loads(out.read_text())
+
+
+def test_plain_run_reports_the_timed_steps_and_dumps_the_last_frame(tmp_path):
+    """`bench.py --gpus N --steps K --warmup W` without --full: set-up, warm-up, the K timed steps and the headline line, nothing more.
+    --dump-outputs DIR writes the frame the last timed step denoised (the strips gathered to rank 0) as float32; a --full run with the same
+    arguments dumps the very same frame (it is taken before anything else runs), and so does every run with the same arguments."""
+    argv = ["--gpus", "2", "--steps", "3", "--warmup", "1", "--width", "64", "--height", "256", "--cpu-frames", "0", "--triangles", "2000",
+            "--tex-size", "16", "--levels", "3"]
+    d = _dry_run(tmp_path, "plain", argv + ["--dump-outputs", str(tmp_path / "plain")])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in d, k
+    assert not [k for k in _FULL_ONLY if k in d]
+    assert d["steps"] == 3 and d["n_gpus"] == 2 and d["dtype"] == "f32" and d["higher_is_better"] is True
+    assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-9  # one figure, two units: frames/s and ms per timed step
+    frame = np.load(tmp_path / "plain" / "radiance.npy")
+    assert frame.dtype == np.float32 and frame.shape == (256, 64, 4) and np.isfinite(frame).all() and np.abs(frame).max() > 0
+    full = _dry_run(tmp_path, "full", argv + ["--full", "--dump-outputs", str(tmp_path / "full")])
+    assert full["kernel_us"] and full["weak_scaling"] and full["value_settled"] > 0
+    assert np.array_equal(np.load(tmp_path / "full" / "radiance.npy"), frame)
+
+
+def test_bench_arguments():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse(["--steps", "7"]).steps == 7 and not bench.parse([]).full and bench.parse([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--gather"], ["--config5"]):  # (the gather and config-5 legs are part of --full)
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+    a = bench.parse(["--full", "--gather", "--config5", "--dump-outputs", "d"])
+    assert a.full and a.gather and a.config5 and a.dump_outputs == "d"
+
+
+def test_dump_outputs_keeps_a_fixed_sample_of_a_frame_past_the_cap(tmp_path, monkeypatch):
+    sys.path.insert(0, ROOT)
+    import bench
+    frame = np.random.default_rng(5).standard_normal((48, 40, 4)).astype(np.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), {"radiance": frame})
+    whole = np.load(tmp_path / "whole" / "radiance.npy")
+    assert whole.dtype == np.float32 and np.array_equal(whole, frame.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4096)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"radiance": frame})
+    a, b = np.load(tmp_path / "a" / "radiance.npy"), np.load(tmp_path / "b" / "radiance.npy")
+    assert a.dtype == np.float32 and a.nbytes <= 4096 and a.shape == (256, 4) and np.array_equal(a, b)
+    rows = whole.reshape(-1, 4)
+    assert all(any(np.array_equal(p, q) for q in rows) for p in a[:16])  # pixels of the frame, not some other numbers
 
 
 def test_launcher_starts_the_ranks_and_relays_rank0s_line():

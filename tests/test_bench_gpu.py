@@ -5,7 +5,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+from test_bench_dryrun import _FULL_ONLY
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +20,7 @@ def _last_json(out):
 
 
 def test_single_gpu_line():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--cpu-frames", "1"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "4", "--warmup", "2", "--cpu-frames", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
@@ -46,9 +48,27 @@ def test_single_gpu_line():
     assert 0 < d["frame_roofline"]["frac"] < d["svgf_roofline"]["frac"] < 1
 
 
+def test_plain_line_and_the_dumped_frame(tmp_path):
+    """A plain run: the headline line and nothing that only --full measures.  --dump-outputs: the frame the last timed step denoised, float32,
+    the same from run to run (seeded scene, fixed camera and frame indices)."""
+    frames = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--tex-size", "256",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = _last_json(p.stdout)
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["dtype"] == "f32" and d["higher_is_better"] is True and d["value"] > 0
+        assert abs(d["value"] * d["ms_per_step"] * 1e-3 - 1.0) < 1e-9
+        assert not [k for k in _FULL_ONLY if k in d]
+        frames.append(np.load(tmp_path / run / "radiance.npy"))
+    a, b = frames
+    assert a.dtype == np.float32 and a.shape == (1080, 1920, 4) and np.isfinite(a).all() and a[..., :3].max() > 0
+    assert np.array_equal(a, b)
+
+
 def test_single_gpu_line_with_the_separate_kernels():
     """NEB_BENCH_NO_FUSE=1: option svgf_fuse = 0 -- the temporal pass as its own kernel, level times still from the library's events."""
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--cpu-frames", "0", "--tex-size", "256"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--cpu-frames", "0", "--tex-size", "256", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=dict(os.environ, NEB_BENCH_NO_FUSE="1"))
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
@@ -81,7 +101,7 @@ def test_two_rank_rehearsal(scheme):
     launcher = [] if scheme == "once" else ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                                             "--master-port", str(29650 + (os.getpid() % 200))]
     cmd = [sys.executable] + launcher + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--cpu-frames", "0", "--gather", "--tex-size", "256"] + (["--config5", "--config5-frames", "4"] if scheme == "once" else [])
+           "--cpu-frames", "0", "--full", "--gather", "--tex-size", "256"] + (["--config5", "--config5-frames", "4"] if scheme == "once" else [])
     env = {k: v for k, v in env.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]

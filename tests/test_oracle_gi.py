@@ -1,5 +1,5 @@
 """CPU tests of the GI oracle: RNG known answers, format helpers, brute-force cross-check of its BVH,
-and the real reference assets (cornell_box, DamagedHelmet) when /root/reference is mounted."""
+and the real reference assets (cornell_box, DamagedHelmet) as committed under tests/golden/."""
 import ctypes as C
 import os
 
@@ -10,7 +10,10 @@ from nebulae_amd import scene as S
 from nebulae_amd import synth
 from oracle_lib import OracleTracer, _trace_lib
 
-REF = "/root/reference/assets"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+# the reference's assets as binary glTF fixtures (tests/golden/README.md): cornell_box bit for bit, DamagedHelmet's geometry with its
+# three original JPEG maps embedded byte for byte
+ASSET_FIXTURES = {"cornell_box/cornell_box.gltf": "cornell_box.glb", "DamagedHelmet/DamagedHelmet.gltf": "DamagedHelmet_jpeg.glb"}
 
 
 def test_r11g11b10_roundtrip_and_known_values():
@@ -130,10 +133,12 @@ def test_oracle_bvh_against_brute_force():
         assert 0.0 <= depth[y, x] <= 1.0
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference assets not mounted (GPU box)")
 @pytest.mark.parametrize("asset,tris,geoms", [("cornell_box/cornell_box.gltf", 34, 3), ("DamagedHelmet/DamagedHelmet.gltf", 15452, 1)])
 def test_reference_assets_load_and_trace(asset, tris, geoms):
-    sc = S.load_gltf(os.path.join(REF, asset))
+    path = os.path.join(GOLDEN, ASSET_FIXTURES[asset])
+    if not os.path.exists(path):
+        pytest.skip(f"tests/golden/{ASSET_FIXTURES[asset]} is not present (an optional third-party asset: tests/golden/README.md)")
+    sc = S.load_gltf(path)
     assert sc.num_triangles == tris and len(sc.geometries) == geoms
     o = OracleTracer(sc, threads=4)
     cam = S.orbit_camera()

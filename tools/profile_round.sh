@@ -14,7 +14,7 @@ root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp && cd "$root"
 out=gpurun_out/$tag
 rm -rf "$out" && mkdir -p "$out" profiles
-python bench.py $extra > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 1; }
+python bench.py --full $extra > "$out/bench.json" 2> "$out/bench.err" || { tail -20 "$out/bench.err"; exit 1; }
 echo "[profile_round] bench done"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/stats" -- python bench.py --steps 32 --warmup 8 --cpu-frames 0 --overlap off $extra > "$out/stats.log" 2>&1 || { tail -20 "$out/stats.log"; exit 1; }
 echo "[profile_round] kernel trace done"
@@ -48,7 +48,7 @@ for f in glob.glob(f"profiles/{tag}_*.json"):
         json.dump(d, open(f, "w"), indent=1)
 PY
 # the bench line once more, now that this build's counter summaries exist: it quotes them (roofline.traffic / .valu)
-python bench.py $extra > "$out/bench2.json" 2>> "$out/bench.err" && cp "$out/bench2.json" "profiles/${tag}_bench.json"
+python bench.py --full $extra > "$out/bench2.json" 2>> "$out/bench.err" && cp "$out/bench2.json" "profiles/${tag}_bench.json"
 mkdir -p "$out/profiles" && cp profiles/${tag}_* "$out/profiles/"
 python - "$tag" <<'PY'
 import csv, sys
