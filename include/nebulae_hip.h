@@ -55,7 +55,10 @@ typedef enum neb_plane {
     NEB_PLANE_GEOMETRY = 10,   /* R32G32B32A32_FLOAT 16 B/px, 1 slot: {decoded shading normal.xyz, depth in [0,1]} of the current frame.
                                   No reference counterpart: the temporal pass decodes normal[cur] / depth[cur] once per frame and the
                                   a-trous levels read this instead of decoding them five times (read-only for callers). */
-    NEB_PLANE_COUNT = 11
+    NEB_PLANE_HISTORY_LENGTH = 11, /* R8_UINT 1 B/px, 2 slots: frames of valid history per pixel, saturating at 255.  No reference
+                                      counterpart: exists only while option "svgf_reproject" is 1 (see neb_svgf_set_camera);
+                                      neb_get_plane / uploads / downloads of it return NEB_ERR_STATE otherwise. */
+    NEB_PLANE_COUNT = 12
 } neb_plane;
 
 /* Slot selectors for the 2-slot (ping-pong) planes. */
@@ -134,7 +137,10 @@ int neb_svgf_get_params(const neb_ctx* ctx, neb_svgf_params* out);
  *   "gi_sun_hints":     4 (default), 2 or 0: how many of a triangle's occluder hints the shade pass tries (with the traverser's own
  *                       triangle test) before it leaves the shadow ray to the list pass; results are bit-identical in all three;
  *   "gi_max_bvh_depth": 1..21, the deepest BVH4 neb_gi_build_bvh accepts (default 21 = traversal stack / 3);
- *   "svgf_fuse":        0 (default) / 1 (opt-in), see neb_svgf_atrous;   "svgf_profile": 0 (default) / 1 / 2, see neb_svgf_level_times. */
+ *   "svgf_fuse":        0 (default) / 1 (opt-in), see neb_svgf_atrous;   "svgf_profile": 0 (default) / 1 / 2, see neb_svgf_level_times;
+ *   "svgf_reproject":   0 (default) / 1 (opt-in): the temporal pass reprojects the history through the two frames' cameras, see
+ *                       neb_svgf_set_camera.  NEB_ERR_STATE on a row-strip context.  1 allocates the (zeroed) history-length plane,
+ *                       0 frees it: a context switched on and off again computes what a context that never had it on computes. */
 int neb_set_option(neb_ctx* ctx, const char* key, int value);
 
 /* ---- resource sharing: the ~25 getters of SVGFDenoiser.h:24-70 collapse into one call.
@@ -185,6 +191,34 @@ int neb_svgf_denoise(neb_ctx* ctx, neb_stream stream);
  * the chain ran fused), *n_out = how many.  With "svgf_profile" = 2 only three events are recorded and two durations returned:
  * the first kernel, and all the others together (an event between two launches costs about 2 us of its own). */
 int neb_svgf_level_times(neb_ctx* ctx, float* out_us, uint32_t capacity, uint32_t* n_out);
+/* ---- Temporal reprojection (option "svgf_reproject" = 1; no reference counterpart: the reference's temporal pass reads the history at
+ * the same pixel, SURVEY.md quirk 3, so a moving camera either skips SVGF or ghosts).  In this mode every temporal pass -- neb_svgf_temporal,
+ * neb_svgf_denoise, neb_svgf_temporal_rows (whole frame only) -- runs the reprojecting kernel.  Per pixel p of the dispatch region
+ * [0,Wd) x [0,Hd) (Wd = W/8*8, Hd = H/8*8, as the same-pixel pass):
+ *   mapping:  P = the world point of p, rebuilt from depth[cur] and the camera of cur by inverting neb_gbuffer_raycast's projection
+ *             (pixel centre (x+0.5)/W, the same axes, linear depth -z_view = m32 / (d + m22)); a pixel with no surface (D24 = 0xFFFFFF)
+ *             takes no history.  P is projected with the camera of hist to a continuous pixel position q; its bilinear taps are
+ *             floor(q - 0.5) + {0,1}^2.
+ *   validity: a tap counts when it lies in [0,Wd) x [0,Hd), depth[hist] holds a surface there, the geometric normals (normal.xy) of p and
+ *             of the tap have dot >= 0.9, and the tap's own world point P_t (from depth[hist] and the camera of hist) lies on p's plane:
+ *             |dot(P_t - P, N_p)| <= 0.01 x the linear depth of P in the camera of hist (plane distance, not depth difference: grazing
+ *             floors keep their history).
+ *   blend:    radiance[hist] and moments[hist] are resampled as the bilinear-weighted, renormalised mean over the valid taps, and
+ *             n = the largest history_length[hist] among them (n = 0 with no valid tap or a total weight <= 1e-4).  History weight
+ *             a = n == 0 ? 0 : min(alpha, 1 - 1/(n+1)) -- a cumulative mean until it reaches alpha; radiance[cur] = lerp(current,
+ *             history, a), moments likewise, variance = max(M2 - M1^2, varianceEps), history_length[cur] = min(n + 1, 255).
+ *             depthSigma plays no part, nor does quirk 2 (the same-pixel pass keeps 100 % history where depth and normals disagree).
+ * Which calls behave differently: neb_svgf_temporal enqueues the pass at once, even with "svgf_fuse" = 1, and neb_svgf_atrous /
+ * neb_svgf_denoise run the separate levels (the "svgf_fuse" = 0 kernels: the same bits as with the option 0); neb_svgf_reset_history
+ * also zeroes history_length[hist]; neb_svgf_temporal_rows on less than the whole frame and neb_strip_frame* return NEB_ERR_STATE.
+ * A temporal pass with no camera recorded for cur returns NEB_ERR_STATE; with none for hist it is no error: the pass takes no history.
+ *
+ * neb_svgf_set_camera records the camera that slot `slot` (0, 1, NEB_SLOT_CURRENT or NEB_SLOT_HISTORY, resolved at the call) of the depth
+ * and normal planes was rendered with.  neb_gbuffer_raycast records its camera for cur by itself; a host with its own raster G-buffer
+ * (the reference: InspectCamera eye / target / up, 60 degrees, 0.1, 100 -- src/DeferredRenderer.cpp:133-148) calls this once per frame,
+ * after neb_begin_frame, with slot NEB_SLOT_CURRENT.  neb_resize forgets both cameras.  NEB_ERR_INVALID_ARG for a bad slot or camera. */
+struct neb_camera;
+int neb_svgf_set_camera(neb_ctx* ctx, int slot, const struct neb_camera* cam);
 /* Row-range forms for multi-GPU row strips (no reference counterpart):
  * image rows [row0,row1) must be resident, and for the a-trous level so must every
  * (globally clamped) tap row.  `level` picks step = 1 << level and the source/destination

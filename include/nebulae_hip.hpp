@@ -81,6 +81,12 @@ namespace Neb
         void SubmitDenoising(neb_stream commandList) { ThrowIfFailed(m_ctx, neb_svgf_denoise(m_ctx, commandList), "neb_svgf_denoise"); }
         // Implementation knobs without a reference counterpart ("svgf_fuse", "svgf_profile", "atrous_variant", the "gi_*" options)
         void SetOption(const char* key, int value) { ThrowIfFailed(m_ctx, neb_set_option(m_ctx, key, value), "neb_set_option"); }
+        // Option "svgf_reproject" = 1: the camera the slot's depth / normal planes were rendered with (NEB_SLOT_CURRENT once per frame,
+        // after BeginFrame, for a host with its own raster G-buffer -- see neb_svgf_set_camera and INTEGRATION.md)
+        void SetCamera(int slot, const neb_camera& camera)
+        {
+            ThrowIfFailed(m_ctx, neb_svgf_set_camera(m_ctx, slot, &camera), "neb_svgf_set_camera");
+        }
         // Durations (us) of the kernels of the last SubmitATrousComputeWavelet chain, after SetOption("svgf_profile", 1); returns how many
         uint32_t LevelTimes(float* outMicroseconds, uint32_t capacity)
         {

@@ -11,6 +11,7 @@ from . import build as _build
 NEB_OK = 0
 PLANE_RADIANCE, PLANE_NORMAL, PLANE_DEPTH, PLANE_MOMENTS, PLANE_VARIANCE, PLANE_SCRATCH = 0, 1, 2, 3, 4, 5
 PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY = 6, 7, 8, 9, 10
+PLANE_HISTORY_LENGTH = 11  # only while option svgf_reproject is 1
 SLOT_CURRENT, SLOT_HISTORY = -1, -2
 
 
@@ -120,6 +121,7 @@ def _gi_sigs():
         "neb_pbr_direct": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p]),
         "neb_tonemap": (C.c_int, [C.c_void_p, C.c_void_p]),
         "neb_gbuffer_raycast": (C.c_int, [C.c_void_p, C.POINTER(S.CameraDesc), C.c_void_p]),
+        "neb_svgf_set_camera": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(S.CameraDesc)]),
         "neb_strip_frame": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p, C.POINTER(StripPlan), C.c_void_p]),
         "neb_strip_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),
         "neb_strip_frame_finish": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),

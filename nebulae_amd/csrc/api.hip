@@ -21,6 +21,7 @@ const PlaneInfo kPlaneInfo[NEB_PLANE_COUNT] = {
     {8, 1},  // WORLDPOS     R16G16B16A16_FLOAT
     {4, 1},  // LDR          R8G8B8A8_UNORM
     {16, 1}, // GEOMETRY     R32G32B32A32_FLOAT (decoded shading normal + depth of the current frame)
+    {1, 2},  // HISTORY_LENGTH R8_UINT (only while option svgf_reproject is 1: alloc_history_length)
 };
 } // namespace neb
 
@@ -107,11 +108,33 @@ static int alloc_planes(neb_ctx* ctx)
     // (SURVEY.md quirk 8); this build defines zero-initialised planes.
     const size_t npx = (size_t)ctx->W * (ctx->row_end - ctx->row_begin);
     for (int p = 0; p < NEB_PLANE_COUNT; ++p)
-        for (uint32_t s = 0; s < kPlaneInfo[p].slots; ++s) {
+        for (uint32_t s = 0; p != NEB_PLANE_HISTORY_LENGTH && s < kPlaneInfo[p].slots; ++s) {
             const size_t bytes = npx * kPlaneInfo[p].bytes_per_px;
             NEB_HIP(ctx, hipMalloc(&ctx->planes[p][s], bytes));
             NEB_HIP(ctx, hipMemset(ctx->planes[p][s], 0, bytes));
         }
+    NEB_HIP(ctx, hipDeviceSynchronize());
+    return NEB_OK;
+}
+
+// option svgf_reproject: the history-length plane exists only while it is on (zeroed: no pixel has history yet)
+static void free_history_length(neb_ctx* ctx)
+{
+    for (int s = 0; s < 2; ++s)
+        if (ctx->planes[NEB_PLANE_HISTORY_LENGTH][s]) {
+            (void)hipFree(ctx->planes[NEB_PLANE_HISTORY_LENGTH][s]);
+            ctx->planes[NEB_PLANE_HISTORY_LENGTH][s] = nullptr;
+        }
+}
+
+static int alloc_history_length(neb_ctx* ctx)
+{
+    const size_t bytes = (size_t)ctx->W * (ctx->row_end - ctx->row_begin);
+    for (int s = 0; s < 2; ++s) {
+        if (!ctx->planes[NEB_PLANE_HISTORY_LENGTH][s])
+            NEB_HIP(ctx, hipMalloc(&ctx->planes[NEB_PLANE_HISTORY_LENGTH][s], bytes));
+        NEB_HIP(ctx, hipMemset(ctx->planes[NEB_PLANE_HISTORY_LENGTH][s], 0, bytes));
+    }
     NEB_HIP(ctx, hipDeviceSynchronize());
     return NEB_OK;
 }
@@ -184,7 +207,10 @@ int neb_resize(neb_ctx* ctx, uint32_t width, uint32_t height)
     ctx->H = height;
     ctx->row_begin = 0;
     ctx->row_end = height;
-    return alloc_planes(ctx);
+    ctx->has_cam[0] = ctx->has_cam[1] = false; // (the cameras belonged to the old planes)
+    if (int rc = alloc_planes(ctx))
+        return rc;
+    return ctx->reproject ? alloc_history_length(ctx) : NEB_OK;
 }
 
 int neb_destroy(neb_ctx* ctx)
@@ -295,6 +321,26 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
         ctx->fuse = value;
         return NEB_OK;
     }
+    if (!strcmp(key, "svgf_reproject")) {
+        if (value < 0 || value > 1)
+            return fail(ctx, NEB_ERR_INVALID_ARG, "neb_set_option: svgf_reproject must be 0 or 1");
+        if (value && (ctx->row_begin != 0 || ctx->row_end != ctx->H))
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_reproject needs a whole-frame context (row strips are not supported)");
+        if (value == ctx->reproject)
+            return NEB_OK;
+        NEB_GUARD(ctx);
+        if (value) {
+            if (int rc = alloc_history_length(ctx)) {
+                free_history_length(ctx);
+                return rc;
+            }
+        } else {
+            NEB_HIP(ctx, hipDeviceSynchronize()); // (work already enqueued may still read the plane)
+            free_history_length(ctx);
+        }
+        ctx->reproject = value;
+        return NEB_OK;
+    }
     if (!strcmp(key, "gi_sort_rays")) {
         if (gi_set_sort_rays(ctx, value) != NEB_OK)
             return fail(ctx, NEB_ERR_STATE, "neb_set_option: gi_sort_rays needs a scene and a mask 0..3 (bit 0 shadow rays, bit 1 bounce rays)");
@@ -358,6 +404,8 @@ int neb_get_plane(neb_ctx* ctx, int plane, int slot, void** dptr, size_t* pitch_
     const int s = resolve_slot(ctx, plane, slot);
     if (s < 0)
         return fail(ctx, NEB_ERR_INVALID_ARG, "neb_get_plane: bad plane/slot");
+    if (!ctx->planes[plane][s])
+        return fail(ctx, NEB_ERR_STATE, "neb_get_plane: the history-length plane exists only while option svgf_reproject is 1");
     if (int rc = svgf_flush_pending(ctx))
         return rc;
     if (plane == NEB_PLANE_NORMAL || plane == NEB_PLANE_DEPTH)
@@ -378,6 +426,8 @@ static int copy_rows(neb_ctx* ctx, int plane, int slot, uint32_t row0, uint32_t 
     const int s = resolve_slot(ctx, plane, slot);
     if (s < 0)
         return fail(ctx, NEB_ERR_INVALID_ARG, "copy rows: bad plane/slot");
+    if (!ctx->planes[plane][s])
+        return fail(ctx, NEB_ERR_STATE, "copy rows: the history-length plane exists only while option svgf_reproject is 1");
     if (row0 < ctx->row_begin || row0 + nrows > ctx->row_end)
         return fail(ctx, NEB_ERR_OUT_OF_RANGE, "copy rows: rows not resident in this context");
     if (int rc = svgf_flush_pending(ctx))
@@ -428,6 +478,9 @@ int neb_svgf_reset_history(neb_ctx* ctx, neb_stream stream)
     const size_t bytes = (size_t)ctx->W * (ctx->row_end - ctx->row_begin) * 16;
     NEB_HIP(ctx, hipMemcpyAsync(ctx->planes[NEB_PLANE_RADIANCE][ctx->hist], ctx->planes[NEB_PLANE_RADIANCE][ctx->cur],
                                 bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (ctx->reproject) // reprojection mode: no pixel has history any more
+        NEB_HIP(ctx, hipMemsetAsync(ctx->planes[NEB_PLANE_HISTORY_LENGTH][ctx->hist], 0, (size_t)ctx->W * (ctx->row_end - ctx->row_begin),
+                                    (hipStream_t)stream));
     return NEB_OK;
 }
 
@@ -527,6 +580,31 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
     // the pass also leaves normal[cur] / depth[cur] decoded in the geometry plane for the a-trous levels -- for the pixels it
     // covers: with a ragged right / bottom remainder (Dispatch(W/8, H/8) floors) the levels' taps clamp into pixels it skips
     const bool fused_geometry = (ctx->W % 8u) == 0 && (ctx->H % 8u) == 0;
+    if (ctx->reproject) {
+        // reprojected taps may come from any row: whole frames only (a strip context cannot turn the option on)
+        if (row0 != 0 || row1 != ctx->H)
+            return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal_rows: with option svgf_reproject the temporal pass covers the whole frame");
+        if (!ctx->has_cam[c])
+            return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal: svgf_reproject needs the camera of the current frame (neb_svgf_set_camera)");
+        if (!ctx->planes[NEB_PLANE_HISTORY_LENGTH][0] || !ctx->planes[NEB_PLANE_HISTORY_LENGTH][1])
+            return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal: the history-length plane is missing (a failed resize?)");
+        const CameraBasis bc = camera_basis(ctx->cams[c], ctx->W, ctx->H);
+        const CameraBasis bh = ctx->has_cam[h] ? camera_basis(ctx->cams[h], ctx->W, ctx->H) : bc;
+        hipError_t e = launch_temporal_reproject(make_launch(ctx, row0, row1), bc, ctx->has_cam[h] ? &bh : nullptr,
+                                                 (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
+                                                 (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c], (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][h],
+                                                 (const uint2*)ctx->planes[NEB_PLANE_NORMAL][c], (const uint2*)ctx->planes[NEB_PLANE_NORMAL][h],
+                                                 (const uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][h], (uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][c],
+                                                 (uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
+                                                 (const uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][h],
+                                                 (uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][c],
+                                                 fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, (hipStream_t)stream);
+        if (e != hipSuccess)
+            return fail(ctx, NEB_ERR_HIP, "svgf_temporal_reproject launch", e);
+        if (fused_geometry)
+            geometry_mark(ctx, row0, row1);
+        return NEB_OK;
+    }
     hipError_t e = launch_temporal(make_launch(ctx, row0, row1), (float4*)ctx->planes[NEB_PLANE_RADIANCE][c],
                                    (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
                                    (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c],
@@ -546,8 +624,11 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
 
 // Can this context's next frame run as the fused chain (temporal pass inside level 0, intermediate planes carrying the
 // luminance)?  A whole frame whose every pixel both passes cover (Dispatch(W/8, H/8) floors), every level on the LDS kernel.
+// Not in reprojection mode: its temporal pass is a kernel of its own, followed by the separate levels.
 static bool fused_chain_possible(const neb_ctx* ctx)
 {
+    if (ctx->reproject)
+        return false;
     if (ctx->row_begin != 0 || ctx->row_end != ctx->H || (ctx->W % 8u) || (ctx->H % 8u) || ctx->levels == 0)
         return false;
     const SvgfLaunch L = make_launch(ctx, 0, ctx->H);
@@ -695,6 +776,22 @@ int neb_svgf_denoise(neb_ctx* ctx, neb_stream stream)
     if (int rc = neb_svgf_temporal_rows(ctx, ctx->row_begin, ctx->row_end, stream))
         return rc;
     return neb_svgf_atrous(ctx, stream);
+}
+
+int neb_svgf_set_camera(neb_ctx* ctx, int slot, const neb_camera* cam)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    if (!cam)
+        return fail(ctx, NEB_ERR_INVALID_ARG, "neb_svgf_set_camera: null camera");
+    const int s = resolve_slot(ctx, NEB_PLANE_DEPTH, slot);
+    if (s < 0)
+        return fail(ctx, NEB_ERR_INVALID_ARG, "neb_svgf_set_camera: slot must be 0, 1, NEB_SLOT_CURRENT or NEB_SLOT_HISTORY");
+    if (!(cam->vfov_deg > 0.f && cam->vfov_deg < 180.f) || !(cam->znear > 0.f) || !(cam->zfar > cam->znear))
+        return fail(ctx, NEB_ERR_INVALID_ARG, "neb_svgf_set_camera: need 0 < vfov_deg < 180 and 0 < znear < zfar");
+    ctx->cams[s] = *cam;
+    ctx->has_cam[s] = true;
+    return NEB_OK;
 }
 
 int neb_svgf_level_times(neb_ctx* ctx, float* out_us, uint32_t capacity, uint32_t* n_out)

@@ -1473,27 +1473,17 @@ int neb_gbuffer_raycast(neb_ctx* ctx, const neb_camera* cam, neb_stream stream)
         return gi_fail(ctx, NEB_ERR_STATE, "neb_gbuffer_raycast: scene/BVH not ready");
     GI_GUARD(ctx);
     ScopedRange range("Deferred G-Buffers (geometry)"); // DeferredRenderer.cpp:267
-    auto norm = [](float* v) {
-        const float l = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
-        v[0] /= l;
-        v[1] /= l;
-        v[2] /= l;
-    };
     GbufArgs a;
     a.S = g->view;
-    float z[3] = {cam->eye[0] - cam->target[0], cam->eye[1] - cam->target[1], cam->eye[2] - cam->target[2]};
-    norm(z);
-    float x[3] = {cam->up[1] * z[2] - cam->up[2] * z[1], cam->up[2] * z[0] - cam->up[0] * z[2], cam->up[0] * z[1] - cam->up[1] * z[0]};
-    norm(x);
-    const float y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
-    memcpy(a.eye, cam->eye, 12);
-    memcpy(a.xaxis, x, 12);
-    memcpy(a.yaxis, y, 12);
-    memcpy(a.zaxis, z, 12);
-    a.tan_half = tanf(cam->vfov_deg * (3.14159265f / 180.0f) * 0.5f);
-    a.aspect = (float)ctx->W / (float)ctx->H;
-    a.m22 = cam->zfar / (cam->znear - cam->zfar); // XMMatrixPerspectiveFovRH
-    a.m32 = cam->znear * cam->zfar / (cam->znear - cam->zfar);
+    const CameraBasis b = camera_basis(*cam, ctx->W, ctx->H);
+    memcpy(a.eye, b.eye, 12);
+    memcpy(a.xaxis, b.xaxis, 12);
+    memcpy(a.yaxis, b.yaxis, 12);
+    memcpy(a.zaxis, b.zaxis, 12);
+    a.tan_half = b.tan_half;
+    a.aspect = b.aspect;
+    a.m22 = b.m22;
+    a.m32 = b.m32;
     a.albedo = (uint32_t*)ctx->planes[NEB_PLANE_ALBEDO][0];
     a.rough_metal = (uint32_t*)ctx->planes[NEB_PLANE_ROUGH_METAL][0];
     a.world_pos = (uint2*)ctx->planes[NEB_PLANE_WORLDPOS][0];
@@ -1507,6 +1497,8 @@ int neb_gbuffer_raycast(neb_ctx* ctx, const neb_camera* cam, neb_stream stream)
     a.tiles_x = (ctx->W + 7) / 8;
     const uint32_t tiles_y = (a.row1 - a.row0 + 7) / 8;
     ctx->geom_lo = ctx->geom_hi = 0; // normal[cur] / depth[cur] change: the decoded geometry plane is stale
+    ctx->cams[ctx->cur] = *cam; // (what the reprojecting temporal pass maps depth[cur] back with)
+    ctx->has_cam[ctx->cur] = true;
     hipLaunchKernelGGL(gbuffer_kernel, dim3(a.tiles_x * tiles_y), dim3(64), 0, (hipStream_t)stream, a);
     GI_HIP(ctx, hipGetLastError());
     return NEB_OK;

@@ -1,6 +1,7 @@
 // neb_internal.h -- context layout and kernel launchers behind the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <string>
 #include <vector>
@@ -80,6 +81,47 @@ hipError_t launch_atrous_lum(const SvgfLaunch& L, uint32_t step, bool last, cons
 hipError_t launch_atrous_fused_temporal(const SvgfLaunch& L, bool only_level, const float4* rad_cur, const float4* rad_hist, const uint32_t* depth_cur,
                                         const uint32_t* depth_hist, const uint2* normal_cur, const uint2* normal_hist, const uint32_t* mom_hist,
                                         uint32_t* mom_cur, uint16_t* variance, float4* geometry, float4* dst, hipStream_t s);
+// A camera as neb_gbuffer_raycast's kernel uses it: eye, the view axes (z points from the target to the eye), tan(vfov / 2), aspect and
+// the two depth-mapping entries of XMMatrixPerspectiveFovRH.  One host function builds it for the G-buffer producer and for the
+// reprojecting temporal pass, so that both see the same float bits.
+struct CameraBasis {
+    float eye[3], xaxis[3], yaxis[3], zaxis[3];
+    float tan_half, aspect, m22, m32;
+};
+inline CameraBasis camera_basis(const neb_camera& cam, uint32_t W, uint32_t H)
+{
+    auto norm = [](float* v) {
+        const float l = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
+        v[0] /= l;
+        v[1] /= l;
+        v[2] /= l;
+    };
+    CameraBasis b;
+    float z[3] = {cam.eye[0] - cam.target[0], cam.eye[1] - cam.target[1], cam.eye[2] - cam.target[2]};
+    norm(z);
+    float x[3] = {cam.up[1] * z[2] - cam.up[2] * z[1], cam.up[2] * z[0] - cam.up[0] * z[2], cam.up[0] * z[1] - cam.up[1] * z[0]};
+    norm(x);
+    const float y[3] = {z[1] * x[2] - z[2] * x[1], z[2] * x[0] - z[0] * x[2], z[0] * x[1] - z[1] * x[0]};
+    for (int k = 0; k < 3; ++k) {
+        b.eye[k] = cam.eye[k];
+        b.xaxis[k] = x[k];
+        b.yaxis[k] = y[k];
+        b.zaxis[k] = z[k];
+    }
+    b.tan_half = tanf(cam.vfov_deg * (3.14159265f / 180.0f) * 0.5f);
+    b.aspect = (float)W / (float)H;
+    b.m22 = cam.zfar / (cam.znear - cam.zfar); // XMMatrixPerspectiveFovRH
+    b.m32 = cam.znear * cam.zfar / (cam.znear - cam.zfar);
+    return b;
+}
+
+// Reprojecting temporal pass (option svgf_reproject, whole-frame contexts): see neb_svgf_set_camera in nebulae_hip.h.
+// cam_hist == nullptr: no camera for the history slot -- the pass takes no history.
+hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
+                                     const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
+                                     const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
+                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s);
+
 // decodes depth / normal rows [row0, row1) (all W columns) into the geometry plane
 hipError_t launch_decode_geometry(uint32_t W, uint32_t row_begin, uint32_t row0, uint32_t row1, const uint32_t* depth, const uint2* normal,
                                   float4* geometry, hipStream_t s);
@@ -125,6 +167,9 @@ struct neb_ctx {
     int profile = 0;                   // option svgf_profile: neb_svgf_atrous brackets its kernels with events (neb_svgf_level_times)
     std::vector<hipEvent_t> prof_events; // levels + 1 of them once profiling has run
     uint32_t prof_recorded = 0;
+    int reproject = 0;                 // option svgf_reproject: the temporal pass reprojects (planes[NEB_PLANE_HISTORY_LENGTH] exist only then)
+    neb_camera cams[2] = {};           // neb_svgf_set_camera / neb_gbuffer_raycast: the camera each slot's depth / normal planes were rendered with
+    bool has_cam[2] = {false, false};
     neb::GiState* gi = nullptr;
     // neb_strip_frame* (strips.hip): a side stream for the halo exchange beside level 0, and the events that order it -- created on first use
     struct StripSync {

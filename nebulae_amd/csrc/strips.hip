@@ -196,6 +196,8 @@ int neb_strips_exchange(neb_ctx* ctx, void* comm, const neb_halo_plane* planes, 
             slot = ctx->hist;
         if (slot != 0 && slot != 1)
             return strip_fail(ctx, NEB_ERR_INVALID_ARG, "neb_strips_exchange: bad slot");
+        if (!ctx->planes[pl][slot])
+            return strip_fail(ctx, NEB_ERR_STATE, "neb_strips_exchange: plane not allocated (history length without svgf_reproject)");
     }
     for (uint32_t k = 0; k < n_swaps; ++k) {
         const neb_halo_swap& s = swaps[k];
@@ -397,6 +399,8 @@ int neb_strip_frame_begin(neb_ctx* ctx, const neb_gi_constants* constants, const
 {
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
+    if (ctx->reproject) // (reprojected taps may come from another strip's rows: no halo covers them)
+        return strip_fail(ctx, NEB_ERR_STATE, "neb_strip_frame_begin: not with option svgf_reproject");
     StripRows R;
     std::string why;
     if (int rc = strip_rows(ctx, plan, R, why))
@@ -436,6 +440,8 @@ int neb_strip_frame_finish(neb_ctx* ctx, void* comm, const neb_strip_plan* plan,
 {
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
+    if (ctx->reproject) // (reprojected taps may come from another strip's rows: no halo covers them)
+        return strip_fail(ctx, NEB_ERR_STATE, "neb_strip_frame_finish: not with option svgf_reproject");
     StripRows R;
     std::string why;
     if (int rc = strip_rows(ctx, plan, R, why))

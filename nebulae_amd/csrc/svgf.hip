@@ -17,6 +17,7 @@
 
 #include "neb_device.h"
 #include "neb_internal.h"
+#include "svgf_reproject.h"
 
 // Tuning / diagnostic switches (tools/build_variant.sh): the product is built with none of them set.
 #ifndef NEB_ATROUS_PER_CU_R2 // most workgroups per CU of the R = 2 tiles (= waves per SIMD = the register budget: 4 -> 128 registers)
@@ -133,15 +134,20 @@ __device__ __forceinline__ float4 temporal_accumulate(float4 Cc, float4 Ch, floa
 }
 
 // moments and variance (:57-67), as the typed R16G16_FLOAT / R16_FLOAT stores leave them: {moments bits, variance bits}
-__device__ __forceinline__ uint2 temporal_moments(float4 Cc, uint32_t mh, float alpha, float varianceEps)
+// (history moments as floats: the reprojecting pass resamples them)
+__device__ __forceinline__ uint2 temporal_moments_f(float4 Cc, float Mh0, float Mh1, float alpha, float varianceEps)
 {
     const float Y = luminance(Cc.x, Cc.y, Cc.z);
-    const float Mh0 = half_bits_to_float(mh & 0xffffu), Mh1 = half_bits_to_float(mh >> 16);
     const float M1 = fmaf(alpha, Mh0 - Y, Y);
     const float Y2 = Y * Y;
     const float M2 = fmaf(alpha, Mh1 - Y2, Y2);
     const float var = fmaxf(fmaf(-M1, M1, M2), varianceEps);
     return make_uint2(float_to_half_bits(M1) | (float_to_half_bits(M2) << 16), float_to_half_bits(var));
+}
+
+__device__ __forceinline__ uint2 temporal_moments(float4 Cc, uint32_t mh, float alpha, float varianceEps)
+{
+    return temporal_moments_f(Cc, half_bits_to_float(mh & 0xffffu), half_bits_to_float(mh >> 16), alpha, varianceEps);
 }
 
 __global__ __launch_bounds__(256) void svgf_temporal_kernel(TemporalArgs a)
@@ -199,6 +205,210 @@ hipError_t launch_temporal(const SvgfLaunch& L, float4* rad_cur, const float4* r
     const uint64_t n = (uint64_t)Wd * a.nrows;
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
     hipLaunchKernelGGL(svgf_temporal_kernel, dim3(blocks), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------
+// Reprojecting temporal accumulation (option svgf_reproject; the mode is documented at neb_svgf_set_camera in nebulae_hip.h).
+// One pixel per lane, an 8x8 tile per wave (the 2x2 history gathers of neighbouring lanes then fall on the same lines), four
+// tiles side by side per 256-lane workgroup; cameras are kernel arguments (SGPRs); every operation is an IEEE fp32 one in the
+// order tests/reproject_ref.py repeats (explicit fmaf, correctly rounded divisions), so the CPU reference reaches the same
+// tap positions bit for bit.  No LDS.
+// ------------------------------------------------------------------------------------------
+struct ReprojCam {
+    float ex, ey, ez;             // eye
+    float xx, xy, xz;             // x axis
+    float yx, yy, yz;             // y axis
+    float zx, zy, zz;             // z axis (points from the target to the eye)
+    float sx, sy;                 // aspect * tan(vfov / 2), tan(vfov / 2): NDC -> view plane
+    float m22, m32;               // depth mapping of XMMatrixPerspectiveFovRH
+};
+
+struct ReprojArgs {
+    float4* rad_cur;
+    const float4* rad_hist;
+    const uint32_t* depth_cur;
+    const uint32_t* depth_hist;
+    const uint2* normal_cur;
+    const uint2* normal_hist;
+    const uint32_t* mom_hist;
+    uint32_t* mom_cur;
+    uint16_t* variance;
+    const uint8_t* hlen_hist;
+    uint8_t* hlen_cur;
+    float4* geometry;             // as TemporalArgs::geometry (null: not written)
+    uint32_t W, tiles_x, n_tiles;
+    int Wd, Hd;
+    float inv_W, inv_H, half_W, half_H;
+    float alpha, varianceEps;
+    int hist_ok;                  // 0: no camera for the history slot -- no history anywhere
+    ReprojCam cc, ch;             // cameras of cur and hist
+};
+
+// world point of pixel (x, y) at stored depth d (D24 unorm) seen by camera c: gbuffer_kernel's mapping inverted
+__device__ __forceinline__ float3 reproj_world_point(const ReprojCam& c, float inv_W, float inv_H, int x, int y, float d)
+{
+    const float ndc_x = fmaf(((float)x + 0.5f) * inv_W, 2.0f, -1.0f);
+    const float ndc_y = fmaf(((float)y + 0.5f) * inv_H, -2.0f, 1.0f);
+    const float a = ndc_x * c.sx, b = ndc_y * c.sy;
+    const float z = c.m32 / (d + c.m22); // linear depth -z_view
+    const float vx = fmaf(c.xx, a, fmaf(c.yx, b, -c.zx));
+    const float vy = fmaf(c.xy, a, fmaf(c.yy, b, -c.zy));
+    const float vz = fmaf(c.xz, a, fmaf(c.yz, b, -c.zz));
+    return make_float3(fmaf(vx, z, c.ex), fmaf(vy, z, c.ey), fmaf(vz, z, c.ez));
+}
+
+__device__ __forceinline__ bool d24_surface(uint32_t d) { return (d & 0xffffffu) != 0xffffffu; }
+
+__global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs a)
+{
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (tile >= a.n_tiles)
+        return;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t ty = tile / a.tiles_x, tx = tile - ty * a.tiles_x;
+    const int x = (int)(tx * 8u + (lane & 7u)), y = (int)(ty * 8u + (lane >> 3));
+    const size_t i = (size_t)y * a.W + (uint32_t)x;
+
+    const float4 Cc = a.rad_cur[i];
+    const uint32_t dc = a.depth_cur[i];
+    const uint2 nc = a.normal_cur[i];
+    const float zc = depth_unorm24(dc);
+
+    float4 Ch = Cc; // (with no history: a = 0 and lerp(Cc, Cc, 0) = Cc exactly)
+    float Mh0 = 0.0f, Mh1 = 0.0f;
+    uint32_t n = 0;
+    if (a.hist_ok && d24_surface(dc)) {
+        const float3 P = reproj_world_point(a.cc, a.inv_W, a.inv_H, x, y, zc);
+        const float3 Ng = oct16_unpack_zw(nc.x); // geometric normal (.xy)
+        // project P with the history camera
+        const float rx = P.x - a.ch.ex, ry = P.y - a.ch.ey, rz = P.z - a.ch.ez;
+        const float zl = -fmaf(rz, a.ch.zz, fmaf(ry, a.ch.zy, rx * a.ch.zx)); // linear depth of P in the history camera
+        const float cx = fmaf(rz, a.ch.xz, fmaf(ry, a.ch.xy, rx * a.ch.xx));
+        const float cy = fmaf(rz, a.ch.yz, fmaf(ry, a.ch.yy, rx * a.ch.yx));
+        const float ndc_x = cx / (zl * a.ch.sx), ndc_y = cy / (zl * a.ch.sy);
+        const float fx = fmaf(ndc_x, a.half_W, a.half_W) - 0.5f; // continuous pixel position - 0.5: the taps are floor + {0, 1}
+        const float fy = fmaf(-ndc_y, a.half_H, a.half_H) - 0.5f;
+        if (zl > 0.0f && fx > -1.0f && fx < (float)a.Wd && fy > -1.0f && fy < (float)a.Hd) { // (false for NaN too)
+            const float x0f = floorf(fx), y0f = floorf(fy);
+            const float wx = fx - x0f, wy = fy - y0f;
+            const int x0 = (int)x0f, y0 = (int)y0f;
+            const float tol = kReprojPlaneTol * zl;
+            // every tap's planes are loaded up front, at a clamped address (in bounds whatever the position), so that the wave has ONE
+            // round trip to memory for the history instead of three dependent ones (tap depth -> tap normal -> tap radiance);
+            // out-of-region taps are then simply not counted
+            const int cx0 = min(max(x0, 0), a.Wd - 1), cx1 = min(max(x0 + 1, 0), a.Wd - 1);
+            const int cy0 = min(max(y0, 0), a.Hd - 1), cy1 = min(max(y0 + 1, 0), a.Hd - 1);
+            size_t j[4];
+            j[0] = (size_t)cy0 * a.W + (uint32_t)cx0;
+            j[1] = (size_t)cy0 * a.W + (uint32_t)cx1;
+            j[2] = (size_t)cy1 * a.W + (uint32_t)cx0;
+            j[3] = (size_t)cy1 * a.W + (uint32_t)cx1;
+            const uint32_t* normal32 = reinterpret_cast<const uint32_t*>(a.normal_hist);
+            uint32_t dt[4], nt[4], mh[4], hl[4];
+            float4 rt[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                dt[t] = a.depth_hist[j[t]];
+                nt[t] = normal32[2 * j[t]]; // .xy: geometric normal
+                rt[t] = a.rad_hist[j[t]];
+                mh[t] = a.mom_hist[j[t]];
+                hl[t] = a.hlen_hist[j[t]];
+            }
+            float sw = 0.0f, ax = 0.0f, ay = 0.0f, az = 0.0f, m0 = 0.0f, m1 = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                const int px = x0 + (t & 1), py = y0 + (t >> 1);
+                if (px < 0 || px >= a.Wd || py < 0 || py >= a.Hd || !d24_surface(dt[t]))
+                    continue;
+                const float3 Nt = oct16_unpack_zw(nt[t]);
+                if (!(fmaf(Ng.z, Nt.z, fmaf(Ng.y, Nt.y, Ng.x * Nt.x)) >= kReprojNormalCos))
+                    continue;
+                const float3 Pt = reproj_world_point(a.ch, a.inv_W, a.inv_H, px, py, depth_unorm24(dt[t]));
+                const float dist = fmaf(Pt.z - P.z, Ng.z, fmaf(Pt.y - P.y, Ng.y, (Pt.x - P.x) * Ng.x));
+                if (!(fabsf(dist) <= tol))
+                    continue;
+                const float w = ((t & 1) ? wx : 1.0f - wx) * ((t >> 1) ? wy : 1.0f - wy);
+                sw += w;
+                ax = fmaf(w, rt[t].x, ax);
+                ay = fmaf(w, rt[t].y, ay);
+                az = fmaf(w, rt[t].z, az);
+                m0 = fmaf(w, half_bits_to_float(mh[t] & 0xffffu), m0);
+                m1 = fmaf(w, half_bits_to_float(mh[t] >> 16), m1);
+                n = hl[t] > n ? hl[t] : n;
+            }
+            if (sw > 1e-4f) {
+                const float inv = 1.0f / sw;
+                Ch = make_float4(ax * inv, ay * inv, az * inv, Cc.w);
+                Mh0 = m0 * inv;
+                Mh1 = m1 * inv;
+            } else {
+                n = 0;
+            }
+        }
+    }
+    const float alpha = n == 0 ? 0.0f : fminf(a.alpha, 1.0f - 1.0f / (float)(n + 1u));
+    if (a.geometry) {
+        const float3 Ns = oct16_unpack_zw(nc.y);
+        a.geometry[i] = make_float4(Ns.x, Ns.y, Ns.z, zc);
+    }
+    const uint2 mv = temporal_moments_f(Cc, Mh0, Mh1, alpha, a.varianceEps);
+    a.rad_cur[i] = temporal_accumulate(Cc, Ch, alpha);
+    a.mom_cur[i] = mv.x;
+    a.variance[i] = (uint16_t)mv.y;
+    a.hlen_cur[i] = (uint8_t)(n < 255u ? n + 1u : 255u);
+}
+
+static ReprojCam reproj_cam(const CameraBasis& b)
+{
+    ReprojCam c;
+    c.ex = b.eye[0], c.ey = b.eye[1], c.ez = b.eye[2];
+    c.xx = b.xaxis[0], c.xy = b.xaxis[1], c.xz = b.xaxis[2];
+    c.yx = b.yaxis[0], c.yy = b.yaxis[1], c.yz = b.yaxis[2];
+    c.zx = b.zaxis[0], c.zy = b.zaxis[1], c.zz = b.zaxis[2];
+    c.sx = b.aspect * b.tan_half; // (gbuffer_kernel: ndc_x * aspect * tan_half, evaluated left to right)
+    c.sy = b.tan_half;
+    c.m22 = b.m22;
+    c.m32 = b.m32;
+    return c;
+}
+
+hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
+                                     const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
+                                     const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
+                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s)
+{
+    const uint32_t Wd = (L.W / 8u) * 8u, Hd = (L.H / 8u) * 8u; // the same-pixel pass's Dispatch(W/8, H/8) region
+    if (Wd == 0 || Hd == 0)
+        return hipSuccess;
+    ReprojArgs a;
+    a.rad_cur = rad_cur;
+    a.rad_hist = rad_hist;
+    a.depth_cur = depth_cur;
+    a.depth_hist = depth_hist;
+    a.normal_cur = normal_cur;
+    a.normal_hist = normal_hist;
+    a.mom_hist = mom_hist;
+    a.mom_cur = mom_cur;
+    a.variance = variance;
+    a.hlen_hist = hlen_hist;
+    a.hlen_cur = hlen_cur;
+    a.geometry = geometry;
+    a.W = L.W;
+    a.tiles_x = Wd / 8u;
+    a.n_tiles = a.tiles_x * (Hd / 8u);
+    a.Wd = (int)Wd;
+    a.Hd = (int)Hd;
+    a.inv_W = 1.0f / (float)L.W;
+    a.inv_H = 1.0f / (float)L.H;
+    a.half_W = 0.5f * (float)L.W;
+    a.half_H = 0.5f * (float)L.H;
+    a.alpha = L.p.alpha;
+    a.varianceEps = L.p.varianceEps;
+    a.hist_ok = cam_hist != nullptr;
+    a.cc = reproj_cam(cam_cur);
+    a.ch = reproj_cam(cam_hist ? *cam_hist : cam_cur);
+    hipLaunchKernelGGL(svgf_temporal_reproject_kernel, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -57,11 +57,16 @@ class DeferredRenderer:
         # reference skips SVGF on those frames (DeferredRenderer.cpp:595) and resets the history when the camera stops;
         # with this flag the temporal pass runs every frame (no reprojection: it then exercises quirk 2).
         self.denoise_while_moving = False
+        # Beyond the reference: reproject the history through the two frames' cameras (option svgf_reproject, set at init):
+        # SVGF runs every frame, moving or not, and the history is never reset when the camera stops.
+        self.temporal_reprojection = False
         self.info = None
 
     # ---- DeferredRenderer::Init (src/DeferredRenderer.cpp:26-57) ----
     def init(self, width, height, atrous_levels=None, device=0, row_begin=0, row_end=0):
         self.svgf.init(width, height, atrous_levels=atrous_levels, device=device, row_begin=row_begin, row_end=row_end)
+        if self.temporal_reprojection:
+            self.svgf.set_option("svgf_reproject", 1)
         self.width, self.height = width, height
         return True
 
@@ -117,6 +122,8 @@ class DeferredRenderer:
         if info.scene is not None and info.scene is not self._scene:
             self.init_pathtracer_scene(info.scene, info.stream)
         self.svgf.begin_frame(info.frame_index)
+        if self.temporal_reprojection:  # (for a caller that uploads its own G-buffer; submit_commands_gbuffer records the same camera)
+            self.svgf.set_camera(SLOT_CURRENT, info.camera)
         eye = tuple(info.camera.eye)
         sun_key = (self.sun.rough_diameter, tuple(self.sun.direction), tuple(self.sun.radiance))
         moved = (eye != self._eye) or (self._sun_key is not None and sun_key != self._sun_key)  # :133-146,169-171
@@ -126,7 +133,7 @@ class DeferredRenderer:
             self.dynamic_scene_this_frame = True
         elif self.dynamic_scene_this_frame:
             self.dynamic_scene_this_frame = False  # camera stopped: reset history and start denoising
-            self.reset_history = not self.denoise_while_moving
+            self.reset_history = not (self.denoise_while_moving or self.temporal_reprojection)
 
     def end_frame(self):
         self.svgf.end_frame()
@@ -192,7 +199,7 @@ class DeferredRenderer:
         self._check(self._lib.neb_gi_resolve(self._ctx, C.c_void_p(self.info.stream if stream is None else stream)), "neb_gi_resolve")
 
     def submit_commands_svgf_denoising(self):
-        if self.dynamic_scene_this_frame and not self.denoise_while_moving:  # :595
+        if self.dynamic_scene_this_frame and not (self.denoise_while_moving or self.temporal_reprojection):  # :595
             return False
         self._lib.neb_marker_push(b"SVGF Denoising")  # NEB_PIX_SCOPED_EVENT, src/DeferredRenderer.cpp:599
         try:

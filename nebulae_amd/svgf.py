@@ -14,14 +14,15 @@ import numpy as np
 
 from . import _lib
 from ._lib import (PLANE_DEPTH, PLANE_MOMENTS, PLANE_NORMAL, PLANE_RADIANCE, PLANE_SCRATCH, PLANE_VARIANCE,  # noqa: F401
-                   PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY, SLOT_CURRENT, SLOT_HISTORY, NebError)
+                   PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY, PLANE_HISTORY_LENGTH, SLOT_CURRENT,
+                   SLOT_HISTORY, NebError)
 
 # plane -> (numpy dtype, channels)
 PLANE_LAYOUT = {
     PLANE_RADIANCE: (np.float32, 4), PLANE_NORMAL: (np.float16, 4), PLANE_DEPTH: (np.uint32, 1),
     PLANE_MOMENTS: (np.float16, 2), PLANE_VARIANCE: (np.float16, 1), PLANE_SCRATCH: (np.float32, 4),
     PLANE_ALBEDO: (np.uint32, 1), PLANE_ROUGH_METAL: (np.float16, 2), PLANE_WORLDPOS: (np.float16, 4),
-    PLANE_LDR: (np.uint32, 1), PLANE_GEOMETRY: (np.float32, 4),
+    PLANE_LDR: (np.uint32, 1), PLANE_GEOMETRY: (np.float32, 4), PLANE_HISTORY_LENGTH: (np.uint8, 1),
 }
 
 
@@ -145,7 +146,7 @@ class SVGFDenoiser:
         import torch
         ptr, _, rows = self.get_plane(plane, slot)
         dt, ch = PLANE_LAYOUT[plane]
-        typestr = {np.float32: "<f4", np.float16: "<f2", np.uint32: "<i4"}[dt]
+        typestr = {np.float32: "<f4", np.float16: "<f2", np.uint32: "<i4", np.uint8: "|u1"}[dt]
         shape = (rows, self.width, ch) if ch > 1 else (rows, self.width)
 
         class _Holder:
@@ -157,6 +158,11 @@ class SVGFDenoiser:
         t = torch.as_tensor(h, device=f"cuda:{self.device}")  # (the context's own device, whatever torch's current one is)
         t._neb_owner = self  # keep the context alive as long as the view
         return t
+
+    def set_camera(self, slot, cam):
+        """neb_svgf_set_camera: the camera (scene.CameraDesc) slot `slot`'s depth / normal planes were rendered with -- what the
+        reprojecting temporal pass (option svgf_reproject) maps them with.  submit_commands_gbuffer records its own."""
+        self._check(self._lib.neb_svgf_set_camera(self._ctx, int(slot), C.byref(cam)), "neb_svgf_set_camera")
 
     def synchronize(self, stream=0):
         self._check(self._lib.neb_stream_synchronize(self._ctx, C.c_void_p(stream)), "neb_stream_synchronize")
