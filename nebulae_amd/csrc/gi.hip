@@ -111,9 +111,6 @@ __device__ __forceinline__ uint32_t gi_block()
 }
 constexpr uint32_t kShadeRuns = 16u, kRaygenRuns = 16u;
 constexpr uint32_t kListSegments = 128u;
-#ifndef NEB_TAIL_STAMPS
-#define NEB_TAIL_STAMPS 0
-#endif
 #ifndef NEB_LIST_QUAD_BELOW
 #define NEB_LIST_QUAD_BELOW 1500000u // dispatches of fewer pixels walk their ray lists with four lanes per ray (row strips; a 1080p frame does not)
 #endif
@@ -146,11 +143,6 @@ __device__ __forceinline__ void count_rays(uint32_t* block_counts, uint32_t mine
 }
 __device__ __forceinline__ void count_rays(uint32_t* block_counts, uint32_t mine) { count_rays(block_counts, mine, blockIdx.x); }
 
-#ifndef NEB_FAST_RAYGEN
-#define NEB_FAST_RAYGEN 0 // A/B arm: 1 = 1-ulp hardware rcp / rsq / sqrt / x^5 in ray generation, 2 = also v_sin / v_cos.  Measured: the
-                          // kernel takes 380 us either way (377 us exact) although ray generation is ~15 % of its instructions, and
-                          // six parity tests leave their 2e-5 band (a direction that moves by an ulp lands on another texel footprint)
-#endif
 // One wave per 8x8 pixel tile.  LDS per wave: the closest-hit walk's stack (kRgStack entries per lane: no bounce ray of the bench frame ever holds
 // more than 12, tools/gi_wave_stamps.py; deeper entries go to the private array) + the child slots of traverse_core (16 bytes per lane) = 4 KB,
 // eight waves per SIMD.
@@ -159,11 +151,12 @@ __device__ __forceinline__ void count_rays(uint32_t* block_counts, uint32_t mine
 #endif
 constexpr int kRgStack = NEB_RG_STACK;
 static_assert(32 * (kRgStack * 256 + 1024) <= 160 * 1024 || NEB_TRACE_WAVES < 8, "LDS budget of the closest-hit pass: 32 waves per CU of stacks and child slots in 160 KB");
-template <bool FAST, bool FAST_TRIG>
+// Ray generation keeps the exact arithmetic (no 1-ulp hardware forms): an ulp of direction can land a ray on another texel footprint,
+// and ray generation is a small share of this kernel's instructions.
 __global__ __launch_bounds__(64, NEB_TRACE_WAVES) void gi_raygen_trace_kernel(GiArgs a)
 {
     __shared__ int stack_mem[kRgStack * 64];
-    __shared__ int child_slot_mem[256];
+    __shared__ __attribute__((aligned(16))) int child_slot_mem[256]; // (traverse_core stores to it 16 bytes at a time)
     uint32_t x, y;
     size_t i64;
     bool active;
@@ -184,7 +177,7 @@ __global__ __launch_bounds__(64, NEB_TRACE_WAVES) void gi_raygen_trace_kernel(Gi
         const uint2 wp = a.world_pos[i];
         const float3 worldPos = f3(half_bits_to_float(wp.x & 0xffffu), half_bits_to_float(wp.x >> 16), half_bits_to_float(wp.y & 0xffffu));
         const uint32_t nzw = a.normal[i].y;
-        const float3 SN = oct_unpack<FAST>(half_bits_to_float(nzw & 0xffffu), half_bits_to_float(nzw >> 16));
+        const float3 SN = oct_unpack(half_bits_to_float(nzw & 0xffffu), half_bits_to_float(nzw >> 16));
         const float metalness = half_bits_to_float(a.rough_metal[i] >> 16);
         uint32_t rng;
         float3 V;
@@ -199,11 +192,11 @@ __global__ __launch_bounds__(64, NEB_TRACE_WAVES) void gi_raygen_trace_kernel(Gi
         (void)rand01(rng); // consumed by NrcCreatePathState (:438)
         const float3 F0 = specular_f0(albedo, metalness);
         float3 throughput = f3(1, 1, 1) * (albedo * (1.0f - metalness)); // :474
-        const float pd = 1.0f - specular_probability<FAST>(saturate1(dot3(normalize3<FAST>(V), SN)), F0, albedo);
+        const float pd = 1.0f - specular_probability(saturate1(dot3(normalize3(V), SN)), F0, albedo);
         if (rand01(rng) < pd)
-            throughput = f3(fdiv<FAST>(throughput.x, pd), fdiv<FAST>(throughput.y, pd), fdiv<FAST>(throughput.z, pd)); // :476-479
+            throughput = f3(throughput.x / pd, throughput.y / pd, throughput.z / pd); // :476-479
         const float u0 = rand01(rng), u1 = rand01(rng);
-        const float3 dir = cosine_hemisphere_aligned<FAST, FAST_TRIG>(u0, u1, SN);
+        const float3 dir = cosine_hemisphere_aligned(u0, u1, SN);
         const float3 org = worldPos + SN * 1e-2f; // :138
         const bool bounce = a.c.maxPathVertices > 1; // for (bounce = 1; bounce < nrcMaxPathVertices; ...)
         a.R.path[i] = make_float4(throughput.x, throughput.y, throughput.z, __uint_as_float(rng));
@@ -618,9 +611,6 @@ __global__ __launch_bounds__(64, NEB_TRACE_WAVES) void gi_shadow_trace_kernel(Gi
 // leave; with the tree warm in cache 52 instead of 56; two nodes per step 68).  So: a fixed grid, workgroup b takes chunks
 // b / kListSegments, + kListChunks, ... of list b % kListSegments -- one counter read, no scan -- and a ray comes out of its list slot
 // whole (64 bytes, consecutive slots: no gather through a pixel index).
-#if NEB_TAIL_STAMPS // diagnostics build: per wave {start, end (s_memrealtime, 100 MHz), rays, max node visits}
-__device__ unsigned long long g_tail_stamps[8192 * 4];
-#endif
 constexpr uint32_t kListChunks = 64u; // chunks of 64 rays per list taken in parallel: kListSegments x kListChunks = 8192 waves = the chip's wave slots
 // QUAD: four lanes per ray (traverse_any_quad, gi_device.h), 16 rays per wave at a time.  Which one runs is a matter of how many rays there
 // are (measured, profiles/r04_tail_stamps.txt and tools/strip_host_cost.py): the 160 k rays a whole 1080p frame leaves put 2.5 one-lane-per-ray
@@ -633,19 +623,11 @@ __global__ __launch_bounds__(64, NEB_LIST_WAVES) void gi_shadow_list_kernel(GiAr
 {
     __shared__ int stack_mem[kLdsStack * 64];
     const uint32_t lane = threadIdx.x;
-#if NEB_TAIL_STAMPS
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    uint32_t st_rays = 0, st_visits = 0;
-#endif
     const uint32_t seg = blockIdx.x % kListSegments, chunks = gridDim.x / kListSegments;
     const uint32_t count = a.list_counts[a.list_set * kListSegments + seg];
     if (blockIdx.x == 0) // the other set of counters is idle until the next shade launch fills it: clear it for that launch
         for (uint32_t k = lane; k < kListSegments; k += 64u)
             a.list_counts[(a.list_set ^ 1u) * kListSegments + k] = 0u;
-#ifdef NEB_TAIL_SKIP // timing-only build (wrong results): trace every NEB_TAIL_SKIP-th list -- is the tail bound by its rays or by its longest wave?
-    if (seg % NEB_TAIL_SKIP)
-        return;
-#endif
     static_assert(kLdsStack * 64 >= 16 * 64, "a quad's LDS column holds the whole 64-entry stack");
     constexpr uint32_t kRaysPerWave = QUAD ? 16u : 64u;
     const uint32_t slot = QUAD ? lane >> 2 : lane; // the ray of the wave's chunk this lane works on
@@ -664,16 +646,8 @@ __global__ __launch_bounds__(64, NEB_LIST_WAVES) void gi_shadow_list_kernel(GiAr
             if ((lane & 3u) != 0u)
                 continue; // the quad's first lane finishes the pixel
         } else {
-#if NEB_TAIL_STAMPS
-            occluded = traverse(a.S, f3(ro.x, ro.y, ro.z), f3(rd.x, rd.y, rd.z), 0.001f, kTraceMax, true, stack_mem + lane, sh, true);
-#else
             occluded = traverse(a.S, f3(ro.x, ro.y, ro.z), f3(rd.x, rd.y, rd.z), 0.001f, kTraceMax, true, stack_mem + lane, sh, a.stats != 0);
-#endif
         }
-#if NEB_TAIL_STAMPS
-        st_rays += 1;
-        st_visits = max(st_visits, sh.node_visits);
-#endif
         if (a.stats) { // diagnostics only
             if (a.hits && a.bounce == 1)
                 a.hits[i].flags |= min(sh.node_visits, 4095u) << 20;
@@ -701,32 +675,7 @@ __global__ __launch_bounds__(64, NEB_LIST_WAVES) void gi_shadow_list_kernel(GiAr
             a.R.srec[4 * i + kSrSum] = sum;
         }
     }
-#if NEB_TAIL_STAMPS
-    {
-        uint32_t r = st_rays, v = st_visits;
-        for (int off = 32; off > 0; off >>= 1) {
-            r += (uint32_t)__shfl_xor((int)r, off);
-            v = max(v, (uint32_t)__shfl_xor((int)v, off));
-        }
-        if (lane == 0 && blockIdx.x < 8192u) {
-            g_tail_stamps[4 * blockIdx.x + 0] = t_start;
-            g_tail_stamps[4 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
-            g_tail_stamps[4 * blockIdx.x + 2] = r;
-            g_tail_stamps[4 * blockIdx.x + 3] = v;
-        }
-    }
-#endif
 }
-
-#if NEB_TAIL_STAMPS
-} // namespace neb
-extern "C" int neb_debug_tail_stamps(unsigned long long* host)
-{
-    (void)hipDeviceSynchronize();
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(neb::g_tail_stamps), sizeof(neb::g_tail_stamps)) == hipSuccess ? 0 : -1;
-}
-namespace neb {
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // G-buffer producer ("next" row f2): primary visibility through the same BVH
@@ -1133,7 +1082,7 @@ static int gi_dispatch(neb_ctx* ctx, const neb_gi_constants* c, uint32_t row0, u
         for (uint32_t b = 1; b <= n_vertices; ++b) { // for (bounce = 1; bounce < nrcMaxPathVertices; ++bounce), :495
             a.bounce = b;
             if (b == 1 && phase != 2) {
-                hipLaunchKernelGGL((gi_raygen_trace_kernel<(NEB_FAST_RAYGEN >= 1), (NEB_FAST_RAYGEN >= 2)>), grid, block, 0, (hipStream_t)stream, a);
+                hipLaunchKernelGGL(gi_raygen_trace_kernel, grid, block, 0, (hipStream_t)stream, a);
             }
             if (phase == 1)
                 continue;
@@ -1150,7 +1099,7 @@ static int gi_dispatch(neb_ctx* ctx, const neb_gi_constants* c, uint32_t row0, u
             a.list_set = ds.list_epoch & 1u;
             if (tail_slot >= 0 && s == 0 && b == 1)
                 GI_HIP(ctx, hipEventRecord(g->tail_ev[tail_slot], (hipStream_t)stream));
-            if (kFastShade && !g->exact_shade)
+            if (!g->exact_shade)
                 hipLaunchKernelGGL(gi_shade_kernel<true>, grid, block, 0, (hipStream_t)stream, a);
             else
                 hipLaunchKernelGGL(gi_shade_kernel<false>, grid, block, 0, (hipStream_t)stream, a);

@@ -219,9 +219,6 @@ __global__ void lbvh_gather_kernel(const float* __restrict__ tris12, const float
 #ifndef NEB_SAH_BINS
 #define NEB_SAH_BINS 32
 #endif
-#ifndef NEB_SAH_BIG
-#define NEB_SAH_BIG 1 // the first levels' splits spread over the chip (sah_big_* kernels); 0: one workgroup per segment at every level
-#endif
 constexpr int kSahBins = NEB_SAH_BINS;
 
 struct BinaryNodes { // the binary tree under construction
@@ -895,7 +892,7 @@ struct CollapseArgs {
     uint32_t* inner_scan;   // exclusive prefix sum of inner_count over the level
     uint32_t* level_state;  // [0] = entries of the next level
     uint32_t level_start, level_count;
-    const float4* plan;     // per binary node: {C(n,1), C(n,2), C(n,3), decision bits} of collapse_plan_kernel, or null (greedy)
+    const float4* plan;     // per binary node: {C(n,1), C(n,2), C(n,3), decision bits} of collapse_plan_kernel
 };
 
 __device__ __forceinline__ bool collapse_is_leaf(const BinaryNodes& N, int node) { return N.size[node] <= (uint32_t)kMaxLeafTris; }
@@ -993,36 +990,14 @@ __global__ void collapse_open_kernel(CollapseArgs a)
         return;
     const uint32_t e = a.level_start + k;
     const int bn = (int)a.q_node[e];
-    int c[4] = {__float_as_int(a.N.lo[bn].w), __float_as_int(a.N.hi[bn].w), -1, -1};
-    int nc = 2;
-    if (a.plan) { // the cost-optimal choice (collapse_plan_kernel)
-        const int k4 = (int)(__float_as_uint(a.plan[bn].w) & 3u);
-        const int l = c[0], r = c[1];
-        nc = 0;
-        collapse_expand(a, l, k4, c, nc);
-        collapse_expand(a, r, 4 - k4, c, nc);
-        for (int q = nc; q < 4; ++q)
-            c[q] = -1;
-    }
-    while (!a.plan && nc < 4) { // (A/B arm, NEB_COLLAPSE_DP = 0) open the inner child with the largest surface area
-        int best = -1;
-        float best_area = -1.0f;
-        for (int q = 0; q < nc; ++q) {
-            if (collapse_is_leaf(a.N, c[q]))
-                continue;
-            const float4 lo = a.N.lo[c[q]], hi = a.N.hi[c[q]];
-            const float ar = box_half_area(f3(lo.x, lo.y, lo.z), f3(hi.x, hi.y, hi.z));
-            if (ar > best_area) {
-                best_area = ar;
-                best = q;
-            }
-        }
-        if (best < 0)
-            break;
-        const int o = c[best];
-        c[best] = __float_as_int(a.N.lo[o].w);
-        c[nc++] = __float_as_int(a.N.hi[o].w);
-    }
+    // the cost-optimal choice (collapse_plan_kernel): k4 of the four slots to the left child, the rest to the right one
+    const int k4 = (int)(__float_as_uint(a.plan[bn].w) & 3u);
+    const int l = __float_as_int(a.N.lo[bn].w), r = __float_as_int(a.N.hi[bn].w);
+    int c[4], nc = 0;
+    collapse_expand(a, l, k4, c, nc);
+    collapse_expand(a, r, 4 - k4, c, nc);
+    for (int q = nc; q < 4; ++q)
+        c[q] = -1;
     uint32_t inner = 0;
     for (int q = 0; q < nc; ++q)
         inner += collapse_is_leaf(a.N, c[q]) ? 0u : 1u;
@@ -1683,10 +1658,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     uint32_t* d_icount = (uint32_t*)dalloc((size_t)n * 4, false);
     uint32_t* d_iscan = (uint32_t*)dalloc((size_t)n * 4, false);
     float4* d_shade = (float4*)dalloc((size_t)n * 128, true);
-#ifndef NEB_COLLAPSE_DP
-#define NEB_COLLAPSE_DP 1 // 1: cost-optimal BVH4 collapse (collapse_plan_kernel); 0: the greedy largest-box rule (A/B arm)
-#endif
-    float4* d_plan = NEB_COLLAPSE_DP ? (float4*)dalloc(n2 * 16, false) : nullptr;
+    float4* d_plan = (float4*)dalloc(n2 * 16, false);
     size_t cub_bytes = 0, cub_b2 = 0, cub_b3 = 0;
     (void)rocprim::radix_sort_keys(nullptr, cub_bytes, d_keys, d_keys2, (size_t)n, 0u, 64u, stream);
     (void)rocprim::exclusive_scan(nullptr, cub_b2, d_flags, d_scan, 0ull, (size_t)n, rocprim::plus<unsigned long long>(), stream);
@@ -1722,11 +1694,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     uint32_t index_bits = 1;
     while (index_bits < 32 && (1ull << index_bits) < (unsigned long long)n)
         ++index_bits;
-#ifdef NEB_MORTON_AXIS_BITS
-    const uint32_t axis_bits = NEB_MORTON_AXIS_BITS;
-#else
     const uint32_t axis_bits = (64 - index_bits) / 3 < 21 ? (64 - index_bits) / 3 : 21;
-#endif
     hipLaunchKernelGGL(lbvh_morton_kernel, dim3(nb), dim3(256), 0, stream, d_tris12, (const float4*)d_boxes, n, smin, sinv, axis_bits, index_bits, d_keys);
     BUILD_HIP(hipGetLastError());
     BUILD_HIP(rocprim::radix_sort_keys(d_cub, cub_bytes, d_keys, d_keys2, (size_t)n, 0u, 64u, stream));
@@ -1762,7 +1730,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
             const SahSegment* segs = d_segs[passes & 1u];
             const uint32_t* idx_in = d_idx[passes & 1u];
             uint32_t* idx_out = d_idx[(passes + 1u) & 1u];
-            if (NEB_SAH_BIG && (size_t)n_segs * 2048 <= (size_t)n && n_segs <= kSahBigMaxSegs) {
+            if ((size_t)n_segs * 2048 <= (size_t)n && n_segs <= kSahBigMaxSegs) {
                 // runs of 2048 primitives and more on average: slices of kSahSlice primitives, one workgroup each (a run shorter than a
                 // slice is one slice); at most n / kSahSlice + n_segs slices exist, blocks beyond the real count leave at once
                 const dim3 sg_grid(n / kSahSlice + n_segs);
@@ -1773,7 +1741,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
                 hipLaunchKernelGGL(sah_big_count_kernel, sg_grid, dim3(256), 0, stream, N, segs, n_segs, idx_in, big, (const SahBigPick*)d_picks);
                 hipLaunchKernelGGL(sah_big_scan_kernel, dim3((n_segs + 63) / 64), dim3(64), 0, stream, n_segs, big);
                 hipLaunchKernelGGL(sah_big_scatter_kernel, sg_grid, dim3(256), 0, stream, N, segs, n_segs, idx_in, idx_out, big, (const SahBigPick*)d_picks);
-            } else if ((size_t)n_segs * 2048 <= (size_t)n) // (A/B arm NEB_SAH_BIG=0, or more long runs than the slice index holds)
+            } else if ((size_t)n_segs * 2048 <= (size_t)n) // (more long runs than the slice index holds: one workgroup each)
                 hipLaunchKernelGGL(sah_split_kernel<1024>, dim3(n_segs), dim3(1024), 0, stream, N, segs, idx_in, idx_out, d_splits);
             else
                 hipLaunchKernelGGL(sah_split_kernel<256>, dim3(n_segs), dim3(256), 0, stream, N, segs, idx_in, idx_out, d_splits);
@@ -1816,15 +1784,14 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
         a.inner_scan = d_iscan;
         a.level_state = d_state + 4;
         a.plan = d_plan;
-        if (d_plan) { // cost of every subtree as 1, 2 or 3 entries of a wide node: triangles first, then bottom-up, one SAH pass at a time
-            hipLaunchKernelGGL(collapse_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, N, 0u, n, d_plan);
-            for (size_t lv = pass_first.size() - 1; lv-- > 0;) {
-                const uint32_t first = pass_first[lv], count = pass_first[lv + 1] - first;
-                if (count)
-                    hipLaunchKernelGGL(collapse_plan_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, N, first, count, d_plan);
-            }
-            BUILD_HIP(hipGetLastError());
+        // cost of every subtree as 1, 2 or 3 entries of a wide node: triangles first, then bottom-up, one SAH pass at a time
+        hipLaunchKernelGGL(collapse_plan_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, N, 0u, n, d_plan);
+        for (size_t lv = pass_first.size() - 1; lv-- > 0;) {
+            const uint32_t first = pass_first[lv], count = pass_first[lv + 1] - first;
+            if (count)
+                hipLaunchKernelGGL(collapse_plan_kernel, dim3((count + 255) / 256), dim3(256), 0, stream, N, first, count, d_plan);
         }
+        BUILD_HIP(hipGetLastError());
         BUILD_HIP(hipMemcpyAsync(d_qnode, &root_node, 4, hipMemcpyHostToDevice, stream));
         BUILD_HIP(hipMemsetAsync(d_qoff, 0, 4, stream));
         BUILD_HIP(hipStreamSynchronize(stream));

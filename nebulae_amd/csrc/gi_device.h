@@ -170,15 +170,11 @@ template <bool FAST = false> __device__ __forceinline__ float specular_probabili
     const float p = fdiv<FAST>(diff, fmaxf(0.0001f, fres + diff));
     return fminf(fmaxf(p, 0.1f), 0.9f);
 }
-template <bool FAST = false, bool FAST_TRIG = false> __device__ __forceinline__ float3 cosine_hemisphere_aligned(float u0, float u1, float3 sn) // brdf.hlsli:166-185
+template <bool FAST = false> __device__ __forceinline__ float3 cosine_hemisphere_aligned(float u0, float u1, float3 sn) // brdf.hlsli:166-185
 {
     const float a = fsqrt<FAST>(u0), b = kPiTwo * u1;
     float sb, cb;
-    if (FAST_TRIG) {
-        sb = __sinf(b), cb = __cosf(b);
-    } else {
-        det_sincosf(b, sb, cb);
-    }
+    det_sincosf(b, sb, cb);
     const float3 z = f3(a * cb, a * sb, fsqrt<FAST>(1.0f - u0));
     const float3 up = fabsf(sn.z) < 0.999f ? f3(0, 0, 1) : f3(1, 0, 0);
     const float3 tx = normalize3<FAST>(cross3(up, sn));

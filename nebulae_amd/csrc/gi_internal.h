@@ -88,10 +88,6 @@ static_assert(sizeof(Bvh4NodeQ) == 64, "quantised node layout");
 #define NEB_LEAF_BATCH 12
 #endif
 constexpr int kLeafBatch = NEB_LEAF_BATCH;
-#ifndef NEB_FAST_SHADE
-#define NEB_FAST_SHADE 1 // gi_shade_kernel uses the 1-ulp hardware rcp / rsq / sqrt (see fdiv)
-#endif
-constexpr bool kFastShade = NEB_FAST_SHADE != 0;
 #ifndef NEB_MAX_LEAF_TRIS
 #define NEB_MAX_LEAF_TRIS 2 // 1..4 (the leaf code keeps count - 1 in two bits); measured 1/2/3/4: 1407 / 1390 / 1403 / 1500 us of GI per 1080p frame
 #endif

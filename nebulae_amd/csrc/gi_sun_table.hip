@@ -58,9 +58,6 @@ __device__ inline void node_child_box(const Bvh4Node& nd, int q, double lo[3], d
 // PASS 2, the hints, for those only, in dense waves, over the primary side's column, ending once the four best candidates cover all 28 sample origins.
 // One Receiver is live at a time and nothing a lane keeps is indexed at run time except the node stack and may_occlude's clip buffers (round 5: the one-walk
 // kernel held both sides' receivers and the candidate table in scratch, 1.5-1.8 KB per lane at 255 registers; the build's time was its candidate tests).
-#ifndef NEB_SUN_EDGE_CULL
-#define NEB_SUN_EDGE_CULL 1
-#endif
 #ifndef NEB_SUN_WAVES
 #define NEB_SUN_WAVES 1 // waves per SIMD the register allocation of the lit pass aims for (measured: 1 = 256 registers 1.91 ms, 2 = 176 registers + spills 2.14 ms)
 #endif
@@ -301,19 +298,17 @@ __device__ bool sun_walk_column(const SunTableArgs& a, const lit::Receiver& R, b
                 // offset box and by the drift a ray can have when it has climbed to the node's top, exactly the half-planes lit::may_occlude clips every
                 // triangle with -- holds nothing that can matter (may_occlude would clip each of its triangles to nothing; cover_mask finds no sample under
                 // them).  For a large receiver the box is twice the triangle.
-                if constexpr (NEB_SUN_EDGE_CULL) {
-                    const double rho = ((chh + eh) - R.h_min + a.F.margin) * a.F.tau + a.F.margin;
-                    bool outside = false;
+                const double rho = ((chh + eh) - R.h_min + a.F.margin) * a.F.tau + a.F.margin;
+                bool outside = false;
 #pragma unroll
-                    for (int ed = 0; ed < 3; ++ed) {
-                        const double na = R.en_a[ed], nb = R.en_b[ed];
-                        const double lim = R.en_c[ed] + R.en_off[ed] + rho * (fabs(na) + fabs(nb));
-                        // least value of na * a + nb * b over the node's box (the box's sun-space extents ea, eb bound every corner)
-                        outside = outside || (na * ca + nb * cb - (fabs(na) * ea + fabs(nb) * eb) > lim);
-                    }
-                    if (outside)
-                        continue;
+                for (int ed = 0; ed < 3; ++ed) {
+                    const double na = R.en_a[ed], nb = R.en_b[ed];
+                    const double lim = R.en_c[ed] + R.en_off[ed] + rho * (fabs(na) + fabs(nb));
+                    // least value of na * a + nb * b over the node's box (the box's sun-space extents ea, eb bound every corner)
+                    outside = outside || (na * ca + nb * cb - (fabs(na) * ea + fabs(nb) * eb) > lim);
                 }
+                if (outside)
+                    continue;
                 if (ch[q] < 0) {
                     queue_leaf(ch[q]);
                 } else if (node == kTravDone) {

@@ -19,69 +19,12 @@
 #include "neb_internal.h"
 #include "svgf_reproject.h"
 
-// Tuning / diagnostic switches (tools/build_variant.sh): the product is built with none of them set.
+// Tuning knobs (tools/build_variant.sh): the product is built with none of them set.
 #ifndef NEB_ATROUS_PER_CU_R2 // most workgroups per CU of the R = 2 tiles (= waves per SIMD = the register budget: 4 -> 128 registers)
 #define NEB_ATROUS_PER_CU_R2 4
 #endif
 #ifndef NEB_ATROUS_XGROUP // pixels per column group of the x lattice (see AtrousTile); >= 64 = consecutive columns at every step
 #define NEB_ATROUS_XGROUP 8
-#endif
-#ifndef NEB_ATROUS_NOTRANS // timing only (wrong results): v_log / v_exp replaced by full-rate instructions
-#define NEB_ATROUS_NOTRANS 0
-#endif
-#ifndef NEB_ATROUS_PRIO // 0: no s_setprio; 1: a workgroup's priority = the tiles it still has to do (default)
-#define NEB_ATROUS_PRIO 1
-#endif
-#ifndef NEB_ATROUS_R_NARROW // rows per lane of the LDS kernel at steps <= 4.  2 (8-row tiles, 28 KB, four workgroups per CU at 128 registers): S = 2 / 4
-#define NEB_ATROUS_R_NARROW 2 // of the fused chain 29.4 / 29.0 us against 30.9 / 30.2 with 4, 30.5 / 30.3 with 3; the separate kernels 30.5 against 33.0; a
-#endif                        // 136-row strip 9.4 against 12.8.  (With five workgroups per CU and 96 registers -- the round-2 setting -- 2 lost: 34.3 against 32.4.)
-#ifndef NEB_ATROUS_R_FUSED // rows per lane of the fused temporal + level-0 kernel: 2 (its staging then holds four texels per lane instead of
-#define NEB_ATROUS_R_FUSED 2 // six and the kernel fits 128 registers: four workgroups per CU, 47.6 us against 50.7 with 4)
-#endif
-#ifndef NEB_ATROUS_STORE // how the LDS kernel stores its output: 1 write-through (sc1, default), 0 plain, 2 non-temporal (A/B arms)
-#define NEB_ATROUS_STORE 1
-#endif
-#ifndef NEB_ATROUS_WX8 // 64-column blocks per tile at step 8 / at steps 16 and 32: 1; 2 = A/B arm (128-column tiles, eight waves)
-#define NEB_ATROUS_WX8 1
-#endif
-#ifndef NEB_ATROUS_WX16
-#define NEB_ATROUS_WX16 1
-#endif
-#ifndef NEB_ATROUS_PK // 1: the levels of the fused chain evaluate a texel's taps for the lane's two output rows as packed fp32 pairs (`tap2_geometry` / `tap2_weight`); 0: A/B arm
-#define NEB_ATROUS_PK 1
-#endif
-#ifndef NEB_ATROUS_PK_FUSED // the same in the fused temporal + level-0 kernel (tap constants as scalar operands of two plain fmas, one texel at a time:
-#define NEB_ATROUS_PK_FUSED 1 // it has no registers to spare; 47.9 -> 46.2 us); 0: A/B arm
-#endif
-#ifndef NEB_ATROUS_PK_CLASSIC // and in the separate levels (row strips, svgf_fuse = 0), which prefetch the next tile's radiance into registers
-#define NEB_ATROUS_PK_CLASSIC 1
-#endif
-#ifndef NEB_ATROUS_FEWER_LDS_READS // timing only (wrong results), see load_group
-#define NEB_ATROUS_FEWER_LDS_READS 0
-#endif
-#ifndef NEB_ATROUS_STAMPS // diagnostic builds only (tools/atrous_stamps.py): per-wave phase times from s_memtime
-#define NEB_ATROUS_STAMPS 0
-#endif
-#if NEB_ATROUS_NOTRANS
-#define NEB_TAP_LOG2(x) ((x) - 1.0f)
-#define NEB_TAP_EXP2(x) fmaf((x), 0.001f, 1.0f)
-#else
-#define NEB_TAP_LOG2(x) fast_log2(x)
-#define NEB_TAP_EXP2(x) fast_exp2(x)
-#endif
-#if NEB_ATROUS_STAMPS
-#define NEB_STAMP(i)                                        \
-    do {                                                    \
-        __builtin_amdgcn_sched_barrier(0);                  \
-        const uint64_t tn_ = __builtin_amdgcn_s_memtime();  \
-        st[i] += tn_ - tprev;                               \
-        tprev = tn_;                                        \
-        __builtin_amdgcn_sched_barrier(0);                  \
-    } while (0)
-#else
-#define NEB_STAMP(i) \
-    do {             \
-    } while (0)
 #endif
 
 namespace neb {
@@ -487,9 +430,6 @@ struct AtrousArgs {
     uint16_t* variance_out;
     float4* geometry_out;
     float t_neg_inv_two_sigma2_log2e, t_alpha, t_varianceEps;
-#if NEB_ATROUS_STAMPS
-    unsigned long long* stamps;
-#endif
 };
 
 // log2(K[abs(dx)] * K[abs(dy)]) with K = {1/16, 1/4, 3/8, 1/4, 1/16} indexed by abs(d): centre 1/16, +-1 -> 1/4, +-2 -> 3/8
@@ -524,10 +464,10 @@ __device__ __forceinline__ float tap_weight(float h0x, float h0y, float h0z, flo
                                             float lkp)
 {
     const float dh = half_dot_max0(fmaf(h0z, tB.z, fmaf(h0y, tB.y, h0x * tB.x)));
-    float e = fmaf(phiN, NEB_TAP_LOG2(dh), lkp);
+    float e = fmaf(phiN, fast_log2(dh), lkp);
     e = fmaf(-fabsf(z0 - tB.w), cz, e);
     e = fmaf(-fabsf(lum0 - tA.w), cl, e);
-    return NEB_TAP_EXP2(e);
+    return fast_exp2(e);
 }
 
 // the same with MINUS the centre depth and luminance (what the packed form keeps in its register pairs): |t + (-z0)| = |z0 - t| exactly
@@ -535,10 +475,10 @@ __device__ __forceinline__ float tap_weight_neg(float h0x, float h0y, float h0z,
                                                 float lkp)
 {
     const float dh = half_dot_max0(fmaf(h0z, tB.z, fmaf(h0y, tB.y, h0x * tB.x)));
-    float e = fmaf(phiN, NEB_TAP_LOG2(dh), lkp);
+    float e = fmaf(phiN, fast_log2(dh), lkp);
     e = fmaf(-fabsf(tB.w + nz0), cz, e);
     e = fmaf(-fabsf(tA.w + nl0), cl, e);
-    return NEB_TAP_EXP2(e);
+    return fast_exp2(e);
 }
 
 // ---- two output rows per instruction (round 4) ----
@@ -546,7 +486,7 @@ __device__ __forceinline__ float tap_weight_neg(float h0x, float h0y, float h0z,
 // texel and differ in the centre pixel only.  gfx950's packed fp32 forms do two IEEE operations per instruction at 2.09 ns per
 // wave-instruction where a plain v_fma_f32 takes 1.24 and v_mul / v_add / v_sub 1.35-1.38 (tools/ubench_bank.hip): 16-25 % less issue
 // time per operation, and every lane of a pair rounds exactly as the scalar instruction does -- `tap2_geometry` + `tap2_weight` are `tap_weight` twice,
-// bit for bit (the separate kernels, the direct kernel and the strip path keep the scalar form and still agree with the chain).
+// bit for bit (the direct kernel keeps the scalar form and agrees with the LDS kernel).
 // The texel's component is broadcast to both halves by op_sel; what the compiler does not match by itself (a high-half broadcast
 // in v_pk_add_f32, the free [0, 1] clamp on the packed fma) is written out.
 typedef float neb_f2 __attribute__((ext_vector_type(2)));
@@ -574,16 +514,12 @@ __device__ __forceinline__ neb_f2 pk_fma_lo_clamp(neb_f2 x, neb_f2 p, neb_f2 z)
 template <bool SWAP>
 __device__ __forceinline__ neb_f2 pk_fma_const(neb_f2 c, neb_f2 l, neb_f2 k)
 {
-#if NEB_ATROUS_PK == 2 // A/B arm: left to the compiler
-    return pk_fma(__builtin_shufflevector(c, c, 0, 0), l, SWAP ? __builtin_shufflevector(k, k, 1, 0) : k);
-#else
     neb_f2 r;
     if constexpr (SWAP)
         asm("s_nop 0\n\tv_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,0,1] op_sel_hi:[0,1,0]" : "=v"(r) : "v"(c), "v"(l), "v"(k));
     else
         asm("s_nop 0\n\tv_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1]" : "=v"(r) : "v"(c), "v"(l), "v"(k));
     return r;
-#endif
 }
 // The taps of one texel for the lane's two output rows, in three phases so that the caller can run each phase for all texels of a group before the next
 // (a v_log / v_exp result needs a wait state before it is read, and the wave really waits: with a texel's phases back to back the level ran 1.1 us longer):
@@ -599,7 +535,7 @@ __device__ __forceinline__ Tap2 tap2_geometry(neb_f2 h0x, neb_f2 h0y, neb_f2 h0z
     d = pk_fma(h0y, __builtin_shufflevector(bxy, bxy, 1, 1), d);
     d = pk_fma_lo_clamp(h0z, bzw, d);
     Tap2 t;
-    t.l = (neb_f2){NEB_TAP_LOG2(d.x), NEB_TAP_LOG2(d.y)};
+    t.l = (neb_f2){fast_log2(d.x), fast_log2(d.y)};
     t.dz = pk_add_hi(bzw, nz0);
     t.dl = pk_add_hi(azw, nl0);
     return t;
@@ -618,24 +554,17 @@ __device__ __forceinline__ neb_f2 tap2_weight(const Tap2& t, neb_f2 cl, neb_f2 p
     e.y = fmaf(-fabsf(t.dz.y), pc.y, e.y);
     e.x = fmaf(-fabsf(t.dl.x), cl.x, e.x);
     e.y = fmaf(-fabsf(t.dl.y), cl.y, e.y);
-    return (neb_f2){NEB_TAP_EXP2(e.x), NEB_TAP_EXP2(e.y)};
+    return (neb_f2){fast_exp2(e.x), fast_exp2(e.y)};
 }
 
-// The a-trous output store.  A plain store leaves its line dirty in the XCD's L2, and what is dirty when the kernel ends is
-// written back before the next kernel starts (MI355X_MICROARCH.md, "boundary"); written through (sc1) the 33 MB of a level
-// leave beside the arithmetic: 32.4-33.5 us per level against 34.4 (non-temporal stores: 34.5).
+// The a-trous output store, written through (sc1).  A plain store leaves its line dirty in the XCD's L2, and what is dirty when
+// the kernel ends is written back before the next kernel starts (MI355X_MICROARCH.md, "boundary"); written through, the 33 MB
+// of a level leave beside the arithmetic instead.
 typedef float neb_f4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void store_output(float4* p, float4 v)
 {
-#if NEB_ATROUS_STORE == 1
     const neb_f4 d = {v.x, v.y, v.z, v.w};
     asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(d) : "memory");
-#elif NEB_ATROUS_STORE == 2
-    const neb_f4 d = {v.x, v.y, v.z, v.w};
-    __builtin_nontemporal_store(d, reinterpret_cast<neb_f4*>(p));
-#else
-    *p = v;
-#endif
 }
 
 // Direct kernel: one pixel per lane, 25 taps straight from global memory (L1/L2 absorb the reuse).
@@ -702,10 +631,6 @@ __global__ __launch_bounds__(256) void svgf_atrous_direct_kernel(AtrousArgs a)
 //   last level writes radiance[cur], which still holds the frame's input) or from the fused staging (kInFused).
 enum : int { kInClassic = 0, kInLum = 1, kInFused = 2 };
 
-// WX: 64-column blocks per tile.  With 2, a workgroup of eight waves shares the 4 S halo columns over 128 columns (1.5 x the
-// columns staged per output at S = 16 instead of 2) -- measured SLOWER, 39.2 against 36.2 us at S = 16 and 35.3 against 31.9 at
-// S = 8: two large workgroups per CU leave the SIMDs idle at their barriers more than the smaller halo saves.  Product: 1.
-//
 // The columns of a tile.  Up to S = 8 a tile's 64 output columns are consecutive and it stages 64 + 4 S of them.  Beyond, that halo
 // doubles and triples the tile (128 staged columns per 64 outputs at S = 16), so the columns form a lattice too, in GROUPS of
 // XS = 8 pixels (128 bytes of a plane = one L2 line: every load and store instruction still touches whole lines): local column c is
@@ -714,12 +639,16 @@ enum : int { kInClassic = 0, kInLum = 1, kInFused = 2 };
 // of three), and S / XS tiles whose x0 differ by XS interleave over the same span of (64 / XS) S pixels.  For S <= XS this is the
 // plain layout.  Measured inside the frame (same box): S = 16 33.2 us against 34.9; with groups of 4 pixels (64 bytes, 80 staged
 // columns) 35.6 -- an LDS-DMA instruction then touches sixteen half lines instead of eight whole ones.
-template <int S, int R, int IN, int WX = 1>
+template <int S, int IN>
 struct AtrousTile {
-    static constexpr int THREADS = 256 * WX;
+    // R = 2 rows per lane at every step, level 0 with the temporal pass included: 8-row tiles of 68 - 96 staged columns (26 - 37 KB)
+    // fit four workgroups per CU at 128 registers per lane, and the fused kernel's staging then holds four texels per lane, not six,
+    // which is what lets it fit 128 registers at all.  Two rows are also what the packed tap arithmetic pairs (tap2_geometry).
+    static constexpr int R = 2;
+    static constexpr int THREADS = 256;
     static constexpr int XS = S < NEB_ATROUS_XGROUP ? S : NEB_ATROUS_XGROUP; // pixels per column group = the tap stride in local columns
     static constexpr int XM = S / XS;                                        // interleaved tiles per span
-    static constexpr int BW = 64 * WX, SPAN = (BW / XS) * S;                 // output columns of a tile, and the pixels they span
+    static constexpr int BW = 64, SPAN = (BW / XS) * S;                      // output columns of a tile (one per lane), and the pixels they span
     static constexpr int BH = 4 * R, COLS = BW + 4 * XS, ROWS = BH + 4, TOTAL = ROWS * COLS;
     static_assert(S % XS == 0 && 64 % XS == 0, "column groups tile both the step and the wave");
     // pixel column (relative to the tile's x0) of local column c
@@ -727,36 +656,31 @@ struct AtrousTile {
     static constexpr int NLOAD = (TOTAL + THREADS - 1) / THREADS;
     // kInFused keeps {variance, alpha} of the tile's own pixels in a third, small plane
     static constexpr int LDS_BYTES = TOTAL * 2 * 16 + (IN == kInFused ? BH * BW * 8 : 0);
-    // workgroups per CU: what the 160 KB of LDS hold, at most 4 (R <= 2: 128 registers per lane) / 3 (168) -- also the register budget the kernel is compiled for
-    static constexpr int PER_CU_CAP = R <= 2 ? NEB_ATROUS_PER_CU_R2 : (R == 3 ? 4 : 3);
-    static constexpr int PER_CU = PER_CU_CAP < (160 * 1024) / LDS_BYTES ? PER_CU_CAP : (160 * 1024) / LDS_BYTES;
-    static constexpr int WAVES_PER_SIMD = PER_CU * WX < 8 ? PER_CU * WX : 8; // launch bound: k blocks of T threads per CU <=> k T / 256 waves per SIMD
+    // workgroups per CU: what the 160 KB of LDS hold, at most NEB_ATROUS_PER_CU_R2 (4: 128 registers per lane) -- also the register budget the kernel is
+    // compiled for
+    static constexpr int PER_CU = NEB_ATROUS_PER_CU_R2 < (160 * 1024) / LDS_BYTES ? NEB_ATROUS_PER_CU_R2 : (160 * 1024) / LDS_BYTES;
+    static constexpr int WAVES_PER_SIMD = PER_CU < 8 ? PER_CU : 8; // launch bound: k blocks of 256 threads per CU <=> k waves per SIMD
 };
 
-template <int S, int R, int IN, bool OUT_ALPHA, int WX = 1>
-__global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD)) void svgf_atrous_lds_kernel(AtrousArgs a)
+template <int S, int IN, bool OUT_ALPHA>
+__global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf_atrous_lds_kernel(AtrousArgs a)
 {
-    using T = AtrousTile<S, R, IN, WX>;
-    constexpr int BW = T::BW, BH = T::BH, COLS = T::COLS, ROWS = T::ROWS, TOTAL = T::TOTAL, NLOAD = T::NLOAD, THREADS = T::THREADS;
+    using T = AtrousTile<S, IN>;
+    constexpr int R = T::R, BW = T::BW, BH = T::BH, COLS = T::COLS, ROWS = T::ROWS, TOTAL = T::TOTAL, NLOAD = T::NLOAD, THREADS = T::THREADS;
     constexpr int XS = T::XS, XM = T::XM, SPAN = T::SPAN;
-    static_assert(IN != kInFused || (S == 1 && WX == 1), "the fused temporal staging is level 0");
+    static_assert(IN != kInFused || S == 1, "the fused temporal staging is level 0");
     extern __shared__ float4 lds[];
     float4* __restrict__ A = lds;               // {r, g, b, lum}
     float4* __restrict__ B = lds + ROWS * COLS; // {nx, ny, nz, z}
     float2* __restrict__ V = reinterpret_cast<float2*>(lds + 2 * ROWS * COLS); // kInFused: {variance as stored (fp16), alpha} [BH][BW]
 
-#if NEB_ATROUS_STAMPS
-    uint64_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const uint64_t t_begin_real = __builtin_amdgcn_s_memrealtime();
-    uint64_t tprev = __builtin_amdgcn_s_memtime();
-    const uint64_t t_begin = tprev;
-    uint32_t ntiles = 0;
-#endif
     const float4* __restrict__ src = a.src;
     const float4* __restrict__ geometry = a.geometry;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // (wave-uniform: row bases and row addresses become scalar)
-    const int rg = wv & 3, cb = wv >> 2; // the wave's row group (R lattice rows) and 64-column block of the tile
+    // the wave's row group (R lattice rows) and 64-column block of the tile.  A tile is one wave wide, so cb is always 0 and rg = wv, but the
+    // compiler cannot see wv < 4 through readfirstlane: written without cb, every LDS kernel is scheduled differently.
+    const int rg = wv & 3, cb = wv >> 2;
 
     // Tile walk, XCD-aware: workgroups b, b+8, ... share an XCD (and its L2); each XCD takes a contiguous
     // run of tiles, and the workgroups of an XCD interleave inside that run.  Speed only.
@@ -905,50 +829,46 @@ __global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD
     // in this kernel the difference does not show: 192.5 against 192.0 us per frame)
     float cz = a.cz, phiN = a.phiNormal;
     // log2(Kx Ky) + phiN of the six tap classes (|dx|, |dy| in {0, 1, 2}), set up once: computed per tap it would be an add each.
-    // The levels of the fused chain hold all eight constants in vector registers.  The fused kernel and the kernels that prefetch
-    // the next tile's radiance into registers run at their register budget (with the constants in registers the 16-row fused kernel
-    // spilled five, and a kernel that needs scratch memory right after the GI kernels, which use theirs at another size, waits for
-    // the queue's scratch set-up: 57.7 us per launch against 50.9): there they are scalar operands.
+    // The levels of the fused chain (kInLum) hold them in vector registers.  The fused kernel and the kernels that prefetch the next
+    // tile's radiance into registers run at their register budget (with the constants in registers the fused kernel spilled, and a
+    // kernel that needs scratch memory right after the GI kernels, which use theirs at another size, waits for the queue's scratch
+    // set-up): there they are scalar operands, and a texel's taps are evaluated one texel at a time (kLkScalar).
+    constexpr bool kLkScalar = IN != kInLum;
     float lkp[3][3];
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = i; j < 3; ++j) {
             lkp[i][j] = tap_constant(phiN, i, j);
-            if constexpr (IN != kInLum || R == 4) // (R = 4: two pairs of rows per lane leave no registers for the constants either)
+            if constexpr (kLkScalar)
                 lkp[i][j] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, lkp[i][j])));
             else
                 asm volatile("" : "+v"(lkp[i][j]));
             lkp[j][i] = lkp[i][j];
         }
-    if constexpr (IN == kInLum && R != 4)
+    if constexpr (!kLkScalar)
         asm volatile("" : "+v"(cz), "+v"(phiN));
     // the packed tap's constants: {phiNormal, cz}, and per |dx| the pairs {lkp[.][0], lkp[.][1]} and {lkp[.][1], lkp[.][2]} (read straight
-    // or swapped by op_sel): 14 registers where the scalar form holds 8
-    constexpr bool kPacked = NEB_ATROUS_PK && (R == 2 || R == 4) && (IN == kInLum || (IN == kInFused && NEB_ATROUS_PK_FUSED) || (IN == kInClassic && NEB_ATROUS_PK_CLASSIC));
-    constexpr bool kLkScalar = IN != kInLum || R == 4;
-    constexpr bool kPhased = NEB_ATROUS_PK != 3 && IN == kInLum && R != 4; // (the fused kernel has no registers for a whole group's intermediate values)
+    // or swapped by op_sel)
     neb_f2 pcz = {phiN, cz}, lkq[3][2];
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         lkq[i][0] = (neb_f2){lkp[i][0], lkp[i][1]};
         lkq[i][1] = (neb_f2){lkp[i][1], lkp[i][2]};
-        if constexpr (kPacked && !kLkScalar)
+        if constexpr (!kLkScalar)
             asm volatile("" : "+v"(lkq[i][0]), "+v"(lkq[i][1]));
     }
-    if constexpr (kPacked && !kLkScalar)
+    if constexpr (!kLkScalar)
         asm volatile("" : "+v"(pcz));
 
-    NEB_STAMP(0);
     while (have) {
-#if NEB_ATROUS_PRIO
         // The SIMD's arbiter serves its oldest wave first: of the three workgroups of a CU the first-dispatched one races
         // ahead and the youngest is left to finish alone, one wave per SIMD, at half the issue rate.  Priority = tiles still
         // to do lets the workgroups finish together.
         {
             const uint32_t remaining = (t_end - t + wgs_per_xcd - 1u) / wgs_per_xcd; // (this tile included)
-            // (four levels: with 8-row tiles a workgroup has four tiles or more -- 28.7 / 27.4 / 28.0 / 30.6 us for S = 2 .. 16 against
-            // 29.0 / 28.0 / 28.3 / 30.9 with "three and more" as one level; no priorities at all: 32.0 / 30.7 / 31.5 / 34.5)
+            // (four levels: with 8-row tiles a workgroup has four tiles or more, and a separate level for them finishes the
+            // workgroups closer together than "three and more" as one)
             if (remaining >= 4u)
                 __builtin_amdgcn_s_setprio(3);
             else if (remaining == 3u)
@@ -958,7 +878,6 @@ __global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD
             else
                 __builtin_amdgcn_s_setprio(0);
         }
-#endif
         const int cr = nt.r, cjbase = nt.jbase, cx0 = nt.x0;
         // ---- stage the tile ----
         if constexpr (IN == kInClassic) {
@@ -1027,9 +946,7 @@ __global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD
                 }
             }
         }
-        NEB_STAMP(1);
         __syncthreads(); // (also waits for this wave's DMA: an LDS-DMA is a pending LDS write on the VM counter)
-        NEB_STAMP(2);
 
         // ---- next tile: issue its loads now, consume them after this tile is filtered ----
         uint32_t cvar[R];
@@ -1054,7 +971,6 @@ __global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD
                 issue_load(k, nt);
         }
 
-        NEB_STAMP(3);
         // ---- filter the current tile ----
         const int xo = cx0 + T::xcol(cb * 64 + lane + 2 * XS);
         float z0[R], n0x[R], n0y[R], n0z[R], lum0[R], cl[R], alpha0[R];
@@ -1092,181 +1008,115 @@ __global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD
             if ((g & 1) == 0) {
 #pragma unroll
                 for (int j = 0; j < 3; ++j) {
-#if NEB_ATROUS_FEWER_LDS_READS == 1 // timing only (wrong results, and the compiler merges the identical taps: not a clean probe): one texel read per group instead of three / two -- what ANY saving of LDS reads could buy
-                    if (j > 0) {
-                        gA[0][j] = gA[0][0], gB[0][j] = gB[0][0];
-                        continue;
-                    }
-#endif
                     gA[0][j] = A[lrow_base + (j - 2) * XS];
-#if NEB_ATROUS_FEWER_LDS_READS == 2 // timing only (wrong results): the B plane read as 8 bytes instead of 16 -- a quarter of the LDS bytes gone, every VALU instruction still there
-                    {
-                        const float2 b2 = *reinterpret_cast<const float2*>(&B[lrow_base + (j - 2) * XS]);
-                        gB[0][j] = make_float4(b2.x, b2.y, gA[0][j].z, gA[0][j].w);
-                    }
-#else
                     gB[0][j] = B[lrow_base + (j - 2) * XS];
-#endif
                 }
             } else {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-#if NEB_ATROUS_FEWER_LDS_READS == 1
-                    if (j > 0) {
-                        gA[1][j] = gA[1][0], gB[1][j] = gB[1][0];
-                        continue;
-                    }
-#endif
                     gA[1][j] = A[lrow_base + (j + 1) * XS];
-#if NEB_ATROUS_FEWER_LDS_READS == 2
-                    {
-                        const float2 b2 = *reinterpret_cast<const float2*>(&B[lrow_base + (j + 1) * XS]);
-                        gB[1][j] = make_float4(b2.x, b2.y, gA[1][j].z, gA[1][j].w);
-                    }
-#else
                     gB[1][j] = B[lrow_base + (j + 1) * XS];
-#endif
                 }
             }
         };
-        if constexpr (kPacked) {
-            // the lane's output rows side by side in PAIRS (see tap2_geometry): pair p = rows 2 p, 2 p + 1; staged row ir is row lir = ir - 2 p of the
-            // pair's own six, tap dy = lir - 2 of its first row and lir - 3 of its second.  (R = 4, round 5: two pairs per lane -- a staged texel is
-            // read from LDS once for up to four output rows, 20 reads per pixel instead of 30 -- at the price of 16-row tiles and their registers.)
-            constexpr int NP = R / 2;
-            neb_f2 h0x[NP], h0y[NP], h0z[NP], nz0[NP], nl0[NP], cl2[NP], sr2[NP], sg2[NP], sb2[NP], sw2[NP];
+        // The lane's output rows side by side in PAIRS (see tap2_geometry): pair p = rows 2 p, 2 p + 1; staged row ir is row lir = ir - 2 p of the
+        // pair's own six, tap dy = lir - 2 of its first row and lir - 3 of its second.  (R = 2 makes it one pair; written without the pair loop,
+        // the fused chain's kernels are scheduled differently.)
+        constexpr int NP = R / 2;
+        neb_f2 h0x[NP], h0y[NP], h0z[NP], nz0[NP], nl0[NP], cl2[NP], sr2[NP], sg2[NP], sb2[NP], sw2[NP];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+            h0x[p] = (neb_f2){n0x[2 * p], n0x[2 * p + 1]}, h0y[p] = (neb_f2){n0y[2 * p], n0y[2 * p + 1]}, h0z[p] = (neb_f2){n0z[2 * p], n0z[2 * p + 1]};
+            nz0[p] = (neb_f2){-z0[2 * p], -z0[2 * p + 1]}, nl0[p] = (neb_f2){-lum0[2 * p], -lum0[2 * p + 1]}, cl2[p] = (neb_f2){cl[2 * p], cl[2 * p + 1]};
+            sr2[p] = sg2[p] = sb2[p] = sw2[p] = (neb_f2){0.f, 0.f};
+        }
+        load_group(0);
+#pragma unroll
+        for (int g = 0; g < 2 * (R + 4); ++g) {
+            const int ir = g >> 1;
+            if ((g & 1) == 0 && ir < NLOAD && have_next)
+                issue_load(ir, nt);
+            if (g + 1 < 2 * (R + 4))
+                load_group(g + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            constexpr int kMaxGroup = 3;
+            const int ng = (g & 1) ? 2 : 3; // texels of this group: dx = -2, -1, 0 or 1, 2
 #pragma unroll
             for (int p = 0; p < NP; ++p) {
-                h0x[p] = (neb_f2){n0x[2 * p], n0x[2 * p + 1]}, h0y[p] = (neb_f2){n0y[2 * p], n0y[2 * p + 1]}, h0z[p] = (neb_f2){n0z[2 * p], n0z[2 * p + 1]};
-                nz0[p] = (neb_f2){-z0[2 * p], -z0[2 * p + 1]}, nl0[p] = (neb_f2){-lum0[2 * p], -lum0[2 * p + 1]}, cl2[p] = (neb_f2){cl[2 * p], cl[2 * p + 1]};
-                sr2[p] = sg2[p] = sb2[p] = sw2[p] = (neb_f2){0.f, 0.f};
-            }
-            load_group(0);
+                const int lir = ir - 2 * p;
+                if (lir == 0 || lir == 5) { // taps of one row only (dy = -2 of the pair's first row, dy = +2 of its second)
+                    const int k = lir == 0 ? 0 : 1;
 #pragma unroll
-            for (int g = 0; g < 2 * (R + 4); ++g) {
-                const int ir = g >> 1;
-                if ((g & 1) == 0 && ir < NLOAD && have_next)
-                    issue_load(ir, nt);
-                if (g + 1 < 2 * (R + 4))
-                    load_group(g + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                constexpr int kMaxGroup = 3;
-                const int ng = (g & 1) ? 2 : 3; // texels of this group: dx = -2, -1, 0 or 1, 2
-#pragma unroll
-                for (int p = 0; p < NP; ++p) {
-                    const int lir = ir - 2 * p;
-                    if (lir < 0 || lir > 5)
-                        continue;
-                    if (lir == 0 || lir == 5) { // taps of one row only (dy = -2 of the pair's first row, dy = +2 of its second)
-                        const int k = lir == 0 ? 0 : 1;
-#pragma unroll
-                        for (int j = 0; j < ng; ++j) {
-                            const int dx = (g & 1) ? j + 1 : j - 2, adx = dx < 0 ? -dx : dx;
-                            const float4 tA = gA[g & 1][j];
-                            const float4 tB = gB[g & 1][j];
-                            const float w = tap_weight_neg(h0x[p][k], h0y[p][k], h0z[p][k], nz0[p][k], nl0[p][k], cl2[p][k], tA, tB, pcz.x, pcz.y, lkq[adx][1].y);
-                            sr2[p][k] = fmaf(w, tA.x, sr2[p][k]);
-                            sg2[p][k] = fmaf(w, tA.y, sg2[p][k]);
-                            sb2[p][k] = fmaf(w, tA.z, sb2[p][k]);
-                            sw2[p][k] += w;
-                        }
-                    } else if constexpr (kLkScalar) {
-                        // the fused kernel: one texel at a time (its staging phase leaves no registers for a whole group's intermediate values)
-#pragma unroll
-                        for (int j = 0; j < ng; ++j) {
-                            const int dx = (g & 1) ? j + 1 : j - 2, adx = dx < 0 ? -dx : dx;
-                            const float4 tA = gA[g & 1][j];
-                            const Tap2 t = tap2_geometry(h0x[p], h0y[p], h0z[p], nz0[p], nl0[p], tA, gB[g & 1][j]);
-                            const neb_f2 w = (lir == 1)   ? tap2_weight<false, true>(t, cl2[p], pcz, lkq[adx][1])
-                                             : (lir == 2) ? tap2_weight<false, true>(t, cl2[p], pcz, lkq[adx][0])
-                                             : (lir == 3) ? tap2_weight<true, true>(t, cl2[p], pcz, lkq[adx][0])
-                                                          : tap2_weight<true, true>(t, cl2[p], pcz, lkq[adx][1]);
-                            const neb_f2 axy = {tA.x, tA.y}, azw = {tA.z, tA.w};
-                            sr2[p] = pk_fma(w, __builtin_shufflevector(axy, axy, 0, 0), sr2[p]);
-                            sg2[p] = pk_fma(w, __builtin_shufflevector(axy, axy, 1, 1), sg2[p]);
-                            sb2[p] = pk_fma(w, __builtin_shufflevector(azw, azw, 0, 0), sb2[p]);
-                            sw2[p] += w;
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    } else {
-                        Tap2 t[kMaxGroup];
-                        neb_f2 w[kMaxGroup];
-#pragma unroll
-                        for (int j = 0; j < ng; ++j)
-                            t[j] = tap2_geometry(h0x[p], h0y[p], h0z[p], nz0[p], nl0[p], gA[g & 1][j], gB[g & 1][j]);
-                        if constexpr (kPhased)
-                            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int j = 0; j < ng; ++j) {
-                            const int dx = (g & 1) ? j + 1 : j - 2, adx = dx < 0 ? -dx : dx;
-                            // (|dy0|, |dy1|) = (1, 2), (0, 1), (1, 0), (2, 1) for lir = 1 .. 4: the constant pairs {0, 1} and {1, 2}, straight or swapped
-                            w[j] = (lir == 1)   ? tap2_weight<false, kLkScalar>(t[j], cl2[p], pcz, lkq[adx][1])
-                                   : (lir == 2) ? tap2_weight<false, kLkScalar>(t[j], cl2[p], pcz, lkq[adx][0])
-                                   : (lir == 3) ? tap2_weight<true, kLkScalar>(t[j], cl2[p], pcz, lkq[adx][0])
-                                                : tap2_weight<true, kLkScalar>(t[j], cl2[p], pcz, lkq[adx][1]);
-                        }
-                        if constexpr (kPhased)
-                            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int j = 0; j < ng; ++j) {
-                            const float4 tA = gA[g & 1][j];
-                            const neb_f2 axy = {tA.x, tA.y}, azw = {tA.z, tA.w};
-                            sr2[p] = pk_fma(w[j], __builtin_shufflevector(axy, axy, 0, 0), sr2[p]);
-                            sg2[p] = pk_fma(w[j], __builtin_shufflevector(axy, axy, 1, 1), sg2[p]);
-                            sb2[p] = pk_fma(w[j], __builtin_shufflevector(azw, azw, 0, 0), sb2[p]);
-                            sw2[p] += w[j];
-                        }
+                    for (int j = 0; j < ng; ++j) {
+                        const int dx = (g & 1) ? j + 1 : j - 2, adx = dx < 0 ? -dx : dx;
+                        const float4 tA = gA[g & 1][j];
+                        const float4 tB = gB[g & 1][j];
+                        const float w = tap_weight_neg(h0x[p][k], h0y[p][k], h0z[p][k], nz0[p][k], nl0[p][k], cl2[p][k], tA, tB, pcz.x, pcz.y, lkq[adx][1].y);
+                        sr2[p][k] = fmaf(w, tA.x, sr2[p][k]);
+                        sg2[p][k] = fmaf(w, tA.y, sg2[p][k]);
+                        sb2[p][k] = fmaf(w, tA.z, sb2[p][k]);
+                        sw2[p][k] += w;
                     }
-                    asm volatile("" : "+v"(sr2[p]), "+v"(sg2[p]), "+v"(sb2[p]), "+v"(sw2[p])); // (pinned for the reason given below)
-                    if constexpr (NP > 1)
+                } else if constexpr (kLkScalar) {
+                    // one texel at a time (the fused kernel's staging phase leaves no registers for a whole group's intermediate values)
+#pragma unroll
+                    for (int j = 0; j < ng; ++j) {
+                        const int dx = (g & 1) ? j + 1 : j - 2, adx = dx < 0 ? -dx : dx;
+                        const float4 tA = gA[g & 1][j];
+                        const Tap2 t = tap2_geometry(h0x[p], h0y[p], h0z[p], nz0[p], nl0[p], tA, gB[g & 1][j]);
+                        const neb_f2 w = (lir == 1)   ? tap2_weight<false, true>(t, cl2[p], pcz, lkq[adx][1])
+                                         : (lir == 2) ? tap2_weight<false, true>(t, cl2[p], pcz, lkq[adx][0])
+                                         : (lir == 3) ? tap2_weight<true, true>(t, cl2[p], pcz, lkq[adx][0])
+                                                      : tap2_weight<true, true>(t, cl2[p], pcz, lkq[adx][1]);
+                        const neb_f2 axy = {tA.x, tA.y}, azw = {tA.z, tA.w};
+                        sr2[p] = pk_fma(w, __builtin_shufflevector(axy, axy, 0, 0), sr2[p]);
+                        sg2[p] = pk_fma(w, __builtin_shufflevector(axy, axy, 1, 1), sg2[p]);
+                        sb2[p] = pk_fma(w, __builtin_shufflevector(azw, azw, 0, 0), sb2[p]);
+                        sw2[p] += w;
                         __builtin_amdgcn_sched_barrier(0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
+                    }
+                } else {
+                    // the whole group phase by phase: geometry, weights, sums (see tap2_geometry)
+                    Tap2 t[kMaxGroup];
+                    neb_f2 w[kMaxGroup];
 #pragma unroll
-            for (int k = 0; k < R; ++k) {
-                sr[k] = sr2[k >> 1][k & 1];
-                sg[k] = sg2[k >> 1][k & 1];
-                sb[k] = sb2[k >> 1][k & 1];
-                sw[k] = sw2[k >> 1][k & 1];
-            }
-        } else {
-            load_group(0);
+                    for (int j = 0; j < ng; ++j)
+                        t[j] = tap2_geometry(h0x[p], h0y[p], h0z[p], nz0[p], nl0[p], gA[g & 1][j], gB[g & 1][j]);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int g = 0; g < 2 * (R + 4); ++g) {
-                const int ir = g >> 1;
-                if ((g & 1) == 0 && ir < NLOAD && have_next)
-                    issue_load(ir, nt);
-                if (g + 1 < 2 * (R + 4))
-                    load_group(g + 1);
-                __builtin_amdgcn_sched_barrier(0);
+                    for (int j = 0; j < ng; ++j) {
+                        const int dx = (g & 1) ? j + 1 : j - 2, adx = dx < 0 ? -dx : dx;
+                        // (|dy0|, |dy1|) = (1, 2), (0, 1), (1, 0), (2, 1) for lir = 1 .. 4: the constant pairs {0, 1} and {1, 2}, straight or swapped
+                        w[j] = (lir == 1)   ? tap2_weight<false, false>(t[j], cl2[p], pcz, lkq[adx][1])
+                               : (lir == 2) ? tap2_weight<false, false>(t[j], cl2[p], pcz, lkq[adx][0])
+                               : (lir == 3) ? tap2_weight<true, false>(t[j], cl2[p], pcz, lkq[adx][0])
+                                            : tap2_weight<true, false>(t[j], cl2[p], pcz, lkq[adx][1]);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int j = 0; j < ((g & 1) ? 2 : 3); ++j) {
-                    const int dx = (g & 1) ? j + 1 : j - 2;
-                    const float4 tA = gA[g & 1][j];
-                    const float4 tB = gB[g & 1][j];
-#pragma unroll
-                    for (int k = 0; k < R; ++k) {
-                        const int dy = ir - k - 2;
-                        if (dy < -2 || dy > 2)
-                            continue;
-                        const float w = tap_weight(n0x[k], n0y[k], n0z[k], z0[k], lum0[k], cl[k], tA, tB, phiN, cz, lkp[dx < 0 ? -dx : dx][dy < 0 ? -dy : dy]);
-                        sr[k] = fmaf(w, tA.x, sr[k]);
-                        sg[k] = fmaf(w, tA.y, sg[k]);
-                        sb[k] = fmaf(w, tA.z, sb[k]);
-                        sw[k] += w;
+                    for (int j = 0; j < ng; ++j) {
+                        const float4 tA = gA[g & 1][j];
+                        const neb_f2 axy = {tA.x, tA.y}, azw = {tA.z, tA.w};
+                        sr2[p] = pk_fma(w[j], __builtin_shufflevector(axy, axy, 0, 0), sr2[p]);
+                        sg2[p] = pk_fma(w[j], __builtin_shufflevector(axy, axy, 1, 1), sg2[p]);
+                        sb2[p] = pk_fma(w[j], __builtin_shufflevector(azw, azw, 0, 0), sb2[p]);
+                        sw2[p] += w[j];
                     }
                 }
-                // Pin the partial sums here: they only feed the predicated store below, so LLVM would
-                // otherwise sink ALL the arithmetic under that branch and keep every staged texel live
-                // (spilling ~1.3 KB per lane).  The sched_barrier keeps one group's ds_reads per region.
-#pragma unroll
-                for (int k = 0; k < R; ++k)
-                    asm volatile("" : "+v"(sr[k]), "+v"(sg[k]), "+v"(sb[k]), "+v"(sw[k]));
-                __builtin_amdgcn_sched_barrier(0);
+                // Pin the partial sums here: they only feed the predicated store below, so LLVM would otherwise sink ALL the arithmetic
+                // under that branch and keep every staged texel live (spilling ~1.3 KB per lane).  The sched_barrier keeps one group's
+                // ds_reads per region.
+                asm volatile("" : "+v"(sr2[p]), "+v"(sg2[p]), "+v"(sb2[p]), "+v"(sw2[p]));
             }
+            __builtin_amdgcn_sched_barrier(0);
         }
-        NEB_STAMP(4);
+#pragma unroll
+        for (int k = 0; k < R; ++k) {
+            sr[k] = sr2[k >> 1][k & 1];
+            sg[k] = sg2[k >> 1][k & 1];
+            sb[k] = sb2[k >> 1][k & 1];
+            sw[k] = sw2[k >> 1][k & 1];
+        }
 #pragma unroll
         for (int k = 0; k < R; ++k) {
             if (!valid[k])
@@ -1276,72 +1126,27 @@ __global__ __launch_bounds__(256 * WX, (AtrousTile<S, R, IN, WX>::WAVES_PER_SIMD
             const float r = sr[k] * inv, g = sg[k] * inv, b = sb[k] * inv;
             store_output(a.dst + ((size_t)(yo - a.row_begin) * a.W + xo), make_float4(r, g, b, OUT_ALPHA ? alpha0[k] : luminance(r, g, b)));
         }
-        NEB_STAMP(5);
         have = have_next;
         if (have)
             __syncthreads(); // everyone is done reading LDS before the next tile overwrites it
-        NEB_STAMP(6);
-#if NEB_ATROUS_STAMPS
-        ++ntiles;
-#endif
     }
-#if NEB_ATROUS_STAMPS
-    if (lane == 0) {
-        unsigned long long* o = a.stamps + ((size_t)blockIdx.x * 4 + wv) * 16;
-        for (int i = 0; i < 7; ++i)
-            o[i] = st[i];
-        o[7] = __builtin_amdgcn_s_memtime() - t_begin;
-        o[8] = t_begin_real;
-        o[9] = __builtin_amdgcn_s_memrealtime();
-        o[10] = ntiles;
-        o[11] = __builtin_amdgcn_s_getreg(6164 /* HW_REG_XCC_ID (20), offset 0, size 4: ((4-1)<<11)|20 */);
-        o[12] = __builtin_amdgcn_s_getreg(((32 - 1) << 11) | 4 /* HW_REG_HW_ID */);
-        o[13] = __builtin_amdgcn_s_getreg(((32 - 1) << 11) | 6 /* HW_REG_LDS_ALLOC */);
-    }
-#endif
 }
-
-#if NEB_ATROUS_STAMPS
-// one stamp block per step (log2 S = 0..5): 2048 workgroups x 4 waves x 16 words; read back by neb_debug_atrous_stamps
-static unsigned long long* g_stamp_buf = nullptr;
-static uint32_t g_stamp_grid[6] = {0, 0, 0, 0, 0, 0};
-static constexpr size_t kStampWords = 2048 * 4 * 16;
-static unsigned long long* atrous_stamp_buffer(int S, uint32_t grid)
-{
-    if (!g_stamp_buf && hipMalloc(&g_stamp_buf, 6 * kStampWords * 8) != hipSuccess)
-        return nullptr;
-    int l = 0;
-    while ((1 << l) < S)
-        ++l;
-    g_stamp_grid[l] = grid;
-    return g_stamp_buf + (size_t)l * kStampWords;
-}
-extern "C" int neb_debug_atrous_stamps(unsigned long long* host, uint32_t* grids)
-{
-    if (!g_stamp_buf)
-        return -1;
-    (void)hipDeviceSynchronize();
-    for (int l = 0; l < 6; ++l)
-        grids[l] = g_stamp_grid[l];
-    return hipMemcpy(host, g_stamp_buf, 6 * kStampWords * 8, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -2;
-}
-#endif
 
 // (Measured and dropped: a double-buffered LDS variant that weaves the staging of tile i+1 into the row loop of
 // tile i, one barrier per tile -- 45-94 us per level against 41-49 us for the kernel above; the longer live
 // ranges cost more than the barrier and the exposed decode they remove.  Round 3: the geometry texels prefetched into
 // registers like the radiance instead of the DMA at the tile boundary: 45 us per level against 35.)
-template <int S, int R, int IN, bool OUT_ALPHA, int WX = 1>
+template <int S, int IN, bool OUT_ALPHA>
 static hipError_t launch_lds(AtrousArgs a, int device, int num_cus, hipStream_t s)
 {
-    using T = AtrousTile<S, R, IN, WX>;
+    using T = AtrousTile<S, IN>;
     constexpr size_t lds_bytes = (size_t)T::LDS_BYTES;
     // the dynamic-LDS limit is a per-device function attribute: remember which devices have it (one bit each; a
     // device ordinal beyond the mask just sets it on every launch)
     static std::atomic<uint64_t> attr_set{0};
     const uint64_t bit = (device >= 0 && device < 64) ? (1ull << device) : 0ull;
     if (!(attr_set.load(std::memory_order_acquire) & bit)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&svgf_atrous_lds_kernel<S, R, IN, OUT_ALPHA, WX>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&svgf_atrous_lds_kernel<S, IN, OUT_ALPHA>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess)
             return e;
@@ -1358,25 +1163,20 @@ static hipError_t launch_lds(AtrousArgs a, int device, int num_cus, hipStream_t 
     if (grid > a.nblocks)
         grid = a.nblocks;
     grid = ((grid + 7u) / 8u) * 8u;
-#if NEB_ATROUS_STAMPS
-    a.stamps = atrous_stamp_buffer(S, grid);
-#endif
-    hipLaunchKernelGGL((svgf_atrous_lds_kernel<S, R, IN, OUT_ALPHA, WX>), dim3(grid), dim3(T::THREADS), lds_bytes, s, a);
+    hipLaunchKernelGGL((svgf_atrous_lds_kernel<S, IN, OUT_ALPHA>), dim3(grid), dim3(T::THREADS), lds_bytes, s, a);
     return hipGetLastError();
 }
 
-// R = 2 rows per lane at every step (12 staged rows of 68 - 96 columns: 26 - 37 KB, 4 workgroups per CU, 128 registers per lane),
-// as measured -- the fused temporal + level-0 kernel included (NEB_ATROUS_R_FUSED)
 template <int IN, bool OUT_ALPHA>
 static hipError_t launch_lds_step(const AtrousArgs& a, uint32_t step, int device, int num_cus, hipStream_t s)
 {
     switch (step) {
-    case 1: return launch_lds<1, NEB_ATROUS_R_NARROW, IN, OUT_ALPHA>(a, device, num_cus, s);
-    case 2: return launch_lds<2, NEB_ATROUS_R_NARROW, IN, OUT_ALPHA>(a, device, num_cus, s);
-    case 4: return launch_lds<4, NEB_ATROUS_R_NARROW, IN, OUT_ALPHA>(a, device, num_cus, s);
-    case 8: return launch_lds<8, 2, IN, OUT_ALPHA, NEB_ATROUS_WX8>(a, device, num_cus, s);
-    case 16: return launch_lds<16, 2, IN, OUT_ALPHA, NEB_ATROUS_WX16>(a, device, num_cus, s);
-    case 32: return launch_lds<32, 2, IN, OUT_ALPHA, NEB_ATROUS_WX16>(a, device, num_cus, s);
+    case 1: return launch_lds<1, IN, OUT_ALPHA>(a, device, num_cus, s);
+    case 2: return launch_lds<2, IN, OUT_ALPHA>(a, device, num_cus, s);
+    case 4: return launch_lds<4, IN, OUT_ALPHA>(a, device, num_cus, s);
+    case 8: return launch_lds<8, IN, OUT_ALPHA>(a, device, num_cus, s);
+    case 16: return launch_lds<16, IN, OUT_ALPHA>(a, device, num_cus, s);
+    case 32: return launch_lds<32, IN, OUT_ALPHA>(a, device, num_cus, s);
     default: return hipErrorInvalidValue;
     }
 }
@@ -1460,7 +1260,7 @@ hipError_t launch_atrous_fused_temporal(const SvgfLaunch& L, bool only_level, co
     a.t_alpha = L.p.alpha;
     a.t_varianceEps = L.p.varianceEps;
     const int num_cus = L.num_cus > 0 ? L.num_cus : 256;
-    return only_level ? launch_lds<1, NEB_ATROUS_R_FUSED, kInFused, true>(a, L.device, num_cus, s) : launch_lds<1, NEB_ATROUS_R_FUSED, kInFused, false>(a, L.device, num_cus, s);
+    return only_level ? launch_lds<1, kInFused, true>(a, L.device, num_cus, s) : launch_lds<1, kInFused, false>(a, L.device, num_cus, s);
 }
 
 } // namespace neb

@@ -1,5 +1,5 @@
 """One-time costs on the bench scene: scene upload + texture tables + BVH build (wall), the BVH build alone (the library's own
-timer) and the tree it gives.  python tools/time_build.py   (NEB_LIB_PATH selects an A/B build, e.g. -DNEB_SAH_BIG=0)"""
+timer) and the tree it gives.  python tools/time_build.py   (NEB_LIB_PATH selects a tuning build, e.g. -DNEB_SAH_BINS=16)"""
 import os
 import sys
 import time
