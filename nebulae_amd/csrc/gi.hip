@@ -91,6 +91,9 @@ struct GiArgs {
     uint32_t list_cap, list_set;
     float smin[3], sinv[3];      // scene box for the Morton keys
     uint32_t first_px, n_px;     // dispatched pixel range [first_px, first_px + n_px) of the resident planes
+    // (read by gi_shade_kernel only, and last: the other kernels' arguments stay where they were)
+    const ShadeHeader* heads;    // per-geometry shade headers (GiState::shade_heads)
+    float sun_L[3], sun_B[3], sun_T[3]; // frame of the sun-disk samples for c.sunLightDirection (sun_frame, gi_device.h)
 };
 // Position of this workgroup in the dispatch (tile number, or run of 64 sorted rays).  Workgroups are dealt round-robin
 // over the 8 XCDs, each with its own L2.  With RUNS > 0 the dispatch is cut into RUNS segments and inside a segment each
@@ -290,12 +293,13 @@ struct ShadeOut {
 // ReconstructSurfaceData, sun-disk shadow ray + BRDF contribution, and for maxPathVertices > 2 the next bounce ray.
 // FAST: the arithmetic policy of gi_device.h (1-ulp hardware rcp / rsq / sqrt / sin / cos, the forms an HLSL compiler emits);
 // FAST = false is the C arithmetic of the oracle (option "gi_exact_shade", see neb_set_option).
-// STAGED: the hit triangle's shading record is already in LDS at `staged` (gi_shade_kernel); otherwise it is fetched here.
-template <bool FAST, bool STAGED>
-__device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const float4 h, ShadeOut& o, const float4* staged, uint32_t staged_swz)
+// The hit triangle's shading record is in LDS at `staged` (gi_shade_kernel), and `pth`, `rd`, `ro` = R.path[i], R.ray_d[i], R.ray_o[i]
+// were loaded beside the hit, before the gather.  A hit pixel's loads wait for one another only where the data do:
+// {hit, path, rays} -> record -> {shade header, first pair of hint triangles} -> texture footprint.
+template <bool FAST>
+__device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const float4 h, const float4 pth, const float4 rd, const float4 ro, ShadeOut& o,
+                                            const float4* staged, uint32_t staged_swz)
 {
-    const float4 pth = a.R.path[i];
-    const float4 rd = a.R.ray_d[i];
     const uint32_t trav_iters = a.stats ? __float_as_uint(a.R.srec[4 * i + kSrContrib].w) : 0u; // diagnostics (written by the tracer)
     float3 throughput = f3(pth.x, pth.y, pth.z);
     if (!(a.sample == 0 && a.bounce == 1))
@@ -310,19 +314,24 @@ __device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const flo
     } else if (alive && h.x >= 0.0f) {
         const uint32_t tri = __float_as_uint(h.w);
         Surface surf;
-        uint32_t geom;
-        TriShade ts;
-        if constexpr (STAGED)
-            ts = load_tri_shade_at(staged, staged_swz);
-        else
-            ts = load_tri_shade(a.S, tri);
-        const bool shaded = reconstruct_surface<FAST>(a.S, ts, h.y, h.z, surf, geom);
+        const TriShade ts = load_tri_shade_at(staged, staged_swz);
+        const ShadeHead head = load_shade_header(a.heads, ts.geom);
+        // The first pair of occluder hints is named by the record: its triangles are requested here, beside the header, by every
+        // lane whose hinted side is not proven lit -- a superset of the lanes that test them below (the side the ray leaves on is
+        // not known yet) -- and tested where they always were, under the same condition.
+        const bool hint_fetch = a.sun_table && a.hint_pairs && !((ts.lit >> ts.hint_side) & 1u) && ts.hint[0] != kNoHint;
+        float4 ha0 = make_float4(0.f, 0.f, 0.f, 0.f), hb0 = ha0, hc0 = ha0, ha1 = ha0, hb1 = ha0, hc1 = ha0;
+        if (hint_fetch) {
+            const uint32_t h0 = ts.hint[0], h1 = ts.hint[1] != kNoHint ? ts.hint[1] : h0;
+            ha0 = a.S.tris[3 * h0], hb0 = a.S.tris[3 * h0 + 1], hc0 = a.S.tris[3 * h0 + 2];
+            ha1 = a.S.tris[3 * h1], hb1 = a.S.tris[3 * h1 + 1], hc1 = a.S.tris[3 * h1 + 2];
+        }
+        const bool shaded = reconstruct_surface<FAST>(a.S, head, ts, h.y, h.z, surf);
         dbg.t = h.x;
-        dbg.geometry = geom;
+        dbg.geometry = ts.geom;
         if (a.hits)
             dbg.primitive = __float_as_uint(a.S.shade[8 * (size_t)tri + 7].x);
         if (shaded) {
-            const float4 ro = a.R.ray_o[i];
             const float3 org = f3(ro.x, ro.y, ro.z), dir = f3(rd.x, rd.y, rd.z);
             const float3 hitP = org + dir * h.x;
             const float3 V = normalize3<FAST>(-dir); // :522
@@ -334,11 +343,8 @@ __device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const flo
             // million at a silhouette -- 5e-4 of a frame's L2 norm each time.  ~150 instructions per hit in a pass bound by
             // memory; the BRDF and the surface reconstruction keep the 1-ulp hardware forms (no discrete outcome hangs on them).
             const float angle = a0 * 2.0f * 3.1415926535f, dist = fsqrt<false>(a1);
-            const float3 sun_dir = f3(a.c.sunLightDirection[0], a.c.sunLightDirection[1], a.c.sunLightDirection[2]);
             const float3 sun_rad = f3(a.c.sunLightRadiance[0], a.c.sunLightRadiance[1], a.c.sunLightRadiance[2]);
-            const float3 L = normalize3<false>(-sun_dir);
-            const float3 Bv = normalize3<false>(perpendicular(L));
-            const float3 T = cross3(Bv, L);
+            const float3 L = f3(a.sun_L[0], a.sun_L[1], a.sun_L[2]), Bv = f3(a.sun_B[0], a.sun_B[1], a.sun_B[2]), T = f3(a.sun_T[0], a.sun_T[1], a.sun_T[2]);
             float sn_a, cs_a;
             det_sincosf(angle, sn_a, cs_a);
             const float3 inc = normalize3<false>(L + (Bv * sn_a + T * cs_a) * a.c.sunTanHalfAngle * dist);
@@ -359,6 +365,11 @@ __device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const flo
                     const uint32_t h0 = ts.hint[pair];
                     if (h0 == kNoHint || (uint32_t)pair >= 2u * a.hint_pairs)
                         break;
+                    if (pair == 0) { // (fetched beside the header; every lane that gets here has them)
+                        hinted_hit = intersect_tri_regs(ha0, hb0, hc0, so, inc, 0.001f, kTraceMax, tt, uu, vv) ||
+                                     intersect_tri_regs(ha1, hb1, hc1, so, inc, 0.001f, kTraceMax, tt, uu, vv);
+                        continue;
+                    }
                     const uint32_t h1 = ts.hint[pair + 1] != kNoHint ? ts.hint[pair + 1] : h0;
                     const float4 a0 = a.S.tris[3 * h0], b0 = a.S.tris[3 * h0 + 1], c0 = a.S.tris[3 * h0 + 2];
                     const float4 a1 = a.S.tris[3 * h1], b1 = a.S.tris[3 * h1 + 1], c1 = a.S.tris[3 * h1 + 2];
@@ -437,8 +448,19 @@ __global__ __launch_bounds__(64, NEB_SHADE_WAVES) void gi_shade_kernel(GiArgs a)
     const bool active = gi_pixel<kShadeRuns>(a, x, y, i);
     ShadeOut o;
     float4 h = make_float4(-2.0f, 0.f, 0.f, 0.f);
-    if (active)
+    // Everything whose address is the pixel's is requested at once, before the gather: the hit, the path, both halves of the ray (the
+    // origin is rewritten for the next bounce by this same lane, after its last use) and -- where this launch finishes the pixels that
+    // leave no ray -- the radiance the sum is added into (a pixel that does leave a ray has read its 16 bytes for nothing).
+    const bool final_vertex = a.sample + 1 == a.c.samplesPerPixel && a.bounce + 1 >= a.c.maxPathVertices && !a.defer_resolve;
+    float4 pth = make_float4(0.f, 0.f, 0.f, 0.f), rd = pth, ro = pth, rad = pth;
+    if (active) {
         h = a.R.hit[i];
+        pth = a.R.path[i];
+        rd = a.R.ray_d[i];
+        ro = a.R.ray_o[i];
+        if (a.list && final_vertex)
+            rad = a.radiance[i];
+    }
     // The 128-byte shading records of the wave's (up to) 64 hit triangles are gathered COOPERATIVELY: eight lanes fetch
     // the eight 16-byte pieces of one record -- one cache line per eight lanes instead of one per lane and load -- straight
     // into LDS (LDS-DMA), eight records per instruction.  The texture-address units, which the scattered per-lane gathers
@@ -459,19 +481,18 @@ __global__ __launch_bounds__(64, NEB_SHADE_WAVES) void gi_shade_kernel(GiArgs a)
     }
     __syncthreads(); // (waits for the DMA: an LDS-DMA is a pending LDS write on the VM counter)
     if (active)
-        shade_pixel<FAST, true>(a, i, h, o, smem + lane * 8u, lane & 7u);
+        shade_pixel<FAST>(a, i, h, pth, rd, ro, o, smem + lane * 8u, lane & 7u);
     if (a.list) {
         // Compacted tail (the sun table is on: most pixels have no ray left to trace).  A pixel WITHOUT a ray is finished here, in
         // tile order: what gi_shadow_trace_kernel does for it after gathering its record in sorted order -- radiance[cur] += sum / spp
         // on the last vertex of the last sample (the stand-in for NRC Resolve), otherwise carry the sum -- same operands, same
         // order.  A pixel WITH a ray writes its 64-byte record and appends itself to one of the ray lists.
         const bool trace = active && o.shadow_d.w != 0.0f;
-        const bool final_vertex = a.sample + 1 == a.c.samplesPerPixel && a.bounce + 1 >= a.c.maxPathVertices && !a.defer_resolve;
         if (active && !trace) {
             if (final_vertex) {
                 if (o.sum.x != 0.0f || o.sum.y != 0.0f || o.sum.z != 0.0f) {
                     const float inv_spp = 1.0f / (float)a.c.samplesPerPixel;
-                    float4 r = a.radiance[i];
+                    float4 r = rad;
                     r.x += o.sum.x * inv_spp;
                     r.y += o.sum.y * inv_spp;
                     r.z += o.sum.z * inv_spp;
@@ -983,6 +1004,8 @@ static int gi_dispatch(neb_ctx* ctx, const neb_gi_constants* c, uint32_t row0, u
         g->last_dispatch_stream = (hipStream_t)stream;
         g->last_dispatch_stream_set = true;
     }
+    a.heads = g->shade_heads;
+    sun_frame(c->sunLightDirection, a.sun_L, a.sun_B, a.sun_T);
     a.sun_table = g->sun_table_state == 1 ? 1u : 0u;
     a.hint_pairs = (uint32_t)g->sun_hints / 2u;
     // the pass that takes the rays the table leaves: the compacted lists, unless the measurement of this table said the sorted pass (GiState::tail_tune)

@@ -1357,6 +1357,24 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         g->view.texels = reinterpret_cast<const uint32_t*>(d_tables);
         g->view.bundles = d_bundles;
     }
+    // the shade pass's per-geometry headers: the two tables above are final here (a new scene makes new ones)
+    std::vector<ShadeHeader> heads(n_geoms);
+    for (uint32_t gi = 0; gi < n_geoms; ++gi) {
+        ShadeHeader& hd = heads[gi];
+        const DevGeom& d = dgeoms[gi];
+        memset(&hd, 0, sizeof(hd));
+        memcpy(hd.m, d.m, sizeof(hd.m));
+        hd.valid = d.valid;
+        hd.material = d.material;
+        hd.tex[0] = hd.tex[1] = hd.tex[2] = -1;
+        if (d.material >= 0) {
+            const DevMat& mt = dmats[d.material];
+            hd.bundle = mt.bundle, hd.bundle_w = mt.bundle_w, hd.bundle_h = mt.bundle_h;
+            memcpy(hd.tex, mt.tex, sizeof(hd.tex));
+            memcpy(hd.albedo, mt.albedo, sizeof(hd.albedo));
+            hd.rough = mt.rough, hd.metal = mt.metal;
+        }
+    }
     g->n_tris = (uint32_t)(g->h_tris.size() / 12);
     memcpy(g->scene_min, smin, sizeof(smin));
     memcpy(g->scene_max, smax, sizeof(smax));
@@ -1364,7 +1382,7 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     if ((e = upload(g, dgeoms, &g->view.geoms)) != hipSuccess || (e = upload(g, dmats, &g->view.mats)) != hipSuccess ||
         (e = upload(g, dtexs, &g->view.texs)) != hipSuccess || (e = upload(g, indices, &g->view.indices)) != hipSuccess ||
         (e = upload(g, normals, &g->view.normals)) != hipSuccess || (e = upload(g, uvs, &g->view.uvs)) != hipSuccess ||
-        (e = upload(g, tangents, &g->view.tangents)) != hipSuccess) {
+        (e = upload(g, tangents, &g->view.tangents)) != hipSuccess || (e = upload(g, heads, &g->shade_heads)) != hipSuccess) {
         gi_destroy(g);
         return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_scene: upload", e);
     }

@@ -189,6 +189,27 @@ __device__ __forceinline__ float3 perpendicular(float3 u) // sun_disk_sampling.h
     const uint32_t zm = 1 ^ (xm | ym);
     return cross3(u, f3((float)xm, (float)ym, (float)zm));
 }
+// The frame of the sun-disk samples -- L = normalize(-sunDir), B = normalize(perpendicular(L)), T = cross(B, L) -- is the same for
+// every pixel of a dispatch: the host computes it once (neb_gi_trace) and the shade pass reads it as kernel arguments.  The operations
+// and their order are those of normalize3<false> / perpendicular / cross3 above (IEEE sqrtf and division, no contraction), which give
+// the same bits on the host as on the device: the oracle reproduces them with host arithmetic.
+__host__ __device__ inline void sun_frame(const float sun_dir[3], float L[3], float B[3], float T[3])
+{
+    const float nx = -sun_dir[0], ny = -sun_dir[1], nz = -sun_dir[2];
+    const float l = sqrtf(nx * nx + ny * ny + nz * nz);
+    L[0] = nx / l, L[1] = ny / l, L[2] = nz / l;
+    const float ax = fabsf(L[0]), ay = fabsf(L[1]), az = fabsf(L[2]);
+    const uint32_t xm = ((ax - ay) < 0 && (ax - az) < 0) ? 1 : 0;
+    const uint32_t ym = (ay - az) < 0 ? (1 ^ xm) : 0;
+    const uint32_t zm = 1 ^ (xm | ym);
+    const float ex = (float)xm, ey = (float)ym, ez = (float)zm;
+    const float px = L[1] * ez - L[2] * ey, py = L[2] * ex - L[0] * ez, pz = L[0] * ey - L[1] * ex;
+    const float pl = sqrtf(px * px + py * py + pz * pz);
+    B[0] = px / pl, B[1] = py / pl, B[2] = pz / pl;
+    T[0] = B[1] * L[2] - B[2] * L[1];
+    T[1] = B[2] * L[0] - B[0] * L[2];
+    T[2] = B[0] * L[1] - B[1] * L[0];
+}
 
 struct Surface {
     float3 GN, SN, albedo;
@@ -802,13 +823,38 @@ template <typename Ptr> __device__ __forceinline__ TriShade load_tri_shade_at(Pt
 }
 __device__ __forceinline__ TriShade load_tri_shade(const SceneView& S, uint32_t tri) { return load_tri_shade_at(S.shade + 8 * (size_t)tri, 0u); }
 
-// ReconstructSurfaceData (pathtracer.hlsl:299-395); `tri` is the sorted triangle index of the hit.
-template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface(const SceneView& S, const TriShade& ts, float bu, float bv, Surface& out, uint32_t& geom)
+// The geometry's shade header in registers: six 16-byte loads of one line, issued together (ShadeHeader, gi_internal.h).
+struct ShadeHead {
+    float m[9];
+    uint32_t valid;
+    int32_t material;
+    DevMat mat;
+};
+__device__ __forceinline__ ShadeHead load_shade_header(const ShadeHeader* heads, uint32_t geom)
 {
-    // the record names its geometry itself: one gathered line per hit, and the geometry / material table reads hang off it
-    // instead of off a second gather into the triangle array
-    geom = ts.geom;
-    const DevGeom g = S.geoms[geom];
+    const float4* q = reinterpret_cast<const float4*>(heads + geom);
+    const float4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
+    ShadeHead h;
+    h.m[0] = q0.x, h.m[1] = q0.y, h.m[2] = q0.z, h.m[3] = q0.w;
+    h.m[4] = q1.x, h.m[5] = q1.y, h.m[6] = q1.z, h.m[7] = q1.w;
+    h.m[8] = q2.x;
+    h.valid = __float_as_uint(q2.y);
+    h.material = (int32_t)__float_as_uint(q2.z);
+    h.mat.bundle = __float_as_uint(q2.w);
+    h.mat.bundle_w = __float_as_uint(q3.x);
+    h.mat.bundle_h = __float_as_uint(q3.y);
+    h.mat.tex[0] = (int32_t)__float_as_uint(q3.z);
+    h.mat.tex[1] = (int32_t)__float_as_uint(q3.w);
+    h.mat.tex[2] = (int32_t)__float_as_uint(q4.x);
+    h.mat.albedo[0] = q4.y, h.mat.albedo[1] = q4.z, h.mat.albedo[2] = q4.w;
+    h.mat.rough = q5.x, h.mat.metal = q5.y;
+    h.mat.pad = 0;
+    return h;
+}
+
+// ReconstructSurfaceData (pathtracer.hlsl:299-395) of a hit on the triangle of record `ts`, whose geometry's header is `g`.
+template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface(const SceneView& S, const ShadeHead& g, const TriShade& ts, float bu, float bv, Surface& out)
+{
     const float b0 = 1.0f - (bu + bv), b1 = bu, b2 = bv;
     if (!g.valid)
         return false; // :313-318
@@ -819,7 +865,7 @@ template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface
     const float v = ts.uv0.y * b0 + ts.uv1.y * b1 + ts.uv2.y * b2;
     if (g.material < 0)
         return false; // :349
-    const DevMat m = S.mats[g.material];
+    const DevMat& m = g.mat;
     MapSamples maps;
     sample_material_maps<FAST>(S, m, u, v, maps);
     if (m.tex[0] < 0) {

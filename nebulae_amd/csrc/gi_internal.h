@@ -34,6 +34,22 @@ struct DevMat {
     uint32_t bundle_w, bundle_h;
     uint32_t pad;
 };
+// What the shade pass takes from a geometry AND from the material it names, side by side in one 128-byte line (built where the two
+// tables are, neb_gi_set_scene): the hit's record names the geometry, and one lookup -- six 16-byte loads of one line -- stands where
+// geoms[geom] -> mats[material] were two that waited for one another.  Same values as the two tables (a geometry without a material
+// keeps material < 0 and the fields of no material: zeros, tex = -1).
+struct alignas(128) ShadeHeader {
+    float m[9];        // DevGeom::m                                  q0, q1, q2.x
+    uint32_t valid;    // DevGeom::valid                              q2.y
+    int32_t material;  // DevGeom::material (sign kept)               q2.z
+    uint32_t bundle;   // DevMat::bundle, bundle_w, bundle_h          q2.w, q3.xy
+    uint32_t bundle_w, bundle_h;
+    int32_t tex[3];    // DevMat::tex                                 q3.zw, q4.x
+    float albedo[3];   // DevMat::albedo                              q4.yzw
+    float rough, metal; //                                            q5.xy
+    uint32_t pad[10];
+};
+static_assert(sizeof(ShadeHeader) == 128 && offsetof(ShadeHeader, rough) == 80, "shade header layout (load_shade_header, gi_device.h)");
 struct DevTex {
     uint32_t offset; // in footprint entries (16 B), into the texel pool
     uint32_t w, h, pad;
@@ -147,6 +163,7 @@ struct SceneView {
 
 struct GiState {
     SceneView view{};
+    const ShadeHeader* shade_heads = nullptr; // one per geometry, for gi_shade_kernel (the other kernels read view.geoms / view.mats)
     std::vector<void*> allocs;
     // host copies kept for the build
     std::vector<float> h_tris; // 12 floats per triangle
