@@ -369,6 +369,30 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
  * One-time setup: enqueues on `stream` and SYNCHRONISES it before returning.  On failure the scene keeps its previous
  * state (unbuilt, or the previous valid tree); calling it again rebuilds. */
 int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream);
+/* RTAccelerationStructureBuilder::CreateTlas with a valid updateTlas (RTAccelerationStructureBuilder.cpp:100-130): new instance
+ * transforms for n submeshes, the tree kept.  geometry_indices[k] names a geometry of neb_gi_set_scene, surfaceToWorld + 16 * k is
+ * its new matrix (layout and row-vector convention of neb_geometry_desc::surfaceToWorld).  Every transform is applied to the
+ * object-space positions of neb_gi_set_scene, never to the previous world positions: a chain of updates does not drift.
+ * What is rewritten, on the device and in place: the world-space triangles of the named submeshes (same operation order as the
+ * bake of neb_gi_set_scene, same bits), their rows of the geometry tables, the boxes of the 128-byte nodes above them (refitted
+ * bottom-up, one launch per level) and the 64-byte nodes (quantised again).  Topology, node numbering, leaf order and depth do
+ * not change; results are those of a tree built from the moved scene up to exact ties between coincident hits (only the exact
+ * triangle tests decide a hit).  A leaf none of whose triangles moved keeps its box bit for bit; a leaf holding a clipped
+ * reference of a moved triangle takes the whole triangle's bounds.  Tree quality degrades with the distance moved: DESIGN.md 3.4a.
+ * A matrix equal to the one already set moves nothing; a call that moves nothing enqueues nothing.
+ * Streams: enqueue only -- no device synchronisation, no allocation (the host waits only when it is kStageSlots = 4 updates ahead
+ * of the device).  The rewrite runs on `stream` behind every dispatch enqueued before the call on whichever stream (an event is
+ * recorded on each stream that has read the scene since the last update: those streams must still exist), and every later
+ * neb_gi_trace* / neb_pbr_direct / neb_gbuffer_raycast on another stream waits for it: two frames in flight stay correct.
+ * Sun table: treated as after a scene change.  Lit bits and occluder hints are not used from the moment of the call; the hold
+ * policy ("gi_sun_hold") decides when a table is built again, against the new scene box (none beyond +-218 units).
+ * A later neb_gi_build_bvh builds from the updated transforms.  Row-strip contexts accept the call; contexts given the same
+ * updates hold the same tree.
+ * Refusals, each leaving everything unchanged: NEB_ERR_STATE before a successful neb_gi_build_bvh; NEB_ERR_INVALID_ARG for a null
+ * pointer with n > 0, an index >= n_geoms or an index named twice; NEB_ERR_OUT_OF_RANGE when a matrix entry is not finite or the
+ * transform takes a corner of the submesh's object-space box (or a vertex) to a position that is not finite.  n == 0: NEB_OK. */
+int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, const float* surfaceToWorld /* n x 16, as neb_geometry_desc */,
+                             uint32_t n, neb_stream stream);
 int neb_gi_scene_info(const neb_ctx* ctx, uint32_t* n_triangles, uint32_t* n_nodes);
 /* Device bytes of the scene: {texture footprint tables + material bundles, triangles + shading records, BVH nodes: the
  * builder's 128-byte nodes + the 64-byte quantised nodes the rays walk}. */

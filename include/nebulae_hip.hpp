@@ -125,6 +125,11 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_build_bvh(m_svgf.Context(), commandList), "neb_gi_build_bvh");
         }
+        // RTAccelerationStructureBuilder::CreateTlas(commandList, instances, updateTlas) with a valid updateTlas: new transforms, the tree kept
+        void UpdateInstanceTransforms(const uint32_t* geometryIndices, const float* surfaceToWorld, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_update_transforms(m_svgf.Context(), geometryIndices, surfaceToWorld, n, commandList), "neb_gi_update_transforms");
+        }
         void SubmitCommandsGIPathtrace(const neb_gi_constants& globalConstants, neb_stream commandList)
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_trace(m_svgf.Context(), &globalConstants, commandList), "neb_gi_trace");

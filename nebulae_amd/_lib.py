@@ -97,6 +97,7 @@ def _gi_sigs():
         "neb_gi_set_scene": (C.c_int, [C.c_void_p, C.POINTER(S.GeometryDesc), C.c_uint32, C.POINTER(S.MaterialDesc), C.c_uint32,
                                        C.POINTER(S.TextureDesc), C.c_uint32]),
         "neb_gi_build_bvh": (C.c_int, [C.c_void_p, C.c_void_p]),
+        "neb_gi_update_transforms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
         "neb_gi_scene_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "neb_gi_bvh_depth": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
         "neb_gi_build_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

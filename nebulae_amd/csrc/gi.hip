@@ -998,6 +998,7 @@ static int gi_dispatch(neb_ctx* ctx, const neb_gi_constants* c, uint32_t row0, u
     // unsorted (the sort's six launches cost more than coherence is worth to the ~14 % that are left).
     // the sun-visibility table: brought up to date with this frame's sun (a rebuild only when the sun or the scene changed -- and
     // then only once the new sun has held for a second frame: a sun that is being dragged is traced the plain way meanwhile)
+    GI_HIP(ctx, gi_scene_reader(g, (hipStream_t)stream)); // triangles, nodes and tables may be rewritten in place (neb_gi_update_transforms)
     if (phase != 1) { // (the flags are read by the shade pass)
         GI_HIP(ctx, gi_sun_table_update(g, *c, (hipStream_t)stream));
         GI_HIP(ctx, gi_sun_table_order(g, (hipStream_t)stream)); // a rewrite of the flags enqueued on another stream comes first
@@ -1229,6 +1230,7 @@ int neb_pbr_direct(neb_ctx* ctx, const neb_gi_constants* c, neb_stream stream)
         return gi_fail(ctx, NEB_ERR_STATE, "neb_pbr_direct: scene/BVH not ready (neb_gi_set_scene + neb_gi_build_bvh)");
     GI_GUARD(ctx);
     ScopedRange range("PBR Direct Lighting + Shadows"); // DeferredRenderer.cpp:338
+    GI_HIP(ctx, gi_scene_reader(g, (hipStream_t)stream));
     GiArgs a{};
     a.S = g->view;
     a.c = *c;
@@ -1445,6 +1447,7 @@ int neb_gbuffer_raycast(neb_ctx* ctx, const neb_camera* cam, neb_stream stream)
         return gi_fail(ctx, NEB_ERR_STATE, "neb_gbuffer_raycast: scene/BVH not ready");
     GI_GUARD(ctx);
     ScopedRange range("Deferred G-Buffers (geometry)"); // DeferredRenderer.cpp:267
+    GI_HIP(ctx, gi_scene_reader(g, (hipStream_t)stream));
     GbufArgs a;
     a.S = g->view;
     const CameraBasis b = camera_basis(*cam, ctx->W, ctx->H);

@@ -57,6 +57,14 @@ void gi_destroy(GiState* g)
     for (hipEvent_t& e : g->tail_ev)
         if (e)
             (void)hipEventDestroy(e);
+    for (hipEvent_t& e : g->stage_ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    for (hipEvent_t& e : g->reader_ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    if (g->h_stage)
+        (void)hipHostFree(g->h_stage);
     delete g;
 }
 
@@ -1144,6 +1152,37 @@ __global__ void quantise_nodes_kernel(const Bvh4Node* __restrict__ nodes, uint32
     out[i] = o;
 }
 
+hipError_t gi_quantise_nodes(const Bvh4Node* nodes, uint32_t n, Bvh4NodeQ* out, hipStream_t stream)
+{
+    if (!n)
+        return hipSuccess;
+    hipLaunchKernelGGL(quantise_nodes_kernel, dim3((n + 127) / 128), dim3(128), 0, stream, nodes, n, out);
+    return hipGetLastError();
+}
+
+// The host bake of neb_gi_set_scene again, for the geometries neb_gi_update_transforms has moved since: the next build starts from
+// the triangles the device holds.  (Positions were checked finite when the transform was accepted.)
+void gi_rebake_host(GiState* g)
+{
+    for (uint32_t gi = 0; gi < (uint32_t)g->h_geoms.size(); ++gi) {
+        GiState::HostGeom& hg = g->h_geoms[gi];
+        if (!hg.dirty)
+            continue;
+        hg.dirty = false;
+        for (uint32_t p = 0; p < hg.n_tris; ++p) {
+            float w[3][3];
+            for (int k = 0; k < 3; ++k)
+                (void)gi_bake_point(hg.m, &g->h_pos[3 * (size_t)(hg.vertexBase + g->h_indices[hg.firstIndex + 3 * p + k])], w[k]);
+            float* t = &g->h_tris[12 * (size_t)(hg.firstTri + p)];
+            for (int q = 0; q < 3; ++q) {
+                t[q] = w[0][q];
+                t[3 + q] = w[1][q] - w[0][q];
+                t[6 + q] = w[2][q] - w[0][q];
+            }
+        }
+    }
+}
+
 } // namespace neb
 
 using namespace neb;
@@ -1162,10 +1201,13 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     gi_destroy(ctx->gi);
     ctx->gi = nullptr;
     GiState* g = new GiState();
+    g->h_geoms.resize(n_geoms);
+    g->h_seen.assign(n_geoms, 0u);
+    g->n_geoms = n_geoms;
     std::vector<DevGeom> dgeoms(n_geoms);
     std::vector<DevMat> dmats(n_mats);
     std::vector<DevTex> dtexs(n_texs);
-    std::vector<uint32_t> indices;
+    std::vector<uint32_t>& indices = g->h_indices;
     std::vector<float> normals, uvs, tangents;
     uint32_t vertex_base = 0;
     float smin[3] = {3.4e38f, 3.4e38f, 3.4e38f}, smax[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
@@ -1184,6 +1226,12 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         d.vertexBase = vertex_base;
         d.valid = (s.indices && s.attributes[0] && s.attributes[1] && s.attributes[2] && s.attributes[3]) ? 1u : 0u;
         d.pad[0] = d.pad[1] = d.pad[2] = 0;
+        GiState::HostGeom& hg = g->h_geoms[gi];
+        memcpy(hg.m, m, sizeof(hg.m));
+        hg.firstIndex = d.firstIndex;
+        hg.vertexBase = vertex_base;
+        hg.firstTri = (uint32_t)(g->h_tris.size() / 12);
+        hg.firstRef = (uint32_t)g->h_ref_verts.size();
         auto rd_index = [&](uint32_t i) -> uint32_t {
             const uint8_t* p = (const uint8_t*)s.indices + (size_t)i * s.indexStride;
             if (s.indexStride == 2) {
@@ -1213,6 +1261,8 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         }
         for (uint32_t v = 0; v < s.numVertices; ++v) {
             float t[4];
+            rd_attr(0, v, t, 3);
+            g->h_pos.insert(g->h_pos.end(), t, t + 3);
             rd_attr(1, v, t, 3);
             normals.insert(normals.end(), t, t + 3);
             rd_attr(2, v, t, 2);
@@ -1223,22 +1273,41 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         vertex_base += s.numVertices;
         // bake world-space triangles: world = (p,1) * M (the correct instance transform)
         if (s.attributes[0]) {
+            hg.n_tris = ntri;
+            {   // the vertices the triangles name, each once, and their object-space box (neb_gi_update_transforms)
+                std::vector<char> named(s.numVertices, 0);
+                for (uint32_t i = 0; i < ntri * 3; ++i)
+                    named[g->h_indices[hg.firstIndex + i]] = 1;
+                for (int q = 0; q < 3; ++q)
+                    hg.obj_lo[q] = 3.4e38f, hg.obj_hi[q] = -3.4e38f;
+                for (uint32_t v = 0; v < s.numVertices; ++v)
+                    if (named[v]) {
+                        g->h_ref_verts.push_back(v);
+                        for (int q = 0; q < 3; ++q) {
+                            const float c = g->h_pos[3 * (size_t)(hg.vertexBase + v) + q];
+                            hg.obj_lo[q] = fminf(hg.obj_lo[q], c);
+                            hg.obj_hi[q] = fmaxf(hg.obj_hi[q], c);
+                        }
+                    }
+                hg.n_refs = (uint32_t)g->h_ref_verts.size() - hg.firstRef;
+                for (int q = 0; q < 3; ++q)
+                    hg.world_lo[q] = 3.4e38f, hg.world_hi[q] = -3.4e38f;
+            }
             for (uint32_t p = 0; p < ntri; ++p) {
                 float w[3][3];
                 for (int k = 0; k < 3; ++k) {
                     float a[3];
                     rd_attr(0, rd_index(3 * p + k), a, 3);
-                    w[k][0] = a[0] * m[0] + a[1] * m[4] + a[2] * m[8] + m[12];
-                    w[k][1] = a[0] * m[1] + a[1] * m[5] + a[2] * m[9] + m[13];
-                    w[k][2] = a[0] * m[2] + a[1] * m[6] + a[2] * m[10] + m[14];
+                    // (a position that is not a finite number has no place in a tree: min / max drop NaNs silently, the SAH's areas would not)
+                    if (!gi_bake_point(m, a, w[k])) {
+                        delete g;
+                        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_set_scene: a vertex position (after the instance transform) is not a finite number");
+                    }
                     for (int q = 0; q < 3; ++q) {
-                        // (a position that is not a finite number has no place in a tree: min / max drop NaNs silently, the SAH's areas would not)
-                        if (!(fabsf(w[k][q]) <= 3.0e38f)) {
-                            delete g;
-                            return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_set_scene: a vertex position (after the instance transform) is not a finite number");
-                        }
                         smin[q] = fminf(smin[q], w[k][q]);
                         smax[q] = fmaxf(smax[q], w[k][q]);
+                        hg.world_lo[q] = fminf(hg.world_lo[q], w[k][q]);
+                        hg.world_hi[q] = fmaxf(hg.world_hi[q], w[k][q]);
                     }
                 }
                 float t12[12] = {w[0][0], w[0][1], w[0][2], w[1][0] - w[0][0], w[1][1] - w[0][1], w[1][2] - w[0][2],
@@ -1382,9 +1451,31 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     if ((e = upload(g, dgeoms, &g->view.geoms)) != hipSuccess || (e = upload(g, dmats, &g->view.mats)) != hipSuccess ||
         (e = upload(g, dtexs, &g->view.texs)) != hipSuccess || (e = upload(g, indices, &g->view.indices)) != hipSuccess ||
         (e = upload(g, normals, &g->view.normals)) != hipSuccess || (e = upload(g, uvs, &g->view.uvs)) != hipSuccess ||
-        (e = upload(g, tangents, &g->view.tangents)) != hipSuccess || (e = upload(g, heads, &g->shade_heads)) != hipSuccess) {
+        (e = upload(g, tangents, &g->view.tangents)) != hipSuccess || (e = upload(g, heads, &g->shade_heads)) != hipSuccess ||
+        (e = upload(g, g->h_pos, &g->d_pos)) != hipSuccess) {
         gi_destroy(g);
         return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_scene: upload", e);
+    }
+    if (n_geoms) { // what neb_gi_update_transforms needs, so that it never allocates: the 4x4s, the stamps, the pinned argument slots
+        std::vector<float> xf((size_t)n_geoms * 16);
+        for (uint32_t gi = 0; gi < n_geoms; ++gi)
+            memcpy(&xf[16 * (size_t)gi], g->h_geoms[gi].m, 64);
+        const float* d_xf = nullptr;
+        void* stamps = nullptr;
+        void* stage = nullptr;
+        if ((e = upload(g, xf, &d_xf)) != hipSuccess || (e = hipMalloc(&stamps, (size_t)n_geoms * 4)) != hipSuccess) {
+            gi_destroy(g);
+            return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_scene: transform tables", e);
+        }
+        g->allocs.push_back(stamps);
+        g->d_xf = const_cast<float*>(d_xf);
+        g->d_geom_epoch = (uint32_t*)stamps;
+        if ((e = hipMemset(stamps, 0, (size_t)n_geoms * 4)) != hipSuccess ||
+            (e = hipHostMalloc(&stage, (size_t)GiState::kStageSlots * n_geoms * sizeof(GiState::StageEntry), hipHostMallocDefault)) != hipSuccess) {
+            gi_destroy(g);
+            return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_scene: transform tables", e);
+        }
+        g->h_stage = (GiState::StageEntry*)stage;
     }
     void* ctr = nullptr;
     if ((e = hipMalloc(&ctr, 16 * sizeof(unsigned long long))) != hipSuccess || (e = hipMemset(ctr, 0, 16 * sizeof(unsigned long long))) != hipSuccess) {
@@ -1597,6 +1688,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
     const auto t_build0 = std::chrono::steady_clock::now(); // (the build ends with a stream synchronisation: wall time = device time + launches)
+    gi_rebake_host(g);
     if (g->n_tris == 0) { // empty scene: every ray misses
         g->built = true;
         g->n_nodes = 0;
@@ -1785,6 +1877,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     // ---- collapse to BVH4, triangles into leaf order ----
     int root_code = 0, max_depth = 0;
     uint32_t n_wide = 0;
+    std::vector<uint32_t> level_first; // breadth-first: level l = nodes [level_first[l], level_first[l + 1]) (neb_gi_update_transforms refits by level)
     if (n <= (uint32_t)kMaxLeafTris) { // the whole scene is one leaf
         BUILD_HIP(hipMemcpyAsync(d_final, d_sorted, (size_t)n * 48, hipMemcpyDeviceToDevice, stream));
         root_code = ~(int)((0u << 2) | (n - 1u));
@@ -1816,6 +1909,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
         uint32_t level_start = 0, level_count = 1;
         while (level_count > 0) {
             ++max_depth;
+            level_first.push_back(level_start);
             if ((size_t)level_start + level_count > (size_t)n)
                 return bail(NEB_ERR_HIP, "neb_gi_build_bvh: wide-node bound exceeded (internal error)");
             a.level_start = level_start;
@@ -1833,9 +1927,11 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
             level_count = next;
         }
         n_wide = level_start;
+        level_first.push_back(n_wide);
     }
     Bvh4Node* d_wide = nullptr;
     Bvh4NodeQ* d_wide_q = nullptr;
+    uint32_t* d_node_epoch = nullptr;
     if (n_wide) {
         d_wide = (Bvh4Node*)dalloc((size_t)n_wide * sizeof(Bvh4Node), true);
         if (!d_wide)
@@ -1846,6 +1942,10 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
             return bail(NEB_ERR_HIP, "neb_gi_build_bvh: out of device memory");
         hipLaunchKernelGGL(quantise_nodes_kernel, dim3((n_wide + 127) / 128), dim3(128), 0, stream, d_wide, n_wide, d_wide_q);
         BUILD_HIP(hipGetLastError());
+        d_node_epoch = (uint32_t*)dalloc((size_t)n_wide * 4, true);
+        if (!d_node_epoch)
+            return bail(NEB_ERR_HIP, "neb_gi_build_bvh: out of device memory");
+        BUILD_HIP(hipMemsetAsync(d_node_epoch, 0, (size_t)n_wide * 4, stream));
     }
     {
         SceneView sv = g->view;
@@ -1866,7 +1966,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
         return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, msg);
     }
     // ---- commit: release the previous build's arrays (a rebuild), adopt the new ones ----
-    const void* old[] = {g->view.tris, g->view.shade, g->view.nodes, g->view.qnodes};
+    const void* old[] = {g->view.tris, g->view.shade, g->view.nodes, g->view.qnodes, g->d_node_epoch};
     if (g->built)
         (void)hipDeviceSynchronize(); // no launch may still be walking the tree that is about to be freed
     for (const void* o : old) {
@@ -1886,11 +1986,14 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     g->view.nodes = d_wide;
     g->view.qnodes = d_wide_q;
     g->view.n_qnodes = n_wide;
+    g->d_node_epoch = d_node_epoch;
+    g->level_first.swap(level_first);
     g->view.root = root_code;
     g->n_nodes = n_wide;
     g->bvh_depth = (uint32_t)max_depth;
     g->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
     g->sun_table_state = 0; // fresh shading records carry no sun-visibility flags yet
+    g->sun_table_stale = false;
     g->built = true; // (h_tris stays: the scene can be rebuilt)
     return NEB_OK;
 }

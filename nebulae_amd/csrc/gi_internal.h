@@ -241,9 +241,79 @@ struct GiState {
     bool tail_sorted = false;         // the decision for this table
     hipEvent_t tail_ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float tail_us[2] = {0.f, 0.f};    // the two times of the last measurement {lists, sorted pass}
+    bool sun_table_stale = false;     // the flags in the records belong to a scene that has moved since (neb_gi_update_transforms): no sun brings them back
+    // ---- moving submeshes: neb_gi_update_transforms (gi_refit.hip) ----
+    // Host copies of what a transform is applied to (the build bakes h_tris from them again when a geometry is dirty) ...
+    struct HostGeom {
+        uint32_t firstIndex = 0, vertexBase = 0, n_tris = 0; // into h_indices / h_pos; triangles of the geometry
+        uint32_t firstTri = 0;                               // its first triangle in h_tris (geometries follow one another)
+        uint32_t firstRef = 0, n_refs = 0;                   // its referenced vertices (each once), into h_ref_verts
+        float obj_lo[3] = {0, 0, 0}, obj_hi[3] = {0, 0, 0};  // object-space box of the referenced vertices
+        float world_lo[3] = {0, 0, 0}, world_hi[3] = {0, 0, 0}; // exact world-space box under the current transform
+        float m[16] = {};                                    // surfaceToWorld as last set
+        bool dirty = false;                                  // h_tris still holds the bake of an earlier transform
+    };
+    std::vector<HostGeom> h_geoms;
+    std::vector<uint32_t> h_indices, h_ref_verts;
+    std::vector<float> h_pos; // 3 per vertex, object space
+    std::vector<uint32_t> h_seen; // per geometry: the update call that named it last (duplicate check without clearing)
+    uint32_t seen_stamp = 0;
+    // ... and on the device: the object-space positions, the 4x4 of every geometry, and two stamp arrays -- geom_epoch[g] == epoch:
+    // geometry g was moved by the update in progress; node_epoch[i] == epoch: a child box of node i was rewritten by it.
+    const float* d_pos = nullptr;
+    float* d_xf = nullptr;
+    uint32_t* d_geom_epoch = nullptr;
+    uint32_t* d_node_epoch = nullptr; // (belongs to the tree: replaced by every build)
+    uint32_t epoch = 0;               // updates enqueued so far
+    std::vector<uint32_t> level_first; // breadth-first nodes: level l = [level_first[l], level_first[l + 1])
+    // The arguments of an update wait in pinned host memory until its first kernel has read them: kStageSlots updates may be
+    // enqueued before the host has to wait for the oldest one's kernel.
+    static constexpr int kStageSlots = 4;
+    struct StageEntry { uint32_t geom, pad[3]; float m[16]; };
+    StageEntry* h_stage = nullptr;    // [kStageSlots][n_geoms]
+    hipEvent_t stage_ev[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
+    bool stage_used[kStageSlots] = {false, false, false, false};
+    // Streams that have read triangles / nodes / geometry tables since the last update: an update on another stream orders itself
+    // behind them (an event recorded on each, waited for on its own stream).  More than kReaderStreams: it waits for the device.
+    static constexpr int kReaderStreams = 4;
+    hipStream_t reader_streams[kReaderStreams] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t reader_ev[kReaderStreams] = {nullptr, nullptr, nullptr, nullptr};
+    int n_reader_streams = 0;
+    bool reader_overflow = false;
+    uint32_t n_geoms = 0;
 };
 hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_t stream);
 hipError_t gi_sun_table_order(GiState* g, hipStream_t stream);
+hipError_t mark_rewrite(GiState* g, hipStream_t stream);
+hipError_t gi_quantise_nodes(const Bvh4Node* nodes, uint32_t n, Bvh4NodeQ* out, hipStream_t stream);
+void gi_rebake_host(GiState* g);
+
+// Every entry point that reads triangles, nodes or the geometry tables on `stream` starts here: a rewrite enqueued on another stream
+// (sun table, neb_gi_update_transforms) comes first, and the stream is remembered for the next update to wait for.
+inline hipError_t gi_scene_reader(GiState* g, hipStream_t stream)
+{
+    bool known = false;
+    for (int k = 0; k < g->n_reader_streams; ++k)
+        known = known || g->reader_streams[k] == stream;
+    if (!known) {
+        if (g->n_reader_streams < GiState::kReaderStreams)
+            g->reader_streams[g->n_reader_streams++] = stream;
+        else
+            g->reader_overflow = true;
+    }
+    return gi_sun_table_order(g, stream);
+}
+
+// world = (p, 1) * M, row-vector convention: THE operation order of the bake -- products and sums rounded one by one, left to right.
+// rebake_kernel (gi_refit.hip) repeats it with __fmul_rn / __fadd_rn and must give the same bits.  false: not a finite position.
+inline bool gi_bake_point(const float* m, const float a[3], float w[3])
+{
+#pragma clang fp contract(off)
+    w[0] = a[0] * m[0] + a[1] * m[4] + a[2] * m[8] + m[12];
+    w[1] = a[0] * m[1] + a[1] * m[5] + a[2] * m[9] + m[13];
+    w[2] = a[0] * m[2] + a[1] * m[6] + a[2] * m[10] + m[14];
+    return fabsf(w[0]) <= 3.0e38f && fabsf(w[1]) <= 3.0e38f && fabsf(w[2]) <= 3.0e38f;
+}
 
 void gi_on_resize(GiState* g);
 void gi_destroy(GiState* g);

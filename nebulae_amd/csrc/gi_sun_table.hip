@@ -487,7 +487,7 @@ __global__ void sun_table_clear_kernel(float4* shade, uint32_t n)
 }
 
 // behind a launch that rewrites the flags: dispatches on other streams order themselves after it (gi_sun_table_order)
-static hipError_t mark_rewrite(GiState* g, hipStream_t stream)
+hipError_t mark_rewrite(GiState* g, hipStream_t stream)
 {
     if (!g->sun_table_event)
         if (hipError_t e = hipEventCreateWithFlags(&g->sun_table_event, hipEventDisableTiming); e != hipSuccess)
@@ -531,10 +531,11 @@ hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_
             if (hipError_t em = mark_rewrite(g, stream); em != hipSuccess)
                 return em;
             g->sun_table_state = 0;
+            g->sun_table_stale = false;
         }
         return hipGetLastError();
     }
-    if (g->sun_table_state != 0 && !memcmp(key, g->sun_table_key, sizeof(key))) {
+    if (g->sun_table_state != 0 && !g->sun_table_stale && !memcmp(key, g->sun_table_key, sizeof(key))) {
         g->sun_table_state = 1; // (back to the sun the flags were built for)
         g->sun_table_age++;
         return hipSuccess;
@@ -577,6 +578,7 @@ hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_
                 return em;
         }
         g->sun_table_state = 0;
+        g->sun_table_stale = false;
         return hipGetLastError();
     }
     if (!g->d_sun_counts) {
@@ -630,6 +632,7 @@ hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_
         return em;
     memcpy(g->sun_table_key, key, sizeof(key));
     g->sun_table_state = 1;
+    g->sun_table_stale = false;
     g->sun_table_age = 0;
     g->sun_seen = 0;
     g->sun_table_builds++;

@@ -89,6 +89,27 @@ class DeferredRenderer:
         self._check(self._lib.neb_gi_build_bvh(self._ctx, C.c_void_p(stream)), "neb_gi_build_bvh")
         self._scene = scene
 
+    # ---- RTAccelerationStructureBuilder::CreateTlas with a valid updateTlas (RTAccelerationStructureBuilder.cpp:100-130) ----
+    def update_transforms(self, indices, matrices, stream=None):
+        """Move submeshes: geometry indices[k] gets the 4x4 surfaceToWorld matrices[k] (row-vector convention, as Scene.add_geometry's
+        M); the tree is refitted in place (neb_gi_update_transforms).  The renderer's scene object takes the same matrices, so its
+        G-buffer and oracle helpers see the scene the device holds -- a Scene shared with another renderer moves there too."""
+        if self._scene is None:
+            raise NebError("update_transforms: no scene (init_pathtracer_scene first)")
+        idx = np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))
+        if idx.size and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise NebError("update_transforms: geometry index out of range")
+        idx = idx.astype(np.uint32)
+        mats = np.ascontiguousarray(np.asarray(matrices, np.float32).reshape(-1, 4, 4))
+        if mats.shape[0] != idx.size:
+            raise NebError(f"update_transforms: {idx.size} indices but {mats.shape[0]} matrices")
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        rc = self._lib.neb_gi_update_transforms(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                mats.ctypes.data_as(C.POINTER(C.c_float)), idx.size, st)
+        self._check(rc, "neb_gi_update_transforms")
+        for k, gi in enumerate(idx):
+            self._scene.geometries[int(gi)]["M"] = mats[k].copy()
+
     def scene_info(self):
         t, n = C.c_uint32(), C.c_uint32()
         self._check(self._lib.neb_gi_scene_info(self._ctx, C.byref(t), C.byref(n)), "neb_gi_scene_info")
