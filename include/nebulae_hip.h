@@ -60,6 +60,11 @@ typedef enum neb_plane {
                                       neb_get_plane / uploads / downloads of it return NEB_ERR_STATE otherwise. */
     NEB_PLANE_COUNT = 12
 } neb_plane;
+/* R32_UINT 4 B/px, 2 slots: the geometry index (submesh) of each pixel's primary hit, 0xFFFFFFFF where depth holds no surface.  Not one
+ * of the reference-format planes, not counted by NEB_PLANE_COUNT: exists only while option "svgf_motion" is 1 (allocated zeroed, freed
+ * when the option is turned off, re-created by neb_resize); neb_get_plane / uploads / downloads of it return NEB_ERR_STATE otherwise.
+ * neb_gbuffer_raycast writes slot cur; a host with its own raster G-buffer uploads or writes it. */
+#define NEB_PLANE_SUBMESH_ID 12
 
 /* Slot selectors for the 2-slot (ping-pong) planes. */
 #define NEB_SLOT_CURRENT (-1) /* GetCurrentResourceIndex(), SVGFDenoiser.h:24 */
@@ -140,7 +145,12 @@ int neb_svgf_get_params(const neb_ctx* ctx, neb_svgf_params* out);
  *   "svgf_fuse":        0 (default) / 1 (opt-in), see neb_svgf_atrous;   "svgf_profile": 0 (default) / 1 / 2, see neb_svgf_level_times;
  *   "svgf_reproject":   0 (default) / 1 (opt-in): the temporal pass reprojects the history through the two frames' cameras, see
  *                       neb_svgf_set_camera.  NEB_ERR_STATE on a row-strip context.  1 allocates the (zeroed) history-length plane,
- *                       0 frees it: a context switched on and off again computes what a context that never had it on computes. */
+ *                       0 frees it: a context switched on and off again computes what a context that never had it on computes.
+ *                       NEB_ERR_STATE for 0 while "svgf_motion" is 1 (turn that off first);
+ *   "svgf_motion":      0 (default) / 1 (opt-in, needs "svgf_reproject" = 1, else NEB_ERR_STATE): the reprojecting temporal pass follows
+ *                       submeshes moved by neb_gi_update_transforms, see neb_svgf_snapshot_transforms.  1 allocates the (zeroed) submesh-id
+ *                       plane and, with a scene set, two per-slot transform tables and the delta table; 0 frees them.  With 0 every
+ *                       kernel, plane and call behaves as if the option did not exist. */
 int neb_set_option(neb_ctx* ctx, const char* key, int value);
 
 /* ---- resource sharing: the ~25 getters of SVGFDenoiser.h:24-70 collapse into one call.
@@ -219,6 +229,31 @@ int neb_svgf_level_times(neb_ctx* ctx, float* out_us, uint32_t capacity, uint32_
  * after neb_begin_frame, with slot NEB_SLOT_CURRENT.  neb_resize forgets both cameras.  NEB_ERR_INVALID_ARG for a bad slot or camera. */
 struct neb_camera;
 int neb_svgf_set_camera(neb_ctx* ctx, int slot, const struct neb_camera* cam);
+/* ---- Moving submeshes under reprojection (option "svgf_motion" = 1 on top of "svgf_reproject" = 1).  Submeshes move as
+ * whole units (neb_gi_update_transforms), so a pixel's motion is: which submesh it shows (NEB_PLANE_SUBMESH_ID) and one small matrix per
+ * submesh and frame pair.  The library keeps, per G-buffer slot, a snapshot of the surfaceToWorld table the slot was rendered with; in front
+ * of every temporal pass one small kernel turns the two snapshots into a delta entry per geometry (skipped when no update was enqueued
+ * between them): flag 0 = the two matrices are equal bit for bit, 1 = moved, 2 = a matrix is singular or not finite; D = M_cur^-1 . M_hist
+ * (row-vector convention: a world point of the current frame -> where that surface point was in the history frame), K = the inverse transpose
+ * of D's 3x3 (carries a normal the same way).  The rule above then changes in two places, for every temporal pass while the option is 1:
+ *   mapping:  g = submesh_id[cur][p].  Entry of g has flag 1: P_h = (P, 1) . D_g, N_h = normalise(N_p . K_g); flag 0, no entry (g >= the
+ *             scene's geometry count, a slot without a snapshot, no scene) or no id: P_h = P, N_h = N_p exactly; flag 2: p takes no history.
+ *             P_h is projected with the camera of hist as P was; the plane tolerance uses ITS linear depth.
+ *   validity: the four tests above with P_h, N_h in place of P, N_p -- and one more: submesh_id[hist][tap] == g.  It applies to every
+ *             pixel, moved or not: a wall uncovered by an object that moved away does not inherit the object's radiance, nor the object the wall's.
+ * Blend, history length and variance are unchanged.
+ *
+ * neb_svgf_snapshot_transforms copies the scene's current transform table into slot `slot`'s snapshot (0, 1, NEB_SLOT_CURRENT or
+ * NEB_SLOT_HISTORY), device to device, enqueue-only on `stream`, ordered behind an update enqueued on another stream and in front of a later one.
+ * neb_gbuffer_raycast does it for cur by itself; a host with its own raster G-buffer calls it once per frame next to neb_svgf_set_camera
+ * (and fills the submesh-id plane of cur).  neb_gi_set_scene and neb_resize forget both snapshots; a context without a scene keeps none (NEB_OK:
+ * nothing moved).  NEB_ERR_INVALID_ARG for a bad slot, NEB_ERR_STATE while "svgf_motion" is 0. */
+int neb_svgf_snapshot_transforms(neb_ctx* ctx, int slot, neb_stream stream);
+/* Test / tooling aid: runs the delta kernel on the snapshots of (cur, hist) whether or not anything moved and downloads its table:
+ * per geometry 32 floats = {flag as uint32 bits, 0, 0, 0 | D, 4 rows x 3 | K, 3 rows x 3 | zeros}; *n_out = entries written (the scene's
+ * geometry count, which `capacity` must reach).  Synchronises `stream`.  host == NULL: the launch alone, enqueue-only (for timing it).
+ * NEB_ERR_STATE without the option, a scene and both snapshots. */
+int neb_svgf_debug_delta_table(neb_ctx* ctx, float* host, uint32_t capacity, uint32_t* n_out, neb_stream stream);
 /* Row-range forms for multi-GPU row strips (no reference counterpart):
  * image rows [row0,row1) must be resident, and for the a-trous level so must every
  * (globally clamped) tap row.  `level` picks step = 1 << level and the source/destination

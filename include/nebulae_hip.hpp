@@ -87,6 +87,19 @@ namespace Neb
         {
             ThrowIfFailed(m_ctx, neb_svgf_set_camera(m_ctx, slot, &camera), "neb_svgf_set_camera");
         }
+        // Option "svgf_motion" = 1: the snapshot of the scene's transforms the slot's G-buffer was rendered with (NEB_SLOT_CURRENT once per
+        // frame next to SetCamera, for a host with its own raster G-buffer -- see neb_svgf_snapshot_transforms), and the submesh-id plane
+        // such a host fills (NEB_PLANE_SUBMESH_ID lies behind the neb_plane enum, hence an accessor of its own)
+        void SnapshotTransforms(int slot, neb_stream commandList)
+        {
+            ThrowIfFailed(m_ctx, neb_svgf_snapshot_transforms(m_ctx, slot, commandList), "neb_svgf_snapshot_transforms");
+        }
+        void* GetSubmeshIdPlane(int slot = NEB_SLOT_CURRENT, size_t* pitchBytes = nullptr, uint32_t* rows = nullptr)
+        {
+            void* p = nullptr;
+            ThrowIfFailed(m_ctx, neb_get_plane(m_ctx, NEB_PLANE_SUBMESH_ID, slot, &p, pitchBytes, rows), "neb_get_plane");
+            return p;
+        }
         // Durations (us) of the kernels of the last SubmitATrousComputeWavelet chain, after SetOption("svgf_profile", 1); returns how many
         uint32_t LevelTimes(float* outMicroseconds, uint32_t capacity)
         {

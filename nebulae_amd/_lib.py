@@ -12,6 +12,7 @@ NEB_OK = 0
 PLANE_RADIANCE, PLANE_NORMAL, PLANE_DEPTH, PLANE_MOMENTS, PLANE_VARIANCE, PLANE_SCRATCH = 0, 1, 2, 3, 4, 5
 PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY = 6, 7, 8, 9, 10
 PLANE_HISTORY_LENGTH = 11  # only while option svgf_reproject is 1
+PLANE_SUBMESH_ID = 12  # only while option svgf_motion is 1 (NEB_PLANE_SUBMESH_ID: behind the enum, not counted by NEB_PLANE_COUNT)
 SLOT_CURRENT, SLOT_HISTORY = -1, -2
 
 
@@ -59,6 +60,8 @@ _SIGS = {
     "neb_download_rows": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "neb_stream_synchronize": (C.c_int, [C.c_void_p, C.c_void_p]),
     "neb_svgf_reset_history": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "neb_svgf_snapshot_transforms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "neb_svgf_debug_delta_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
     "neb_svgf_level_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]),
     "neb_svgf_temporal": (C.c_int, [C.c_void_p, C.c_void_p]),
     "neb_svgf_atrous": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -7,9 +7,10 @@
 #include <new>
 
 #include "neb_internal.h"
+#include "svgf_reproject.h"
 
 namespace neb {
-const PlaneInfo kPlaneInfo[NEB_PLANE_COUNT] = {
+const PlaneInfo kPlaneInfo[kPlaneSlots] = {
     {16, 2}, // RADIANCE     R32G32B32A32_FLOAT
     {8, 2},  // NORMAL       R16G16B16A16_FLOAT
     {4, 2},  // DEPTH        R24G8
@@ -22,6 +23,7 @@ const PlaneInfo kPlaneInfo[NEB_PLANE_COUNT] = {
     {4, 1},  // LDR          R8G8B8A8_UNORM
     {16, 1}, // GEOMETRY     R32G32B32A32_FLOAT (decoded shading normal + depth of the current frame)
     {1, 2},  // HISTORY_LENGTH R8_UINT (only while option svgf_reproject is 1: alloc_history_length)
+    {4, 2},  // SUBMESH_ID   R32_UINT (NEB_PLANE_SUBMESH_ID, behind the enum; only while option svgf_motion is 1: alloc_option_plane)
 };
 } // namespace neb
 
@@ -94,7 +96,7 @@ static int fail(neb_ctx* ctx, int code, const char* what, hipError_t e = hipSucc
 
 static void free_planes(neb_ctx* ctx)
 {
-    for (int p = 0; p < NEB_PLANE_COUNT; ++p)
+    for (int p = 0; p < kPlaneSlots; ++p)
         for (int s = 0; s < 2; ++s)
             if (ctx->planes[p][s]) {
                 (void)hipFree(ctx->planes[p][s]);
@@ -107,8 +109,8 @@ static int alloc_planes(neb_ctx* ctx)
     // InitSVGFResources (SVGFDenoiser.cpp:283-359).  The reference never clears radiance/moments
     // (SURVEY.md quirk 8); this build defines zero-initialised planes.
     const size_t npx = (size_t)ctx->W * (ctx->row_end - ctx->row_begin);
-    for (int p = 0; p < NEB_PLANE_COUNT; ++p)
-        for (uint32_t s = 0; p != NEB_PLANE_HISTORY_LENGTH && s < kPlaneInfo[p].slots; ++s) {
+    for (int p = 0; p < NEB_PLANE_COUNT; ++p) // (not NEB_PLANE_SUBMESH_ID, which lies behind the enum)
+        for (uint32_t s = 0; p != NEB_PLANE_HISTORY_LENGTH && s < kPlaneInfo[p].slots; ++s) { // (the option planes: alloc_option_plane)
             const size_t bytes = npx * kPlaneInfo[p].bytes_per_px;
             NEB_HIP(ctx, hipMalloc(&ctx->planes[p][s], bytes));
             NEB_HIP(ctx, hipMemset(ctx->planes[p][s], 0, bytes));
@@ -117,27 +119,30 @@ static int alloc_planes(neb_ctx* ctx)
     return NEB_OK;
 }
 
-// option svgf_reproject: the history-length plane exists only while it is on (zeroed: no pixel has history yet)
-static void free_history_length(neb_ctx* ctx)
+// The two planes that exist only while their option is on, both slots zeroed: history length (svgf_reproject: no pixel has history
+// yet) and submesh id (svgf_motion).
+static void free_option_plane(neb_ctx* ctx, int plane)
 {
     for (int s = 0; s < 2; ++s)
-        if (ctx->planes[NEB_PLANE_HISTORY_LENGTH][s]) {
-            (void)hipFree(ctx->planes[NEB_PLANE_HISTORY_LENGTH][s]);
-            ctx->planes[NEB_PLANE_HISTORY_LENGTH][s] = nullptr;
+        if (ctx->planes[plane][s]) {
+            (void)hipFree(ctx->planes[plane][s]);
+            ctx->planes[plane][s] = nullptr;
         }
 }
 
-static int alloc_history_length(neb_ctx* ctx)
+static int alloc_option_plane(neb_ctx* ctx, int plane)
 {
-    const size_t bytes = (size_t)ctx->W * (ctx->row_end - ctx->row_begin);
+    const size_t bytes = (size_t)ctx->W * (ctx->row_end - ctx->row_begin) * kPlaneInfo[plane].bytes_per_px;
     for (int s = 0; s < 2; ++s) {
-        if (!ctx->planes[NEB_PLANE_HISTORY_LENGTH][s])
-            NEB_HIP(ctx, hipMalloc(&ctx->planes[NEB_PLANE_HISTORY_LENGTH][s], bytes));
-        NEB_HIP(ctx, hipMemset(ctx->planes[NEB_PLANE_HISTORY_LENGTH][s], 0, bytes));
+        if (!ctx->planes[plane][s])
+            NEB_HIP(ctx, hipMalloc(&ctx->planes[plane][s], bytes));
+        NEB_HIP(ctx, hipMemset(ctx->planes[plane][s], 0, bytes));
     }
     NEB_HIP(ctx, hipDeviceSynchronize());
     return NEB_OK;
 }
+static void free_history_length(neb_ctx* ctx) { free_option_plane(ctx, NEB_PLANE_HISTORY_LENGTH); }
+static int alloc_history_length(neb_ctx* ctx) { return alloc_option_plane(ctx, NEB_PLANE_HISTORY_LENGTH); }
 
 extern "C" {
 
@@ -208,9 +213,13 @@ int neb_resize(neb_ctx* ctx, uint32_t width, uint32_t height)
     ctx->row_begin = 0;
     ctx->row_end = height;
     ctx->has_cam[0] = ctx->has_cam[1] = false; // (the cameras belonged to the old planes)
+    ctx->has_snap[0] = ctx->has_snap[1] = false; // (... and so did the transform snapshots)
     if (int rc = alloc_planes(ctx))
         return rc;
-    return ctx->reproject ? alloc_history_length(ctx) : NEB_OK;
+    if (ctx->reproject)
+        if (int rc = alloc_history_length(ctx))
+            return rc;
+    return ctx->motion ? alloc_option_plane(ctx, NEB_PLANE_SUBMESH_ID) : NEB_OK;
 }
 
 int neb_destroy(neb_ctx* ctx)
@@ -227,6 +236,7 @@ int neb_destroy(neb_ctx* ctx)
             (void)hipEventDestroy(e);
     if (ctx->strip.xstream)
         (void)hipStreamDestroy(ctx->strip.xstream);
+    gi_motion_tables_free(ctx);
     gi_destroy(ctx->gi);
     delete ctx;
     return NEB_OK;
@@ -328,6 +338,8 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
             return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_reproject needs a whole-frame context (row strips are not supported)");
         if (value == ctx->reproject)
             return NEB_OK;
+        if (!value && ctx->motion)
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_reproject cannot be turned off while svgf_motion is 1 (turn svgf_motion off first)");
         NEB_GUARD(ctx);
         if (value) {
             if (int rc = alloc_history_length(ctx)) {
@@ -339,6 +351,31 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
             free_history_length(ctx);
         }
         ctx->reproject = value;
+        return NEB_OK;
+    }
+    if (!strcmp(key, "svgf_motion")) {
+        if (value < 0 || value > 1)
+            return fail(ctx, NEB_ERR_INVALID_ARG, "neb_set_option: svgf_motion must be 0 or 1");
+        if (value && !ctx->reproject)
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_motion needs svgf_reproject = 1");
+        if (value == ctx->motion)
+            return NEB_OK;
+        NEB_GUARD(ctx);
+        if (value) {
+            int rc = alloc_option_plane(ctx, NEB_PLANE_SUBMESH_ID);
+            if (rc == NEB_OK)
+                rc = gi_motion_tables_alloc(ctx);
+            if (rc != NEB_OK) {
+                free_option_plane(ctx, NEB_PLANE_SUBMESH_ID);
+                gi_motion_tables_free(ctx);
+                return rc;
+            }
+        } else {
+            NEB_HIP(ctx, hipDeviceSynchronize()); // (work already enqueued may still read the plane and the tables)
+            free_option_plane(ctx, NEB_PLANE_SUBMESH_ID);
+            gi_motion_tables_free(ctx);
+        }
+        ctx->motion = value;
         return NEB_OK;
     }
     if (!strcmp(key, "gi_sort_rays")) {
@@ -386,7 +423,7 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
 
 static int resolve_slot(const neb_ctx* ctx, int plane, int slot)
 {
-    if (plane < 0 || plane >= NEB_PLANE_COUNT)
+    if (plane < 0 || plane >= kPlaneSlots)
         return -1;
     if (kPlaneInfo[plane].slots == 1)
         return (slot == 0 || slot == NEB_SLOT_CURRENT) ? 0 : -1;
@@ -405,7 +442,8 @@ int neb_get_plane(neb_ctx* ctx, int plane, int slot, void** dptr, size_t* pitch_
     if (s < 0)
         return fail(ctx, NEB_ERR_INVALID_ARG, "neb_get_plane: bad plane/slot");
     if (!ctx->planes[plane][s])
-        return fail(ctx, NEB_ERR_STATE, "neb_get_plane: the history-length plane exists only while option svgf_reproject is 1");
+        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_SUBMESH_ID ? "neb_get_plane: the submesh-id plane exists only while option svgf_motion is 1"
+                                                                      : "neb_get_plane: the history-length plane exists only while option svgf_reproject is 1");
     if (int rc = svgf_flush_pending(ctx))
         return rc;
     if (plane == NEB_PLANE_NORMAL || plane == NEB_PLANE_DEPTH)
@@ -427,7 +465,8 @@ static int copy_rows(neb_ctx* ctx, int plane, int slot, uint32_t row0, uint32_t 
     if (s < 0)
         return fail(ctx, NEB_ERR_INVALID_ARG, "copy rows: bad plane/slot");
     if (!ctx->planes[plane][s])
-        return fail(ctx, NEB_ERR_STATE, "copy rows: the history-length plane exists only while option svgf_reproject is 1");
+        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_SUBMESH_ID ? "copy rows: the submesh-id plane exists only while option svgf_motion is 1"
+                                                                      : "copy rows: the history-length plane exists only while option svgf_reproject is 1");
     if (row0 < ctx->row_begin || row0 + nrows > ctx->row_end)
         return fail(ctx, NEB_ERR_OUT_OF_RANGE, "copy rows: rows not resident in this context");
     if (int rc = svgf_flush_pending(ctx))
@@ -590,6 +629,36 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
             return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal: the history-length plane is missing (a failed resize?)");
         const CameraBasis bc = camera_basis(ctx->cams[c], ctx->W, ctx->H);
         const CameraBasis bh = ctx->has_cam[h] ? camera_basis(ctx->cams[h], ctx->W, ctx->H) : bc;
+        if (ctx->motion) {
+            if (!ctx->planes[NEB_PLANE_SUBMESH_ID][0] || !ctx->planes[NEB_PLANE_SUBMESH_ID][1])
+                return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal: the submesh-id plane is missing (a failed resize?)");
+            ReprojMotion mo;
+            mo.id_cur = (const uint32_t*)ctx->planes[NEB_PLANE_SUBMESH_ID][c];
+            mo.id_hist = (const uint32_t*)ctx->planes[NEB_PLANE_SUBMESH_ID][h];
+            mo.delta = ctx->motion_delta;
+            mo.n_delta = 0;
+            // a slot without a snapshot, no scene, or no update enqueued between the two snapshots: nothing moved, no delta launch
+            if (ctx->motion_delta && ctx->has_snap[c] && ctx->has_snap[h] && ctx->snap_epoch[c] != ctx->snap_epoch[h]) {
+                hipError_t de = launch_reproj_delta(ctx->xf_snap[c], ctx->xf_snap[h], ctx->motion_delta, ctx->motion_geoms, (hipStream_t)stream);
+                if (de != hipSuccess)
+                    return fail(ctx, NEB_ERR_HIP, "reproj_delta launch", de);
+                mo.n_delta = ctx->motion_geoms;
+            }
+            hipError_t e = launch_temporal_reproject_motion(make_launch(ctx, row0, row1), bc, ctx->has_cam[h] ? &bh : nullptr,
+                                                            (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
+                                                            (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c], (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][h],
+                                                            (const uint2*)ctx->planes[NEB_PLANE_NORMAL][c], (const uint2*)ctx->planes[NEB_PLANE_NORMAL][h],
+                                                            (const uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][h], (uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][c],
+                                                            (uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
+                                                            (const uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][h],
+                                                            (uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][c],
+                                                            fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, mo, (hipStream_t)stream);
+            if (e != hipSuccess)
+                return fail(ctx, NEB_ERR_HIP, "svgf_temporal_reproject (motion) launch", e);
+            if (fused_geometry)
+                geometry_mark(ctx, row0, row1);
+            return NEB_OK;
+        }
         hipError_t e = launch_temporal_reproject(make_launch(ctx, row0, row1), bc, ctx->has_cam[h] ? &bh : nullptr,
                                                  (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
                                                  (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c], (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][h],
@@ -791,6 +860,45 @@ int neb_svgf_set_camera(neb_ctx* ctx, int slot, const neb_camera* cam)
         return fail(ctx, NEB_ERR_INVALID_ARG, "neb_svgf_set_camera: need 0 < vfov_deg < 180 and 0 < znear < zfar");
     ctx->cams[s] = *cam;
     ctx->has_cam[s] = true;
+    return NEB_OK;
+}
+
+int neb_svgf_snapshot_transforms(neb_ctx* ctx, int slot, neb_stream stream)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    const int s = resolve_slot(ctx, NEB_PLANE_DEPTH, slot);
+    if (s < 0)
+        return fail(ctx, NEB_ERR_INVALID_ARG, "neb_svgf_snapshot_transforms: slot must be 0, 1, NEB_SLOT_CURRENT or NEB_SLOT_HISTORY");
+    if (!ctx->motion)
+        return fail(ctx, NEB_ERR_STATE, "neb_svgf_snapshot_transforms: option svgf_motion is 0");
+    if (int rc = svgf_flush_pending(ctx))
+        return rc;
+    return gi_snapshot_transforms(ctx, s, (hipStream_t)stream);
+}
+
+int neb_svgf_debug_delta_table(neb_ctx* ctx, float* host, uint32_t capacity, uint32_t* n_out, neb_stream stream)
+{
+    if (!ctx || (host && !n_out))
+        return fail(ctx, NEB_ERR_INVALID_ARG, "neb_svgf_debug_delta_table: null argument");
+    if (n_out)
+        *n_out = 0;
+    if (!ctx->motion || !ctx->motion_delta || !ctx->has_snap[0] || !ctx->has_snap[1])
+        return fail(ctx, NEB_ERR_STATE, "neb_svgf_debug_delta_table: needs option svgf_motion, a scene and a transform snapshot for both slots");
+    if (host && capacity < ctx->motion_geoms)
+        return fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_svgf_debug_delta_table: capacity below the scene's geometry count");
+    if (int rc = svgf_flush_pending(ctx))
+        return rc;
+    NEB_GUARD(ctx);
+    hipError_t e = launch_reproj_delta(ctx->xf_snap[ctx->cur], ctx->xf_snap[ctx->hist], ctx->motion_delta, ctx->motion_geoms, (hipStream_t)stream);
+    if (e != hipSuccess)
+        return fail(ctx, NEB_ERR_HIP, "reproj_delta launch", e);
+    if (!host) // (timing: the launch alone, enqueue-only)
+        return NEB_OK;
+    NEB_HIP(ctx, hipMemcpyAsync(host, ctx->motion_delta, (size_t)ctx->motion_geoms * kReprojDeltaFloat4 * sizeof(float4), hipMemcpyDeviceToHost,
+                                (hipStream_t)stream));
+    NEB_HIP(ctx, hipStreamSynchronize((hipStream_t)stream));
+    *n_out = ctx->motion_geoms;
     return NEB_OK;
 }
 

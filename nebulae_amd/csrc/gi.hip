@@ -14,6 +14,7 @@
 // go through the same traverser in any-hit mode.
 //
 #include "gi_device.h" // (turns floating-point contraction off for this file: see there)
+#include "svgf_reproject.h"
 
 namespace neb {
 
@@ -711,6 +712,7 @@ struct GbufArgs {
     uint2* normal;
     uint32_t* depth;
     uint32_t W, H, row_begin, row0, row1, tiles_x;
+    uint32_t* submesh_id; // option svgf_motion: geometry index of the primary hit (0xFFFFFFFF: no surface); null otherwise -- nothing stored
 };
 
 __global__ __launch_bounds__(64) void gbuffer_kernel(GbufArgs a)
@@ -743,9 +745,10 @@ __global__ __launch_bounds__(64) void gbuffer_kernel(GbufArgs a)
     float rm0 = 0.f, rm1 = 0.f;
     float2 egn = make_float2(0.f, 0.f), esn = make_float2(0.f, 0.f);
     uint32_t ds = 0x00ffffffu;
+    uint32_t geom = 0xFFFFFFFFu;
     if (hit) {
         const float4 ids = a.S.tris[3 * h.tri + 2];
-        const uint32_t geom = __float_as_uint(ids.y);
+        geom = __float_as_uint(ids.y);
         const DevGeom g = a.S.geoms[geom];
         const float b1 = h.u, b2 = h.v, b0 = 1.0f - (b1 + b2);
         rm0 = 1.0f; // deferred_gbuffers.hlsl:91
@@ -794,6 +797,8 @@ __global__ __launch_bounds__(64) void gbuffer_kernel(GbufArgs a)
     a.normal[i] = make_uint2(float_to_half_bits(egn.x) | (float_to_half_bits(egn.y) << 16),
                              float_to_half_bits(esn.x) | (float_to_half_bits(esn.y) << 16));
     a.depth[i] = ds;
+    if (a.submesh_id)
+        a.submesh_id[i] = geom;
 }
 
 // The reference adds the indirect term into radiance[cur] in a separate step (nrc Resolve, DeferredRenderer.cpp:586).
@@ -1474,14 +1479,64 @@ int neb_gbuffer_raycast(neb_ctx* ctx, const neb_camera* cam, neb_stream stream)
     ctx->geom_lo = ctx->geom_hi = 0; // normal[cur] / depth[cur] change: the decoded geometry plane is stale
     ctx->cams[ctx->cur] = *cam; // (what the reprojecting temporal pass maps depth[cur] back with)
     ctx->has_cam[ctx->cur] = true;
+    a.submesh_id = ctx->motion ? (uint32_t*)ctx->planes[NEB_PLANE_SUBMESH_ID][ctx->cur] : nullptr;
     hipLaunchKernelGGL(gbuffer_kernel, dim3(a.tiles_x * tiles_y), dim3(64), 0, (hipStream_t)stream, a);
     GI_HIP(ctx, hipGetLastError());
+    if (ctx->motion) // (the transforms this G-buffer was rendered with: what the temporal pass follows moved submeshes by)
+        return neb::gi_snapshot_transforms(ctx, ctx->cur, (hipStream_t)stream);
     return NEB_OK;
 }
 
 } // extern "C"
 
 namespace neb {
+// ---- option svgf_motion: which surfaceToWorld each slot's G-buffer was rendered with ----
+void gi_motion_tables_free(neb_ctx* ctx)
+{
+    for (void* p : {(void*)ctx->xf_snap[0], (void*)ctx->xf_snap[1], (void*)ctx->motion_delta})
+        if (p)
+            (void)hipFree(p);
+    ctx->xf_snap[0] = ctx->xf_snap[1] = nullptr;
+    ctx->motion_delta = nullptr;
+    ctx->motion_geoms = 0;
+    ctx->has_snap[0] = ctx->has_snap[1] = false;
+}
+
+int gi_motion_tables_alloc(neb_ctx* ctx)
+{
+    gi_motion_tables_free(ctx);
+    const GiState* g = ctx->gi;
+    if (!g || !g->n_geoms || !g->d_xf)
+        return NEB_OK; // no scene: nothing can move
+    GI_GUARD(ctx);
+    hipError_t e = hipSuccess;
+    for (int s = 0; s < 2 && e == hipSuccess; ++s)
+        e = hipMalloc(&ctx->xf_snap[s], (size_t)g->n_geoms * 64);
+    if (e == hipSuccess)
+        e = hipMalloc(&ctx->motion_delta, (size_t)g->n_geoms * kReprojDeltaFloat4 * sizeof(float4));
+    if (e != hipSuccess) {
+        gi_motion_tables_free(ctx);
+        return gi_fail(ctx, NEB_ERR_HIP, "svgf_motion: transform tables", e);
+    }
+    ctx->motion_geoms = g->n_geoms;
+    return NEB_OK;
+}
+
+int gi_snapshot_transforms(neb_ctx* ctx, int s, hipStream_t stream)
+{
+    GiState* g = ctx->gi;
+    if (!g || !ctx->xf_snap[s] || ctx->motion_geoms != g->n_geoms) {
+        ctx->has_snap[s] = false; // no scene: "did not move"
+        return NEB_OK;
+    }
+    GI_GUARD(ctx);
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // an update enqueued on another stream comes first; a later one waits for this copy
+    GI_HIP(ctx, hipMemcpyAsync(ctx->xf_snap[s], g->d_xf, (size_t)g->n_geoms * 64, hipMemcpyDeviceToDevice, stream));
+    ctx->has_snap[s] = true;
+    ctx->snap_epoch[s] = g->epoch;
+    return NEB_OK;
+}
+
 int gi_set_sort_rays(neb_ctx* ctx, int mask)
 {
     if (!ctx->gi || mask < 0 || mask > 3)

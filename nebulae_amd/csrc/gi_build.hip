@@ -1198,6 +1198,7 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_scene: null table");
     GI_GUARD(ctx);
     GI_HIP(ctx, hipDeviceSynchronize());
+    gi_motion_tables_free(ctx); // (option svgf_motion: both transform snapshots belonged to the old scene)
     gi_destroy(ctx->gi);
     ctx->gi = nullptr;
     GiState* g = new GiState();
@@ -1486,7 +1487,7 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     g->d_ray_counter = (unsigned long long*)ctr;
     g->view.n_tris = g->n_tris;
     ctx->gi = g;
-    return NEB_OK;
+    return ctx->motion ? gi_motion_tables_alloc(ctx) : NEB_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -14,7 +14,9 @@ struct PlaneInfo {
     uint32_t bytes_per_px;
     uint32_t slots;
 };
-extern const PlaneInfo kPlaneInfo[NEB_PLANE_COUNT];
+// the reference-format planes of the enum, and behind them NEB_PLANE_SUBMESH_ID (not counted by NEB_PLANE_COUNT)
+constexpr int kPlaneSlots = NEB_PLANE_COUNT + 1;
+extern const PlaneInfo kPlaneInfo[kPlaneSlots];
 
 // Every entry point that launches or copies runs on its context's device whatever device the calling thread had
 // current, and leaves the thread's current device as it found it (a host may hold strip contexts on several GPUs).
@@ -122,6 +124,21 @@ hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam
                                      const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
                                      const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s);
 
+// Option svgf_motion: the motion arm of the same kernel (svgf_temporal_reproject_kernel<true>) -- id planes of the two slots, and
+// the per-geometry delta table launch_reproj_delta wrote in front of it (n_delta = 0: nothing moved between the two snapshots).
+struct ReprojMotion {
+    const uint32_t* id_cur;
+    const uint32_t* id_hist;
+    const float4* delta; // n_delta entries of kReprojDeltaFloat4 float4 (svgf_reproject.h)
+    uint32_t n_delta;
+};
+hipError_t launch_temporal_reproject_motion(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
+                                            const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
+                                            const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
+                                            const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion& motion, hipStream_t s);
+// one lane per geometry: the two slots' 4x4 tables (n x 16 floats, row-vector convention) -> n delta entries
+hipError_t launch_reproj_delta(const float* xf_cur, const float* xf_hist, float4* delta, uint32_t n, hipStream_t s);
+
 // decodes depth / normal rows [row0, row1) (all W columns) into the geometry plane
 hipError_t launch_decode_geometry(uint32_t W, uint32_t row_begin, uint32_t row0, uint32_t row1, const uint32_t* depth, const uint2* normal,
                                   float4* geometry, hipStream_t s);
@@ -149,6 +166,10 @@ int gi_set_exact_shade(neb_ctx* ctx, int on);
 int gi_set_sun_table(neb_ctx* ctx, int on);
 int gi_set_sun_hints(neb_ctx* ctx, int n);
 int gi_set_sun_hold(neb_ctx* ctx, int n);
+// option svgf_motion (gi.hip): the two per-slot transform tables and the delta table exist while the option is on and a scene is set
+int gi_motion_tables_alloc(neb_ctx* ctx); // NEB_OK also without a scene (nothing to allocate); forgets both snapshots
+void gi_motion_tables_free(neb_ctx* ctx);
+int gi_snapshot_transforms(neb_ctx* ctx, int s, hipStream_t stream); // s = 0 / 1, resolved
 
 } // namespace neb
 
@@ -156,7 +177,7 @@ struct neb_ctx {
     int device = 0;
     int num_cus = 256; // hipDeviceProp_t::multiProcessorCount (persistent-grid sizing)
     uint32_t W = 0, H = 0, row_begin = 0, row_end = 0, levels = 4;
-    void* planes[NEB_PLANE_COUNT][2] = {};
+    void* planes[neb::kPlaneSlots][2] = {};
     int cur = 0, hist = 1;
     uint32_t geom_lo = 0, geom_hi = 0; // image rows [geom_lo, geom_hi) of the geometry plane hold this frame's decoded normal / depth
     neb_svgf_params params{};
@@ -170,6 +191,12 @@ struct neb_ctx {
     int reproject = 0;                 // option svgf_reproject: the temporal pass reprojects (planes[NEB_PLANE_HISTORY_LENGTH] exist only then)
     neb_camera cams[2] = {};           // neb_svgf_set_camera / neb_gbuffer_raycast: the camera each slot's depth / normal planes were rendered with
     bool has_cam[2] = {false, false};
+    int motion = 0;                    // option svgf_motion: the temporal pass follows moved submeshes (planes[NEB_PLANE_SUBMESH_ID] exist only then)
+    float* xf_snap[2] = {nullptr, nullptr}; // neb_svgf_snapshot_transforms: the 4x4 table each slot's G-buffer was rendered with (n_geoms x 16)
+    bool has_snap[2] = {false, false};
+    uint32_t snap_epoch[2] = {0, 0};   // updates enqueued before the snapshot: equal for both slots = nothing moved between them
+    float4* motion_delta = nullptr;    // reproj_delta_kernel's output, n_geoms entries
+    uint32_t motion_geoms = 0;         // geometries the three tables were sized for
     neb::GiState* gi = nullptr;
     // neb_strip_frame* (strips.hip): a side stream for the halo exchange beside level 0, and the events that order it -- created on first use
     struct StripSync {

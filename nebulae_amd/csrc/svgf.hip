@@ -203,7 +203,135 @@ __device__ __forceinline__ float3 reproj_world_point(const ReprojCam& c, float i
 
 __device__ __forceinline__ bool d24_surface(uint32_t d) { return (d & 0xffffffu) != 0xffffffu; }
 
-__global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs a)
+// Option svgf_motion: the per-geometry delta table.  One lane per geometry; the two slots' 4x4 (row-vector convention: world =
+// (p, 1) . M, upper 3x3 A, translation t in row 3) -> flag, D = M_cur^-1 . M_hist (4x3) and K = (A_hist^-1 . A_cur)^T.  Double
+// precision in ONE written-down order, which tests/motion_ref.py repeats in float64 and must meet bit for bit:
+//   inverse of a 3x3: the nine cofactors, each "product - product"; det = (a00 c00 + a01 c01) + a02 c02; r = 1 / det;
+//                     inv[i][j] = c[j][i] * r
+//   3x3 product:      (X Y)[i][j] = (x[i][0] y[0][j] + x[i][1] y[1][j]) + x[i][2] y[2][j]
+//   D rows 0..2 = inv(A_cur) A_hist;  translation last: D row 3 [j] = t_hist[j] - ((t_cur[0] D[0][j] + t_cur[1] D[1][j]) + t_cur[2] D[2][j])
+//   K[i][j] = (inv(A_hist) A_cur)[j][i];  one rounding to fp32 at the end.
+// No contraction: this file is compiled with fp contract off, so every product and sum is a v_mul_f64 / v_add_f64 of its own
+// (checked in the ISA: the kernel holds no v_fma_f64 outside the division's expansion).
+struct Mat3d { double m[3][3]; };
+__device__ __forceinline__ bool delta_inverse(const Mat3d& a, Mat3d& inv)
+{
+    double c[3][3];
+    c[0][0] = a.m[1][1] * a.m[2][2] - a.m[1][2] * a.m[2][1];
+    c[0][1] = a.m[1][2] * a.m[2][0] - a.m[1][0] * a.m[2][2];
+    c[0][2] = a.m[1][0] * a.m[2][1] - a.m[1][1] * a.m[2][0];
+    c[1][0] = a.m[0][2] * a.m[2][1] - a.m[0][1] * a.m[2][2];
+    c[1][1] = a.m[0][0] * a.m[2][2] - a.m[0][2] * a.m[2][0];
+    c[1][2] = a.m[0][1] * a.m[2][0] - a.m[0][0] * a.m[2][1];
+    c[2][0] = a.m[0][1] * a.m[1][2] - a.m[0][2] * a.m[1][1];
+    c[2][1] = a.m[0][2] * a.m[1][0] - a.m[0][0] * a.m[1][2];
+    c[2][2] = a.m[0][0] * a.m[1][1] - a.m[0][1] * a.m[1][0];
+    const double det = (a.m[0][0] * c[0][0] + a.m[0][1] * c[0][1]) + a.m[0][2] * c[0][2];
+    const double r = 1.0 / det;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            inv.m[i][j] = c[j][i] * r;
+    return det != 0.0 && fabs(det) <= 1.7e308 && fabs(r) <= 1.7e308; // (false for NaN too)
+}
+__device__ __forceinline__ Mat3d delta_product(const Mat3d& x, const Mat3d& y)
+{
+    Mat3d o;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            o.m[i][j] = (x.m[i][0] * y.m[0][j] + x.m[i][1] * y.m[1][j]) + x.m[i][2] * y.m[2][j];
+    return o;
+}
+
+__global__ __launch_bounds__(64) void reproj_delta_kernel(const float* __restrict__ xf_cur, const float* __restrict__ xf_hist,
+                                                          float4* __restrict__ delta, uint32_t n)
+{
+    const uint32_t g = blockIdx.x * 64u + threadIdx.x;
+    if (g >= n)
+        return;
+    const float4* mc4 = reinterpret_cast<const float4*>(xf_cur) + 4 * (size_t)g;
+    const float4* mh4 = reinterpret_cast<const float4*>(xf_hist) + 4 * (size_t)g;
+    float mc[16], mh[16];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float4 c = mc4[r], h = mh4[r];
+        mc[4 * r] = c.x, mc[4 * r + 1] = c.y, mc[4 * r + 2] = c.z, mc[4 * r + 3] = c.w;
+        mh[4 * r] = h.x, mh[4 * r + 1] = h.y, mh[4 * r + 2] = h.z, mh[4 * r + 3] = h.w;
+    }
+    bool same = true, finite = true;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        same = same && __float_as_uint(mc[q]) == __float_as_uint(mh[q]);
+        finite = finite && fabsf(mc[q]) <= 3.0e38f && fabsf(mh[q]) <= 3.0e38f;
+    }
+    float d[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+    float k[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    uint32_t flag = kReprojDeltaSame;
+    if (!same) {
+        Mat3d ac, ah, ic, ih;
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                ac.m[i][j] = (double)mc[4 * i + j];
+                ah.m[i][j] = (double)mh[4 * i + j];
+            }
+        const bool ok_c = delta_inverse(ac, ic), ok_h = delta_inverse(ah, ih);
+        const Mat3d L = delta_product(ic, ah), Q = delta_product(ih, ac);
+        bool ok = finite && ok_c && ok_h;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double tj = (double)mh[12 + j] - (((double)mc[12] * L.m[0][j] + (double)mc[13] * L.m[1][j]) + (double)mc[14] * L.m[2][j]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                d[3 * i + j] = (float)L.m[i][j];
+                k[3 * i + j] = (float)Q.m[j][i];
+            }
+            d[9 + j] = (float)tj;
+        }
+#pragma unroll
+        for (int q = 0; q < 12; ++q)
+            ok = ok && fabsf(d[q]) <= 3.0e38f;
+#pragma unroll
+        for (int q = 0; q < 9; ++q)
+            ok = ok && fabsf(k[q]) <= 3.0e38f;
+        flag = ok ? kReprojDeltaMoved : kReprojDeltaSingular;
+        if (!ok) {
+#pragma unroll
+            for (int q = 0; q < 12; ++q)
+                d[q] = 0.f;
+#pragma unroll
+            for (int q = 0; q < 9; ++q)
+                k[q] = 0.f;
+        }
+    }
+    float4* e = delta + (size_t)kReprojDeltaFloat4 * g;
+    e[0] = make_float4(__uint_as_float(flag), 0.f, 0.f, 0.f);
+    e[1] = make_float4(d[0], d[1], d[2], d[3]);
+    e[2] = make_float4(d[4], d[5], d[6], d[7]);
+    e[3] = make_float4(d[8], d[9], d[10], d[11]);
+    e[4] = make_float4(k[0], k[1], k[2], k[3]);
+    e[5] = make_float4(k[4], k[5], k[6], k[7]);
+    e[6] = make_float4(k[8], 0.f, 0.f, 0.f);
+    e[7] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+hipError_t launch_reproj_delta(const float* xf_cur, const float* xf_hist, float4* delta, uint32_t n, hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(reproj_delta_kernel, dim3((n + 63u) / 64u), dim3(64), 0, s, xf_cur, xf_hist, delta, n);
+    return hipGetLastError();
+}
+
+// MOTION (option svgf_motion): the pixel's world point and geometric normal are carried to where that surface point
+// was in the history frame by its submesh's delta entry before anything else looks at them, and a tap counts only if the history
+// frame saw the same submesh there.  MOTION = false is the kernel as it was: `m` is not read and the code is the same.
+template <bool MOTION>
+__global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs a, ReprojMotion m)
 {
     const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (tile >= a.n_tiles)
@@ -216,14 +344,38 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
     const float4 Cc = a.rad_cur[i];
     const uint32_t dc = a.depth_cur[i];
     const uint2 nc = a.normal_cur[i];
+    uint32_t g = kReprojNoSubmesh;
+    if constexpr (MOTION)
+        g = m.id_cur[i];
     const float zc = depth_unorm24(dc);
 
     float4 Ch = Cc; // (with no history: a = 0 and lerp(Cc, Cc, 0) = Cc exactly)
     float Mh0 = 0.0f, Mh1 = 0.0f;
     uint32_t n = 0;
     if (a.hist_ok && d24_surface(dc)) {
-        const float3 P = reproj_world_point(a.cc, a.inv_W, a.inv_H, x, y, zc);
-        const float3 Ng = oct16_unpack_zw(nc.x); // geometric normal (.xy)
+        float3 P = reproj_world_point(a.cc, a.inv_W, a.inv_H, x, y, zc);
+        float3 Ng = oct16_unpack_zw(nc.x); // geometric normal (.xy)
+        bool frozen = false; // MOTION: the submesh's transform cannot be inverted -- no history
+        if constexpr (MOTION) {
+            if (g < m.n_delta) { // (no entry, no id: the point did not move -- P and Ng as they are)
+                const float4* e = m.delta + (size_t)kReprojDeltaFloat4 * g;
+                const uint32_t flag = __float_as_uint(e[0].x);
+                frozen = flag == kReprojDeltaSingular;
+                if (flag == kReprojDeltaMoved) { // the 96 bytes of D and K: only lanes on moved geometry (a tile on one object shares the lines)
+                    const float4 d0 = e[1], d1 = e[2], d2 = e[3], k0 = e[4], k1 = e[5], k2 = e[6];
+                    // P_h = (P, 1) . D, N_h = normalise(N . K): D = {d0.xyz | d0.w d1.xy | d1.zw d2.x | d2.yzw}, K = {k0.xyz | k0.w k1.xy | k1.zw k2.x}
+                    const float hx = fmaf(P.z, d1.z, fmaf(P.y, d0.w, fmaf(P.x, d0.x, d2.y)));
+                    const float hy = fmaf(P.z, d1.w, fmaf(P.y, d1.x, fmaf(P.x, d0.y, d2.z)));
+                    const float hz = fmaf(P.z, d2.x, fmaf(P.y, d1.y, fmaf(P.x, d0.z, d2.w)));
+                    const float nx = fmaf(Ng.z, k1.z, fmaf(Ng.y, k0.w, Ng.x * k0.x));
+                    const float ny = fmaf(Ng.z, k1.w, fmaf(Ng.y, k1.x, Ng.x * k0.y));
+                    const float nz = fmaf(Ng.z, k2.x, fmaf(Ng.y, k1.y, Ng.x * k0.z));
+                    const float len = sqrtf(fmaf(nz, nz, fmaf(ny, ny, nx * nx))); // (the correctly rounded one, as the divisions)
+                    P = make_float3(hx, hy, hz);
+                    Ng = make_float3(nx / len, ny / len, nz / len); // (len = 0: NaN, and no tap passes the normal test)
+                }
+            }
+        }
         // project P with the history camera
         const float rx = P.x - a.ch.ex, ry = P.y - a.ch.ey, rz = P.z - a.ch.ez;
         const float zl = -fmaf(rz, a.ch.zz, fmaf(ry, a.ch.zy, rx * a.ch.zx)); // linear depth of P in the history camera
@@ -232,7 +384,7 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
         const float ndc_x = cx / (zl * a.ch.sx), ndc_y = cy / (zl * a.ch.sy);
         const float fx = fmaf(ndc_x, a.half_W, a.half_W) - 0.5f; // continuous pixel position - 0.5: the taps are floor + {0, 1}
         const float fy = fmaf(-ndc_y, a.half_H, a.half_H) - 0.5f;
-        if (zl > 0.0f && fx > -1.0f && fx < (float)a.Wd && fy > -1.0f && fy < (float)a.Hd) { // (false for NaN too)
+        if (!frozen && zl > 0.0f && fx > -1.0f && fx < (float)a.Wd && fy > -1.0f && fy < (float)a.Hd) { // (false for NaN too)
             const float x0f = floorf(fx), y0f = floorf(fy);
             const float wx = fx - x0f, wy = fy - y0f;
             const int x0 = (int)x0f, y0 = (int)y0f;
@@ -248,10 +400,12 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
             j[2] = (size_t)cy1 * a.W + (uint32_t)cx0;
             j[3] = (size_t)cy1 * a.W + (uint32_t)cx1;
             const uint32_t* normal32 = reinterpret_cast<const uint32_t*>(a.normal_hist);
-            uint32_t dt[4], nt[4], mh[4], hl[4];
+            uint32_t dt[4], nt[4], mh[4], hl[4], gt[4];
             float4 rt[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
+                if constexpr (MOTION)
+                    gt[t] = m.id_hist[j[t]];
                 dt[t] = a.depth_hist[j[t]];
                 nt[t] = normal32[2 * j[t]]; // .xy: geometric normal
                 rt[t] = a.rad_hist[j[t]];
@@ -264,6 +418,9 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
                 const int px = x0 + (t & 1), py = y0 + (t >> 1);
                 if (px < 0 || px >= a.Wd || py < 0 || py >= a.Hd || !d24_surface(dt[t]))
                     continue;
+                if constexpr (MOTION)
+                    if (gt[t] != g) // the history frame saw another submesh there (every pixel, moved or not)
+                        continue;
                 const float3 Nt = oct16_unpack_zw(nt[t]);
                 if (!(fmaf(Ng.z, Nt.z, fmaf(Ng.y, Nt.y, Ng.x * Nt.x)) >= kReprojNormalCos))
                     continue;
@@ -316,10 +473,10 @@ static ReprojCam reproj_cam(const CameraBasis& b)
     return c;
 }
 
-hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
-                                     const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
-                                     const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
-                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s)
+static hipError_t launch_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
+                                   const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
+                                   const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
+                                   const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion* motion, hipStream_t s)
 {
     const uint32_t Wd = (L.W / 8u) * 8u, Hd = (L.H / 8u) * 8u; // the same-pixel pass's Dispatch(W/8, H/8) region
     if (Wd == 0 || Hd == 0)
@@ -351,8 +508,29 @@ hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam
     a.hist_ok = cam_hist != nullptr;
     a.cc = reproj_cam(cam_cur);
     a.ch = reproj_cam(cam_hist ? *cam_hist : cam_cur);
-    hipLaunchKernelGGL(svgf_temporal_reproject_kernel, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a);
+    if (motion)
+        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<true>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, *motion);
+    else
+        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<false>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, ReprojMotion{});
     return hipGetLastError();
+}
+
+hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
+                                     const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
+                                     const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
+                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s)
+{
+    return launch_reproject(L, cam_cur, cam_hist, rad_cur, rad_hist, depth_cur, depth_hist, normal_cur, normal_hist, mom_hist, mom_cur, variance,
+                            hlen_hist, hlen_cur, geometry, nullptr, s);
+}
+
+hipError_t launch_temporal_reproject_motion(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
+                                            const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
+                                            const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
+                                            const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion& motion, hipStream_t s)
+{
+    return launch_reproject(L, cam_cur, cam_hist, rad_cur, rad_hist, depth_cur, depth_hist, normal_cur, normal_hist, mom_hist, mom_cur, variance,
+                            hlen_hist, hlen_cur, geometry, &motion, s);
 }
 
 // The same decode for rows the temporal pass did not cover (halo rows of a strip; ragged images; a level run on its own).

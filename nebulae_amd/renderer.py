@@ -60,13 +60,23 @@ class DeferredRenderer:
         # Beyond the reference: reproject the history through the two frames' cameras (option svgf_reproject, set at init):
         # SVGF runs every frame, moving or not, and the history is never reset when the camera stops.
         self.temporal_reprojection = False
+        # ... and follow submeshes moved by update_transforms (option svgf_motion, set at init; needs temporal_reprojection): a pixel's
+        # history is looked up where its surface point was one frame ago, and only taps of the same submesh count.  submit_commands_gbuffer
+        # writes the ids and takes the transform snapshot; a caller that uploads its own G-buffer uploads PLANE_SUBMESH_ID too and
+        # calls svgf.snapshot_transforms(SLOT_CURRENT) once the frame's update_transforms has been made.
+        self.motion_vectors = False
         self.info = None
 
     # ---- DeferredRenderer::Init (src/DeferredRenderer.cpp:26-57) ----
     def init(self, width, height, atrous_levels=None, device=0, row_begin=0, row_end=0):
         self.svgf.init(width, height, atrous_levels=atrous_levels, device=device, row_begin=row_begin, row_end=row_end)
+        if self.motion_vectors and not self.temporal_reprojection:
+            self.svgf.destroy()
+            raise NebError("DeferredRenderer.init: motion_vectors needs temporal_reprojection")
         if self.temporal_reprojection:
             self.svgf.set_option("svgf_reproject", 1)
+        if self.motion_vectors:
+            self.svgf.set_option("svgf_motion", 1)
         self.width, self.height = width, height
         return True
 

@@ -14,8 +14,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (PLANE_DEPTH, PLANE_MOMENTS, PLANE_NORMAL, PLANE_RADIANCE, PLANE_SCRATCH, PLANE_VARIANCE,  # noqa: F401
-                   PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY, PLANE_HISTORY_LENGTH, SLOT_CURRENT,
-                   SLOT_HISTORY, NebError)
+                   PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY, PLANE_HISTORY_LENGTH, PLANE_SUBMESH_ID,
+                   SLOT_CURRENT, SLOT_HISTORY, NebError)
 
 # plane -> (numpy dtype, channels)
 PLANE_LAYOUT = {
@@ -23,6 +23,7 @@ PLANE_LAYOUT = {
     PLANE_MOMENTS: (np.float16, 2), PLANE_VARIANCE: (np.float16, 1), PLANE_SCRATCH: (np.float32, 4),
     PLANE_ALBEDO: (np.uint32, 1), PLANE_ROUGH_METAL: (np.float16, 2), PLANE_WORLDPOS: (np.float16, 4),
     PLANE_LDR: (np.uint32, 1), PLANE_GEOMETRY: (np.float32, 4), PLANE_HISTORY_LENGTH: (np.uint8, 1),
+    PLANE_SUBMESH_ID: (np.uint32, 1),
 }
 
 
@@ -163,6 +164,19 @@ class SVGFDenoiser:
         """neb_svgf_set_camera: the camera (scene.CameraDesc) slot `slot`'s depth / normal planes were rendered with -- what the
         reprojecting temporal pass (option svgf_reproject) maps them with.  submit_commands_gbuffer records its own."""
         self._check(self._lib.neb_svgf_set_camera(self._ctx, int(slot), C.byref(cam)), "neb_svgf_set_camera")
+
+    def snapshot_transforms(self, slot, stream=0):
+        """neb_svgf_snapshot_transforms: remember the scene's transforms as those slot `slot`'s G-buffer was rendered with (option
+        svgf_motion; submit_commands_gbuffer takes its own).  A caller that uploads its own G-buffer calls it next to set_camera."""
+        self._check(self._lib.neb_svgf_snapshot_transforms(self._ctx, int(slot), C.c_void_p(stream)), "neb_svgf_snapshot_transforms")
+
+    def debug_delta_table(self, n_geoms, stream=0):
+        """neb_svgf_debug_delta_table -> float32 [n, 32]: the delta kernel's entries for the snapshots of (cur, hist)"""
+        out = np.zeros((int(n_geoms), 32), np.float32)
+        n = C.c_uint32()
+        self._check(self._lib.neb_svgf_debug_delta_table(self._ctx, out.ctypes.data_as(C.POINTER(C.c_float)), int(n_geoms), C.byref(n),
+                                                         C.c_void_p(stream)), "neb_svgf_debug_delta_table")
+        return out[:n.value]
 
     def synchronize(self, stream=0):
         self._check(self._lib.neb_stream_synchronize(self._ctx, C.c_void_p(stream)), "neb_stream_synchronize")
