@@ -142,6 +142,7 @@ int neb_svgf_get_params(const neb_ctx* ctx, neb_svgf_params* out);
  *   "gi_sun_hints":     4 (default), 2 or 0: how many of a triangle's occluder hints the shade pass tries (with the traverser's own
  *                       triangle test) before it leaves the shadow ray to the list pass; results are bit-identical in all three;
  *   "gi_max_bvh_depth": 1..21, the deepest BVH4 neb_gi_build_bvh accepts (default 21 = traversal stack / 3);
+ *   "gi_deform_stage":  0 (default) / 1: where neb_gi_update_vertices' scatter kernel reads the staged vertices from, see there;
  *   "svgf_fuse":        0 (default) / 1 (opt-in), see neb_svgf_atrous;   "svgf_profile": 0 (default) / 1 / 2, see neb_svgf_level_times;
  *   "svgf_reproject":   0 (default) / 1 (opt-in): the temporal pass reprojects the history through the two frames' cameras, see
  *                       neb_svgf_set_camera.  NEB_ERR_STATE on a row-strip context.  1 allocates the (zeroed) history-length plane,
@@ -428,6 +429,43 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream);
  * transform takes a corner of the submesh's object-space box (or a vertex) to a position that is not finite.  n == 0: NEB_OK. */
 int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, const float* surfaceToWorld /* n x 16, as neb_geometry_desc */,
                              uint32_t n, neb_stream stream);
+/* Deforming submeshes: new object-space vertices for ranges of n submeshes, the tree kept.  NO reference counterpart:
+ * the reference builds its BLASes without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79), so a swaying curtain, a skinned figure or
+ * a morph target would mean new BLASes there; here it is the refit of neb_gi_update_transforms with another way in.
+ * Entry k replaces vertices [firstVertex, firstVertex + numVertices) of geometry `geometry`: positions (float3, object space, required),
+ * and optionally normals (float3) and tangents (float4); NULL keeps what the geometry has.  Pointers are HOST pointers with strides in
+ * bytes, as in neb_geometry_desc; the call copies what it needs before it returns.  Indices, UVs, materials and vertex counts do not change.
+ * What is rewritten, on the device and in place: the position / normal / tangent pools, the world-space triangles of the named submeshes
+ * (ALL their triangles, baked under the current transform in the operation order of neb_gi_set_scene: same bits), the normal and tangent
+ * words of their 128-byte shading records when an entry carried normals or tangents (every other word keeps its bits), the boxes of the
+ * nodes above them and the 64-byte nodes.  Topology, node numbering, leaf order and depth do not change; results are those of a tree built
+ * from the deformed scene up to exact ties between coincident hits; a leaf holding a clipped reference of a deformed triangle takes the
+ * whole triangle's bounds.  Tree quality degrades with the amplitude: DESIGN.md 3.4b.
+ * Streams, sun table, strips: exactly as neb_gi_update_transforms -- enqueue only, no device synchronisation, ordered behind every
+ * dispatch enqueued before the call on whichever stream; the host waits only when it is 4 updates (of either kind) ahead of the device;
+ * lit bits and hints are not used from the moment of the call and "gi_sun_hold" decides when a table is built against the new scene box.
+ * No allocation once the pinned staging has reached the size of the largest update seen (it is allocated by the first call).
+ * A later neb_gi_update_transforms applies its matrix to the deformed positions; a later neb_gi_build_bvh builds from them and packs the
+ * records from the new normals and tangents.  "svgf_motion": a vertex update leaves the transform snapshots equal, so pixels of a deformed
+ * submesh reproject as if static (the submesh-id test still applies).
+ * Refusals, each leaving everything unchanged: NEB_ERR_STATE before a successful neb_gi_build_bvh; NEB_ERR_INVALID_ARG for updates == NULL
+ * with n > 0, NULL positions, a geometry >= n_geoms, a range beyond the geometry's numVertices, two overlapping ranges of one geometry in
+ * the call, normals or tangents for a geometry set without all its attribute streams, a stride smaller than the element;
+ * NEB_ERR_OUT_OF_RANGE when a position, or its world position under the current matrix, is not finite.  n == 0, or every numVertices == 0:
+ * NEB_OK, nothing enqueued.
+ * Option "gi_deform_stage" (A/B arm for profiling, results never depend on it): 0 (default) = the scatter kernel reads the pinned staging
+ * directly, 1 = the staging is copied to a device buffer first (one hipMemcpyAsync); profiles/deform_times.json has both times. */
+typedef struct neb_vertex_update {
+    uint32_t geometry;                 /* index into neb_gi_set_scene's geometries */
+    uint32_t firstVertex, numVertices; /* range inside that geometry's vertices */
+    const void* positions;             /* float3, object space; required */
+    uint32_t positionStride;
+    const void* normals;               /* float3; NULL = keep */
+    uint32_t normalStride;
+    const void* tangents;              /* float4; NULL = keep */
+    uint32_t tangentStride;
+} neb_vertex_update;
+int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream);
 int neb_gi_scene_info(const neb_ctx* ctx, uint32_t* n_triangles, uint32_t* n_nodes);
 /* Device bytes of the scene: {texture footprint tables + material bundles, triangles + shading records, BVH nodes: the
  * builder's 128-byte nodes + the 64-byte quantised nodes the rays walk}. */

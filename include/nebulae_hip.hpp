@@ -143,6 +143,12 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_update_transforms(m_svgf.Context(), geometryIndices, surfaceToWorld, n, commandList), "neb_gi_update_transforms");
         }
+        // No reference counterpart (its BLASes are built without ALLOW_UPDATE, RTAccelerationStructureBuilder.cpp:79): new object-space
+        // vertices for ranges of submeshes -- a swaying drape, a skinned figure --, the tree refitted in place
+        void UpdateVertices(const neb_vertex_update* updates, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_update_vertices(m_svgf.Context(), updates, n, commandList), "neb_gi_update_vertices");
+        }
         void SubmitCommandsGIPathtrace(const neb_gi_constants& globalConstants, neb_stream commandList)
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_trace(m_svgf.Context(), &globalConstants, commandList), "neb_gi_trace");

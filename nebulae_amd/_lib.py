@@ -90,6 +90,13 @@ class StripPeers(C.Structure):
     _fields_ = [("up", C.c_void_p), ("down", C.c_void_p)]
 
 
+class VertexUpdate(C.Structure):
+    """neb_vertex_update"""
+    _fields_ = [("geometry", C.c_uint32), ("firstVertex", C.c_uint32), ("numVertices", C.c_uint32),
+                ("positions", C.c_void_p), ("positionStride", C.c_uint32), ("normals", C.c_void_p), ("normalStride", C.c_uint32),
+                ("tangents", C.c_void_p), ("tangentStride", C.c_uint32)]
+
+
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -101,6 +108,7 @@ def _gi_sigs():
                                        C.POINTER(S.TextureDesc), C.c_uint32]),
         "neb_gi_build_bvh": (C.c_int, [C.c_void_p, C.c_void_p]),
         "neb_gi_update_transforms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
+        "neb_gi_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_scene_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
         "neb_gi_bvh_depth": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
         "neb_gi_build_passes": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

@@ -1600,6 +1600,13 @@ int gi_set_sun_hints(neb_ctx* ctx, int n)
     ctx->gi->sun_hints = n;
     return NEB_OK;
 }
+int gi_set_deform_stage(neb_ctx* ctx, int mode)
+{
+    if (!ctx->gi || (mode != 0 && mode != 1))
+        return NEB_ERR_STATE;
+    ctx->gi->deform_stage = mode;
+    return NEB_OK;
+}
 int gi_set_debug_hits(neb_ctx* ctx, int on)
 {
     if (!ctx->gi)

@@ -65,6 +65,10 @@ void gi_destroy(GiState* g)
             (void)hipEventDestroy(e);
     if (g->h_stage)
         (void)hipHostFree(g->h_stage);
+    if (g->h_vstage)
+        (void)hipHostFree(g->h_vstage);
+    if (g->d_vstage)
+        (void)hipFree(g->d_vstage);
     delete g;
 }
 
@@ -1231,6 +1235,8 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         memcpy(hg.m, m, sizeof(hg.m));
         hg.firstIndex = d.firstIndex;
         hg.vertexBase = vertex_base;
+        hg.n_verts = s.numVertices;
+        hg.valid = d.valid != 0;
         hg.firstTri = (uint32_t)(g->h_tris.size() / 12);
         hg.firstRef = (uint32_t)g->h_ref_verts.size();
         auto rd_index = [&](uint32_t i) -> uint32_t {
@@ -1453,7 +1459,7 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         (e = upload(g, dtexs, &g->view.texs)) != hipSuccess || (e = upload(g, indices, &g->view.indices)) != hipSuccess ||
         (e = upload(g, normals, &g->view.normals)) != hipSuccess || (e = upload(g, uvs, &g->view.uvs)) != hipSuccess ||
         (e = upload(g, tangents, &g->view.tangents)) != hipSuccess || (e = upload(g, heads, &g->shade_heads)) != hipSuccess ||
-        (e = upload(g, g->h_pos, &g->d_pos)) != hipSuccess) {
+        (e = upload(g, g->h_pos, const_cast<const float**>(&g->d_pos))) != hipSuccess) {
         gi_destroy(g);
         return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_scene: upload", e);
     }
@@ -1951,6 +1957,7 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     {
         SceneView sv = g->view;
         sv.tris = d_final;
+        BUILD_HIP(gi_sun_table_order(g, stream)); // (the normal and tangent pools may have been rewritten on another stream: neb_gi_update_vertices)
         hipLaunchKernelGGL(pack_shade_records_kernel, dim3(nb), dim3(256), 0, stream, sv, n, d_shade);
         BUILD_HIP(hipGetLastError());
     }

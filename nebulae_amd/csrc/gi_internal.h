@@ -248,6 +248,8 @@ struct GiState {
         uint32_t firstIndex = 0, vertexBase = 0, n_tris = 0; // into h_indices / h_pos; triangles of the geometry
         uint32_t firstTri = 0;                               // its first triangle in h_tris (geometries follow one another)
         uint32_t firstRef = 0, n_refs = 0;                   // its referenced vertices (each once), into h_ref_verts
+        uint32_t n_verts = 0;                                // numVertices of neb_gi_set_scene (neb_gi_update_vertices checks ranges against it)
+        bool valid = false;                                  // DevGeom::valid: the normal and tangent pools hold data of this geometry
         float obj_lo[3] = {0, 0, 0}, obj_hi[3] = {0, 0, 0};  // object-space box of the referenced vertices
         float world_lo[3] = {0, 0, 0}, world_hi[3] = {0, 0, 0}; // exact world-space box under the current transform
         float m[16] = {};                                    // surfaceToWorld as last set
@@ -260,7 +262,7 @@ struct GiState {
     uint32_t seen_stamp = 0;
     // ... and on the device: the object-space positions, the 4x4 of every geometry, and two stamp arrays -- geom_epoch[g] == epoch:
     // geometry g was moved by the update in progress; node_epoch[i] == epoch: a child box of node i was rewritten by it.
-    const float* d_pos = nullptr;
+    float* d_pos = nullptr; // (rewritten by neb_gi_update_vertices)
     float* d_xf = nullptr;
     uint32_t* d_geom_epoch = nullptr;
     uint32_t* d_node_epoch = nullptr; // (belongs to the tree: replaced by every build)
@@ -273,6 +275,18 @@ struct GiState {
     StageEntry* h_stage = nullptr;    // [kStageSlots][n_geoms]
     hipEvent_t stage_ev[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
     bool stage_used[kStageSlots] = {false, false, false, false};
+    // ---- deforming submeshes: neb_gi_update_vertices (gi_refit.hip) ----
+    // One staged range of vertices: lanes [first_lane, first_lane + count) of deform_scatter_kernel write pool vertices dst ..;
+    // the offsets are in floats from the start of the slot's data, kNoStream where the update keeps that attribute.
+    struct DeformRange { uint32_t first_lane, count, dst, geom, pos_off, nrm_off, tan_off, pad; };
+    static constexpr uint32_t kNoStream = 0xffffffffu;
+    // The vertex data of an update waits in pinned host memory like the matrices of h_stage, in the same ring of kStageSlots slots under
+    // the same events (slot = epoch % kStageSlots for either kind of update).  Allocated by the first update, grown to the largest seen.
+    void* h_vstage = nullptr;         // [kStageSlots][vstage_cap bytes]: {DeformRange x n, padded to 16 B | positions | normals | tangents}
+    size_t vstage_cap = 0;
+    void* d_vstage = nullptr;         // "gi_deform_stage" = 1: the slot is copied here (one hipMemcpyAsync) and the scatter reads device memory
+    size_t d_vstage_cap = 0;
+    int deform_stage = 0;             // option "gi_deform_stage"
     // Streams that have read triangles / nodes / geometry tables since the last update: an update on another stream orders itself
     // behind them (an event recorded on each, waited for on its own stream).  More than kReaderStreams: it waits for the device.
     static constexpr int kReaderStreams = 4;

@@ -5,6 +5,13 @@
 // acceleration structure is ONE tree over world-space triangles, so the counterpart is: bake the moved submeshes' triangles again on the
 // device (same operation order as the host bake of neb_gi_set_scene, same bits), refit the boxes of the 128-byte nodes bottom-up, one
 // launch per level, and quantise the 64-byte nodes again.  Topology, node numbering, leaf order and depth stay.
+//
+// neb_gi_update_vertices has NO reference counterpart: the reference builds its BLASes without ALLOW_UPDATE
+// (RTAccelerationStructureBuilder.cpp:79), so a deformed mesh means new BLASes there.  Here a deformation is the same refit with
+// another way in: new object-space vertices are scattered into the device pools, the stamped geometries are baked again by the
+// very rebake_kernel of the transform path, and the normal / tangent words of their 128-byte shading records are rewritten.
+#include <algorithm>
+
 #include "gi_device.h"
 
 namespace neb {
@@ -77,6 +84,67 @@ __global__ void rebake_kernel(float4* __restrict__ tris, uint32_t n_slots, uint3
     tris[3 * (size_t)i + 2] = make_float4(__fsub_rn(w2.z, w0.z), ids.y, ids.z, ids.w);
 }
 
+// One lane per staged vertex: the compact streams of the update -> the object-space position pool and the normal / tangent pools.
+// The lane finds its range by bisection over first_lane (n ranges, ascending, none empty); lane 0 of a range stamps its geometry.
+// `stage` is the pinned slot itself or its device copy ("gi_deform_stage").
+__global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const float* __restrict__ data, uint32_t n_lanes,
+                                      uint32_t n_pool, uint32_t n_geoms, uint32_t epoch, float* __restrict__ pos, float* __restrict__ normals,
+                                      float* __restrict__ tangents, uint32_t* __restrict__ geom_epoch)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[mid].first_lane <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const GiState::DeformRange r = ranges[lo];
+    const uint32_t j = k - r.first_lane;
+    if (j >= r.count || r.dst + j >= n_pool)
+        return;
+    const size_t v = (size_t)r.dst + j;
+    const float* sp = data + r.pos_off + 3 * (size_t)j;
+    pos[3 * v] = sp[0], pos[3 * v + 1] = sp[1], pos[3 * v + 2] = sp[2];
+    if (r.nrm_off != GiState::kNoStream) {
+        const float* sn = data + r.nrm_off + 3 * (size_t)j;
+        normals[3 * v] = sn[0], normals[3 * v + 1] = sn[1], normals[3 * v + 2] = sn[2];
+    }
+    if (r.tan_off != GiState::kNoStream) {
+        const float* st = data + r.tan_off + 4 * (size_t)j;
+        tangents[4 * v] = st[0], tangents[4 * v + 1] = st[1], tangents[4 * v + 2] = st[2], tangents[4 * v + 3] = st[3];
+    }
+    if (j == 0 && r.geom < n_geoms)
+        geom_epoch[r.geom] = epoch;
+}
+
+// One lane per leaf-order slot: the record of a slot whose geometry is stamped gets its normal and tangent words again from the pools,
+// in pack_shade_records_kernel's layout (r0-r2 .xyz the normals, r3-r5 the tangents).  Every other word keeps its bits: the UV words
+// (r0-r2 .w, r6.xyz), geometry + lit bits (r6.w), primitive and hints (r7).  The record of a geometry without attributes stays zeros.
+__global__ void repack_records_kernel(float* __restrict__ shade, const float4* __restrict__ tris, uint32_t n_slots, uint32_t n_geoms, uint32_t epoch,
+                                      const uint32_t* __restrict__ geom_epoch, const DevGeom* __restrict__ geoms, const uint32_t* __restrict__ indices,
+                                      const float* __restrict__ normals, const float* __restrict__ tangents)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_slots)
+        return;
+    const float4 ids = tris[3 * (size_t)i + 2];
+    const uint32_t gi = __float_as_uint(ids.y), prim = __float_as_uint(ids.z);
+    if (gi >= n_geoms || geom_epoch[gi] != epoch || !geoms[gi].valid)
+        return;
+    const uint32_t first = geoms[gi].firstIndex + 3u * prim, vb = geoms[gi].vertexBase;
+    float* rec = shade + 32 * (size_t)i;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const size_t v = (size_t)vb + indices[first + k];
+        rec[4 * k] = normals[3 * v], rec[4 * k + 1] = normals[3 * v + 1], rec[4 * k + 2] = normals[3 * v + 2];
+        reinterpret_cast<float4*>(rec)[3 + k] = make_float4(tangents[4 * v], tangents[4 * v + 1], tangents[4 * v + 2], tangents[4 * v + 3]);
+    }
+}
+
 // min / max in the order the builder's LDS atomics use (-0 below +0): a refit over unmoved boxes reproduces the builder's bits
 __device__ __forceinline__ uint32_t refit_ordered(float f)
 {
@@ -138,6 +206,47 @@ __global__ void refit_level_kernel(Bvh4Node* __restrict__ nodes, uint32_t first,
     nf[q] = lo[0], nf[4 + q] = lo[1], nf[8 + q] = lo[2];
     nf[16 + q] = hi[0], nf[20 + q] = hi[1], nf[24 + q] = hi[2];
     node_epoch[i] = epoch; // (up to four lanes store the same word)
+}
+
+// ---- what the two kinds of update share on the host ----
+// the scene box: the union of the geometries' exact boxes, as neb_gi_set_scene folds it
+static void refit_scene_box(GiState* g)
+{
+    float smin[3] = {3.4e38f, 3.4e38f, 3.4e38f}, smax[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+    for (const GiState::HostGeom& hg : g->h_geoms)
+        if (hg.n_tris)
+            for (int q = 0; q < 3; ++q) {
+                smin[q] = fminf(smin[q], hg.world_lo[q]);
+                smax[q] = fmaxf(smax[q], hg.world_hi[q]);
+            }
+    memcpy(g->scene_min, smin, sizeof(smin));
+    memcpy(g->scene_max, smax, sizeof(smax));
+}
+// The sun table as after a scene change: the flags in the records are those of the old positions and are ignored from here on (state 2); the hold
+// policy of gi_sun_table_update decides when the next table is built -- and looks at the new scene box when it does.
+static void refit_drop_sun_table(GiState* g)
+{
+    if (g->sun_table_state == 0)
+        return;
+    if (g->sun_table_state == 1)
+        g->sun_hold = g->sun_hold_option > 0 ? (uint32_t)g->sun_hold_option : (g->sun_table_age < 32u ? 32u : 2u); // (kSunTableLife, kSunHoldAfterShortLife)
+    g->sun_table_state = 2;
+    g->sun_table_stale = true;
+    g->sun_seen = 0;
+}
+// the levels of the tree, deepest first, then the 64-byte nodes again
+static hipError_t refit_enqueue_levels(GiState* g, uint32_t call, hipStream_t stream)
+{
+    const uint32_t n_slots = g->view.n_tris;
+    for (size_t lv = g->level_first.size(); lv-- > 1;) {
+        const uint32_t first = g->level_first[lv - 1], count = g->level_first[lv] - first;
+        if (count)
+            hipLaunchKernelGGL(refit_level_kernel, dim3((4u * count + 255) / 256), dim3(256), 0, stream, const_cast<Bvh4Node*>(g->view.nodes), first, count,
+                               g->n_nodes, g->view.tris, n_slots, g->n_geoms, call, (const uint32_t*)g->d_geom_epoch, g->d_node_epoch);
+    }
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    return gi_quantise_nodes(g->view.nodes, g->n_nodes, const_cast<Bvh4NodeQ*>(g->view.qnodes), stream);
 }
 
 } // namespace neb
@@ -258,25 +367,9 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
             memcpy(hg.world_hi, boxes[k].hi, 12);
         }
     }
-    if (any_tris) { // the scene box: the union of the geometries' exact boxes, as neb_gi_set_scene folds it
-        float smin[3] = {3.4e38f, 3.4e38f, 3.4e38f}, smax[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-        for (const GiState::HostGeom& hg : g->h_geoms)
-            if (hg.n_tris)
-                for (int q = 0; q < 3; ++q) {
-                    smin[q] = fminf(smin[q], hg.world_lo[q]);
-                    smax[q] = fmaxf(smax[q], hg.world_hi[q]);
-                }
-        memcpy(g->scene_min, smin, sizeof(smin));
-        memcpy(g->scene_max, smax, sizeof(smax));
-    }
-    // The sun table as after a scene change: the flags in the records are those of the old positions and are ignored from here on (state 2); the hold
-    // policy of gi_sun_table_update decides when the next table is built -- and looks at the new scene box when it does.
-    if (any_tris && g->sun_table_state != 0) {
-        if (g->sun_table_state == 1)
-            g->sun_hold = g->sun_hold_option > 0 ? (uint32_t)g->sun_hold_option : (g->sun_table_age < 32u ? 32u : 2u); // (kSunTableLife, kSunHoldAfterShortLife)
-        g->sun_table_state = 2;
-        g->sun_table_stale = true;
-        g->sun_seen = 0;
+    if (any_tris) {
+        refit_scene_box(g);
+        refit_drop_sun_table(g);
     }
     // ---- enqueue ----
     const uint32_t n_slots = g->view.n_tris;
@@ -287,15 +380,200 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
     g->stage_used[slot] = true;
     if (any_tris && n_slots) {
         hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
-                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->d_pos, (const float*)g->d_xf);
-        for (size_t lv = g->level_first.size(); lv-- > 1;) { // deepest level first
-            const uint32_t first = g->level_first[lv - 1], count = g->level_first[lv] - first;
-            if (count)
-                hipLaunchKernelGGL(refit_level_kernel, dim3((4u * count + 255) / 256), dim3(256), 0, stream, const_cast<Bvh4Node*>(g->view.nodes), first, count,
-                                   g->n_nodes, g->view.tris, n_slots, g->n_geoms, call, (const uint32_t*)g->d_geom_epoch, g->d_node_epoch);
+                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
+        GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
+    }
+    GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_update_vertices: no built scene (neb_gi_set_scene + neb_gi_build_bvh first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!updates)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: null pointer");
+    // ---- everything that can refuse the call comes before anything changes ----
+    struct Span { uint32_t geom, first, count, k; };
+    std::vector<Span> spans;
+    spans.reserve(n);
+    size_t n_lanes = 0, n_nrm = 0, n_tan = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_vertex_update& u = updates[k];
+        if (!u.positions)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: null positions");
+        if (u.geometry >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: geometry index out of range");
+        const GiState::HostGeom& hg = g->h_geoms[u.geometry];
+        if ((uint64_t)u.firstVertex + u.numVertices > hg.n_verts)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: vertex range beyond the geometry's numVertices");
+        if ((u.normals || u.tangents) && !hg.valid)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: normals or tangents for a geometry that was set without its attribute streams");
+        if (u.positionStride < 12u || (u.normals && u.normalStride < 12u) || (u.tangents && u.tangentStride < 16u))
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: a stride is smaller than its element");
+        if (u.numVertices == 0)
+            continue;
+        spans.push_back({u.geometry, u.firstVertex, u.numVertices, k});
+        n_lanes += u.numVertices;
+        n_nrm += u.normals ? u.numVertices : 0u;
+        n_tan += u.tangents ? u.numVertices : 0u;
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom != b.geom ? a.geom < b.geom : a.first < b.first; });
+    for (size_t i = 1; i < spans.size(); ++i)
+        if (spans[i].geom == spans[i - 1].geom && (uint64_t)spans[i - 1].first + spans[i - 1].count > spans[i].first)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: two ranges of one geometry overlap");
+    if (n_lanes > 0xffffffffull / 10u) // (offsets into the slot are 32-bit float counts: at most 10 floats per vertex)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: too many vertices in one call");
+    for (const Span& sp : spans) {
+        const neb_vertex_update& u = updates[sp.k];
+        const float* m = g->h_geoms[sp.geom].m;
+        for (uint32_t j = 0; j < sp.count; ++j) {
+            float a[3], w[3];
+            memcpy(a, (const uint8_t*)u.positions + (size_t)j * u.positionStride, 12);
+            if (!(fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f))
+                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_update_vertices: a position is not a finite number");
+            if (!gi_bake_point(m, a, w))
+                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_update_vertices: a position (after the instance transform) is not a finite number");
         }
-        GI_HIP(ctx, hipGetLastError());
-        GI_HIP(ctx, gi_quantise_nodes(g->view.nodes, g->n_nodes, const_cast<Bvh4NodeQ*>(g->view.qnodes), stream));
+    }
+    if (spans.empty())
+        return NEB_OK; // every range is empty: nothing moves, nothing is enqueued, the sun table stays
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    // ---- the staging slot: pinned host memory, {ranges | positions | normals | tangents}, grown to the largest update seen ----
+    const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
+    const size_t bytes = head + 4u * (3u * n_lanes + 3u * n_nrm + 4u * n_tan);
+    if (bytes > g->vstage_cap) {
+        for (int q = 0; q < GiState::kStageSlots; ++q) // (growing frees the ring: every update that may still read it has to be done)
+            if (g->stage_used[q])
+                GI_HIP(ctx, hipEventSynchronize(g->stage_ev[q]));
+        void* fresh = nullptr;
+        const size_t cap = (bytes + 4095u) & ~(size_t)4095u;
+        GI_HIP(ctx, hipHostMalloc(&fresh, cap * GiState::kStageSlots, hipHostMallocDefault));
+        if (g->h_vstage)
+            (void)hipHostFree(g->h_vstage);
+        g->h_vstage = fresh;
+        g->vstage_cap = cap;
+    }
+    if (g->deform_stage == 1 && g->vstage_cap > g->d_vstage_cap) {
+        void* fresh = nullptr;
+        GI_HIP(ctx, hipMalloc(&fresh, g->vstage_cap));
+        if (g->d_vstage)
+            (void)hipFree(g->d_vstage); // (waits for the device: the update that read it is done)
+        g->d_vstage = fresh;
+        g->d_vstage_cap = g->vstage_cap;
+    }
+    const uint32_t call = g->epoch + 1u;
+    const int slot = (int)(call % (uint32_t)GiState::kStageSlots);
+    if (!g->stage_ev[slot])
+        GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
+    if (g->stage_used[slot])
+        GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
+    // ---- order: behind the last rewrite, and behind every stream that may still be reading what is about to be rewritten ----
+    GI_HIP(ctx, gi_sun_table_order(g, stream));
+    if (g->reader_overflow) {
+        GI_HIP(ctx, hipDeviceSynchronize());
+    } else {
+        for (int k = 0; k < g->n_reader_streams; ++k) {
+            if (g->reader_streams[k] == stream)
+                continue;
+            if (!g->reader_ev[k])
+                GI_HIP(ctx, hipEventCreateWithFlags(&g->reader_ev[k], hipEventDisableTiming));
+            GI_HIP(ctx, hipEventRecord(g->reader_ev[k], g->reader_streams[k]));
+            GI_HIP(ctx, hipStreamWaitEvent(stream, g->reader_ev[k], 0));
+        }
+    }
+    g->n_reader_streams = 0;
+    g->reader_overflow = false;
+    // ---- commit the host side: the slot, h_pos, the boxes ----
+    g->epoch = call;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    GiState::DeformRange* ranges = (GiState::DeformRange*)base;
+    float* data = (float*)(base + head);
+    uint32_t lane = 0, off_p = 0, off_n = (uint32_t)(3u * n_lanes), off_t = (uint32_t)(3u * n_lanes + 3u * n_nrm);
+    bool any_tris = false, any_attr = false;
+    for (size_t i = 0; i < spans.size(); ++i) {
+        const Span& sp = spans[i];
+        const neb_vertex_update& u = updates[sp.k];
+        GiState::HostGeom& hg = g->h_geoms[sp.geom];
+        GiState::DeformRange& r = ranges[i];
+        r.first_lane = lane, r.count = sp.count, r.dst = hg.vertexBase + sp.first, r.geom = sp.geom, r.pad = 0;
+        r.pos_off = off_p;
+        r.nrm_off = u.normals ? off_n : GiState::kNoStream;
+        r.tan_off = u.tangents ? off_t : GiState::kNoStream;
+        float* hp = &g->h_pos[3 * (size_t)r.dst];
+        for (uint32_t j = 0; j < sp.count; ++j) {
+            memcpy(data + off_p + 3 * (size_t)j, (const uint8_t*)u.positions + (size_t)j * u.positionStride, 12);
+            memcpy(hp + 3 * (size_t)j, data + off_p + 3 * (size_t)j, 12);
+        }
+        if (u.normals)
+            for (uint32_t j = 0; j < sp.count; ++j)
+                memcpy(data + off_n + 3 * (size_t)j, (const uint8_t*)u.normals + (size_t)j * u.normalStride, 12);
+        if (u.tangents)
+            for (uint32_t j = 0; j < sp.count; ++j)
+                memcpy(data + off_t + 4 * (size_t)j, (const uint8_t*)u.tangents + (size_t)j * u.tangentStride, 16);
+        lane += sp.count, off_p += 3u * sp.count;
+        off_n += u.normals ? 3u * sp.count : 0u;
+        off_t += u.tangents ? 4u * sp.count : 0u;
+        any_attr = any_attr || u.normals || u.tangents;
+        if (hg.n_tris) {
+            hg.dirty = true;
+            any_tris = true;
+        }
+    }
+    // the boxes of every touched geometry over its referenced vertices: object space, and world space in the bake's own arithmetic
+    for (size_t i = 0; i < spans.size(); ++i) {
+        if (i && spans[i].geom == spans[i - 1].geom)
+            continue;
+        GiState::HostGeom& hg = g->h_geoms[spans[i].geom];
+        if (!hg.n_tris)
+            continue;
+        for (int q = 0; q < 3; ++q) {
+            hg.obj_lo[q] = hg.world_lo[q] = 3.4e38f;
+            hg.obj_hi[q] = hg.world_hi[q] = -3.4e38f;
+        }
+        for (uint32_t r = 0; r < hg.n_refs; ++r) {
+            const float* a = &g->h_pos[3 * (size_t)(hg.vertexBase + g->h_ref_verts[hg.firstRef + r])];
+            float w[3];
+            (void)gi_bake_point(hg.m, a, w); // (checked finite above, or when the position / the matrix was accepted)
+            for (int q = 0; q < 3; ++q) {
+                hg.obj_lo[q] = fminf(hg.obj_lo[q], a[q]);
+                hg.obj_hi[q] = fmaxf(hg.obj_hi[q], a[q]);
+                hg.world_lo[q] = fminf(hg.world_lo[q], w[q]);
+                hg.world_hi[q] = fmaxf(hg.world_hi[q], w[q]);
+            }
+        }
+    }
+    if (any_tris)
+        refit_scene_box(g);
+    if (any_tris)
+        refit_drop_sun_table(g);
+    // ---- enqueue ----
+    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
+    const uint8_t* src = base;
+    if (g->deform_stage == 1) {
+        GI_HIP(ctx, hipMemcpyAsync(g->d_vstage, base, bytes, hipMemcpyHostToDevice, stream));
+        src = (const uint8_t*)g->d_vstage;
+    }
+    hipLaunchKernelGGL(deform_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)src, n_ranges,
+                       (const float*)(src + head), lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
+                       const_cast<float*>(g->view.tangents), g->d_geom_epoch);
+    GI_HIP(ctx, hipGetLastError());
+    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
+    g->stage_used[slot] = true;
+    if (any_tris && n_slots) {
+        hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
+                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
+        if (any_attr)
+            hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
+                               reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
+                               (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->view.normals, g->view.tangents);
+        GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
     }
     GI_HIP(ctx, mark_rewrite(g, stream));
     return NEB_OK;

@@ -166,6 +166,7 @@ int gi_set_exact_shade(neb_ctx* ctx, int on);
 int gi_set_sun_table(neb_ctx* ctx, int on);
 int gi_set_sun_hints(neb_ctx* ctx, int n);
 int gi_set_sun_hold(neb_ctx* ctx, int n);
+int gi_set_deform_stage(neb_ctx* ctx, int mode);
 // option svgf_motion (gi.hip): the two per-slot transform tables and the delta table exist while the option is on and a scene is set
 int gi_motion_tables_alloc(neb_ctx* ctx); // NEB_OK also without a scene (nothing to allocate); forgets both snapshots
 void gi_motion_tables_free(neb_ctx* ctx);

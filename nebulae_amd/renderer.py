@@ -120,6 +120,36 @@ class DeferredRenderer:
         for k, gi in enumerate(idx):
             self._scene.geometries[int(gi)]["M"] = mats[k].copy()
 
+    # ---- no reference counterpart: its BLASes are built without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79) ----
+    def update_vertices(self, index, positions, normals=None, tangents=None, first_vertex=0, stream=None):
+        """Deform a submesh: vertices [first_vertex, first_vertex + len(positions)) of geometry `index` get new object-space positions
+        and, when given, normals (n x 3) and tangents (n x 4); the tree is refitted in place and the shading records follow
+        (neb_gi_update_vertices).  The renderer's scene object takes the same arrays (as copies), as update_transforms writes M."""
+        if self._scene is None:
+            raise NebError("update_vertices: no scene (init_pathtracer_scene first)")
+        index, first_vertex = int(index), int(first_vertex)
+        if not 0 <= index < len(self._scene.geometries) or not 0 <= first_vertex <= 0xFFFFFFFF:
+            raise NebError("update_vertices: geometry index or first vertex out of range")
+        arrays = {"positions": np.ascontiguousarray(np.asarray(positions, np.float32).reshape(-1, 3))}
+        n = arrays["positions"].shape[0]
+        for key, a, width in (("normals", normals, 3), ("tangents", tangents, 4)):
+            if a is not None:
+                arrays[key] = np.ascontiguousarray(np.asarray(a, np.float32).reshape(-1, width))
+                if arrays[key].shape[0] != n:
+                    raise NebError(f"update_vertices: {n} positions but {arrays[key].shape[0]} {key}")
+        u = _lib.VertexUpdate(geometry=index, firstVertex=first_vertex, numVertices=n)
+        for key, width in (("positions", 3), ("normals", 3), ("tangents", 4)):
+            if key in arrays:
+                setattr(u, key, arrays[key].ctypes.data)
+                setattr(u, key[:-1] + "Stride", 4 * width)
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        self._check(self._lib.neb_gi_update_vertices(self._ctx, C.byref(u), 1, st), "neb_gi_update_vertices")
+        gm = self._scene.geometries[index]
+        for key, a in arrays.items():  # (a fresh array: a Scene that shares its vertex streams with a clone does not deform the clone)
+            full = np.array(gm[key], np.float32, copy=True)
+            full[first_vertex:first_vertex + n] = a
+            gm[key] = full
+
     def scene_info(self):
         t, n = C.c_uint32(), C.c_uint32()
         self._check(self._lib.neb_gi_scene_info(self._ctx, C.byref(t), C.byref(n)), "neb_gi_scene_info")
