@@ -466,6 +466,32 @@ typedef struct neb_vertex_update {
     uint32_t tangentStride;
 } neb_vertex_update;
 int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream);
+/* neb_gi_update_vertices for a host that skins, simulates or blends on the GPU: the same entries, the same rewrite, the
+ * same ring, ordering and sun-table handling, but positions / normals / tangents are DEVICE pointers the context's GPU can read, strides
+ * in bytes.  The call only enqueues and never reads a vertex on the host: the sources are read in stream order on `stream`, so the caller
+ * orders `stream` behind whatever produced them and keeps them alive and unmodified until the stream has passed the update.
+ * What the host did per vertex runs on the device: deform_check_kernel validates every position (finite, and finite under the geometry's
+ * current matrix), the scatter reads the strided sources in place, and geom_box_kernel reduces the object- and world-space boxes of the
+ * touched submeshes over their referenced vertices.  {refusal word, boxes} come back in one small copy at the end of the chain; the host
+ * applies such records in call order when it next looks (any update call, neb_gi_update_status, neb_gi_scene_box, neb_gi_build_bvh) and,
+ * waiting, at the dispatch whose hold policy would build a sun table -- the table is built against the exact box, never an older one.
+ * Until then dispatches sort their work by the last known box (the keys only order work).
+ * A position that fails the check refuses the WHOLE call on the device: nothing is written, NEB_OK has long been returned, and
+ * neb_gi_update_status counts it (the sun table was dropped for nothing: harmless, frames do not depend on it).
+ * The host copy of the touched submeshes' positions is stale from here on: later updates of them (host-sourced ranges, transforms --
+ * checked by the corners of the object-space box alone) take their boxes from the device as well, and the next neb_gi_build_bvh reads
+ * the positions back first.
+ * Refusals at the call, each leaving everything unchanged: those of neb_gi_update_vertices except NEB_ERR_OUT_OF_RANGE, and
+ * NEB_ERR_INVALID_ARG for a pointer or stride that is not a multiple of 4 and for a pointer hipPointerGetAttributes does not report as
+ * memory of this context's device (or managed / mapped pinned memory), or whose range leaves its allocation. */
+int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream);
+/* out = {device-sourced updates accepted, refused on the device} since neb_gi_set_scene.  Waits for every outstanding result record and
+ * applies it first, so the counts include every neb_gi_update_vertices_device enqueued before the call. */
+int neb_gi_update_status(neb_ctx* ctx, uint64_t out[2]);
+/* The exact world-space box of the scene (the union of the submeshes' boxes over their referenced vertices), as the sun table's
+ * certificate uses it.  Waits for outstanding result records like neb_gi_update_status; without device-reduced updates it returns
+ * the box the host folded. */
+int neb_gi_scene_box(neb_ctx* ctx, float lo[3], float hi[3]);
 int neb_gi_scene_info(const neb_ctx* ctx, uint32_t* n_triangles, uint32_t* n_nodes);
 /* Device bytes of the scene: {texture footprint tables + material bundles, triangles + shading records, BVH nodes: the
  * builder's 128-byte nodes + the 64-byte quantised nodes the rays walk}. */

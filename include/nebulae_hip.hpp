@@ -149,6 +149,16 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_update_vertices(m_svgf.Context(), updates, n, commandList), "neb_gi_update_vertices");
         }
+        // ... the same with DEVICE pointers in the entries (a skinning or cloth kernel's output): read in stream order on commandList, never on the
+        // host; the caller orders commandList behind the producer and keeps the sources until the stream has passed the update
+        void UpdateVerticesDevice(const neb_vertex_update* updates, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_update_vertices_device(m_svgf.Context(), updates, n, commandList), "neb_gi_update_vertices_device");
+        }
+        // {device-sourced updates accepted, refused on the device}; waits for the updates enqueued so far
+        void UpdateStatus(uint64_t out[2]) { ThrowIfFailed(m_svgf.Context(), neb_gi_update_status(m_svgf.Context(), out), "neb_gi_update_status"); }
+        // the exact world-space box of the scene; waits like UpdateStatus
+        void SceneBox(float lo[3], float hi[3]) { ThrowIfFailed(m_svgf.Context(), neb_gi_scene_box(m_svgf.Context(), lo, hi), "neb_gi_scene_box"); }
         void SubmitCommandsGIPathtrace(const neb_gi_constants& globalConstants, neb_stream commandList)
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_trace(m_svgf.Context(), &globalConstants, commandList), "neb_gi_trace");

@@ -63,6 +63,13 @@ void gi_destroy(GiState* g)
     for (hipEvent_t& e : g->reader_ev)
         if (e)
             (void)hipEventDestroy(e);
+    for (hipEvent_t& e : g->result_ev)
+        if (e)
+            (void)hipEventDestroy(e);
+    if (g->h_result)
+        (void)hipHostFree(g->h_result);
+    if (g->h_box_list)
+        (void)hipHostFree(g->h_box_list);
     if (g->h_stage)
         (void)hipHostFree(g->h_stage);
     if (g->h_vstage)
@@ -1695,6 +1702,20 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
     const auto t_build0 = std::chrono::steady_clock::now(); // (the build ends with a stream synchronisation: wall time = device time + launches)
+    {   // device-sourced updates (gi_refit.hip): their boxes first, then the positions the device holds back into h_pos
+        GI_HIP(ctx, gi_harvest_results(g, true));
+        bool waited = false;
+        for (GiState::HostGeom& hg : g->h_geoms) {
+            if (!hg.host_stale)
+                continue;
+            if (!waited)
+                GI_HIP(ctx, hipDeviceSynchronize()); // (an update may have been enqueued on any stream)
+            waited = true;
+            if (hg.n_verts)
+                GI_HIP(ctx, hipMemcpy(&g->h_pos[3 * (size_t)hg.vertexBase], g->d_pos + 3 * (size_t)hg.vertexBase, 12 * (size_t)hg.n_verts, hipMemcpyDeviceToHost));
+            hg.host_stale = false;
+        }
+    }
     gi_rebake_host(g);
     if (g->n_tris == 0) { // empty scene: every ray misses
         g->built = true;

@@ -254,6 +254,7 @@ struct GiState {
         float world_lo[3] = {0, 0, 0}, world_hi[3] = {0, 0, 0}; // exact world-space box under the current transform
         float m[16] = {};                                    // surfaceToWorld as last set
         bool dirty = false;                                  // h_tris still holds the bake of an earlier transform
+        bool host_stale = false;                             // h_pos no longer holds the truth (neb_gi_update_vertices_device); cleared by a build
     };
     std::vector<HostGeom> h_geoms;
     std::vector<uint32_t> h_indices, h_ref_verts;
@@ -287,6 +288,28 @@ struct GiState {
     void* d_vstage = nullptr;         // "gi_deform_stage" = 1: the slot is copied here (one hipMemcpyAsync) and the scatter reads device memory
     size_t d_vstage_cap = 0;
     int deform_stage = 0;             // option "gi_deform_stage"
+    // ---- device-sourced deformation, boxes reduced on the device: neb_gi_update_vertices_device (gi_refit.hip) ----
+    // One source range of a device-sourced update, beside its DeformRange in the pinned slot: device pointers, strides in bytes.
+    struct DeformSource { const uint8_t *pos, *nrm, *tan; uint32_t pos_stride, nrm_stride, tan_stride, pad; };
+    // The boxes of a geometry whose h_pos is stale are reduced by geom_box_kernel over its referenced vertices: a device copy of
+    // h_ref_verts and of every geometry's {firstRef, n_refs}, uploaded by the first call that needs them.
+    uint32_t* d_ref_verts = nullptr;
+    uint2* d_ref_spans = nullptr;
+    // What such an update reports back, one slot of the ring per call: {call, refusal word, entries, 0} then 12 words per listed
+    // geometry -- keys of refit_ordered, the upper bounds complemented so that all twelve are reduced with atomicMin:
+    // {obj lo xyz, ~obj hi xyz, world lo xyz, ~world hi xyz}.  The chain ends with one copy d_result -> h_result and result_ev.
+    static constexpr uint32_t kResultHead = 4, kResultEntry = 12;
+    uint32_t* d_result = nullptr;     // [kStageSlots][kResultHead + kResultEntry * n_geoms]
+    uint32_t* h_result = nullptr;     // pinned, same layout
+    uint32_t* h_box_list = nullptr;   // pinned [kStageSlots][n_geoms]: the geometries of the slot's entries (geom_box_kernel reads it)
+    hipEvent_t result_ev[kStageSlots] = {nullptr, nullptr, nullptr, nullptr};
+    struct ResultRecord {
+        bool used = false;            // enqueued, not harvested yet
+        bool device_sourced = false;  // counts in neb_gi_update_status
+        uint32_t call = 0;
+        std::vector<uint32_t> geoms;  // entry e holds the boxes of geometry geoms[e]
+    } result_rec[kStageSlots];
+    uint64_t device_updates_accepted = 0, device_updates_refused = 0; // as harvested
     // Streams that have read triangles / nodes / geometry tables since the last update: an update on another stream orders itself
     // behind them (an event recorded on each, waited for on its own stream).  More than kReaderStreams: it waits for the device.
     static constexpr int kReaderStreams = 4;
@@ -301,6 +324,9 @@ hipError_t gi_sun_table_order(GiState* g, hipStream_t stream);
 hipError_t mark_rewrite(GiState* g, hipStream_t stream);
 hipError_t gi_quantise_nodes(const Bvh4Node* nodes, uint32_t n, Bvh4NodeQ* out, hipStream_t stream);
 void gi_rebake_host(GiState* g);
+// Applies the result records of finished updates in call order: boxes of the listed geometries, then the scene box.  block = false
+// stops at the first record whose event has not passed; block = true waits for every record of a call <= upto.
+hipError_t gi_harvest_results(GiState* g, bool block, uint32_t upto = 0xffffffffu);
 
 // Every entry point that reads triangles, nodes or the geometry tables on `stream` starts here: a rewrite enqueued on another stream
 // (sun table, neb_gi_update_transforms) comes first, and the stream is remembered for the next update to wait for.

@@ -10,6 +10,10 @@
 // (RTAccelerationStructureBuilder.cpp:79), so a deformed mesh means new BLASes there.  Here a deformation is the same refit with
 // another way in: new object-space vertices are scattered into the device pools, the stamped geometries are baked again by the
 // very rebake_kernel of the transform path, and the normal / tangent words of their 128-byte shading records are rewritten.
+//
+// neb_gi_update_vertices_device is that update with sources the host never reads: a check kernel validates them, the
+// scatter reads them where they lie, geom_box_kernel reduces the boxes the host used to fold from h_pos, and one small copy at the end
+// of the chain brings {refusal word, boxes} back to a pinned result record the host harvests later (gi_harvest_results).
 #include <algorithm>
 
 #include "gi_device.h"
@@ -87,13 +91,21 @@ __global__ void rebake_kernel(float4* __restrict__ tris, uint32_t n_slots, uint3
 // One lane per staged vertex: the compact streams of the update -> the object-space position pool and the normal / tangent pools.
 // The lane finds its range by bisection over first_lane (n ranges, ascending, none empty); lane 0 of a range stamps its geometry.
 // `stage` is the pinned slot itself or its device copy ("gi_deform_stage").
+// DEVICE_SRC: the vertices are not in the slot but where sources[range] points (strided device memory), and the whole launch leaves
+// at once when deform_check_kernel has set the call's refusal word -- nothing is written, no geometry is stamped, and every kernel
+// behind this one acts on stamped geometries only: a refused update is a no-op on the device.
+template <bool DEVICE_SRC>
 __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const float* __restrict__ data, uint32_t n_lanes,
                                       uint32_t n_pool, uint32_t n_geoms, uint32_t epoch, float* __restrict__ pos, float* __restrict__ normals,
-                                      float* __restrict__ tangents, uint32_t* __restrict__ geom_epoch)
+                                      float* __restrict__ tangents, uint32_t* __restrict__ geom_epoch,
+                                      const GiState::DeformSource* __restrict__ sources, const uint32_t* __restrict__ refused)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_lanes)
         return;
+    if constexpr (DEVICE_SRC)
+        if (*refused)
+            return;
     uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
@@ -107,16 +119,26 @@ __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ r
     if (j >= r.count || r.dst + j >= n_pool)
         return;
     const size_t v = (size_t)r.dst + j;
-    const float* sp = data + r.pos_off + 3 * (size_t)j;
+    const float *sp, *sn = nullptr, *st = nullptr;
+    if constexpr (DEVICE_SRC) {
+        const GiState::DeformSource s = sources[lo];
+        sp = reinterpret_cast<const float*>(s.pos + (size_t)j * s.pos_stride);
+        if (r.nrm_off != GiState::kNoStream)
+            sn = reinterpret_cast<const float*>(s.nrm + (size_t)j * s.nrm_stride);
+        if (r.tan_off != GiState::kNoStream)
+            st = reinterpret_cast<const float*>(s.tan + (size_t)j * s.tan_stride);
+    } else {
+        sp = data + r.pos_off + 3 * (size_t)j;
+        if (r.nrm_off != GiState::kNoStream)
+            sn = data + r.nrm_off + 3 * (size_t)j;
+        if (r.tan_off != GiState::kNoStream)
+            st = data + r.tan_off + 4 * (size_t)j;
+    }
     pos[3 * v] = sp[0], pos[3 * v + 1] = sp[1], pos[3 * v + 2] = sp[2];
-    if (r.nrm_off != GiState::kNoStream) {
-        const float* sn = data + r.nrm_off + 3 * (size_t)j;
+    if (sn)
         normals[3 * v] = sn[0], normals[3 * v + 1] = sn[1], normals[3 * v + 2] = sn[2];
-    }
-    if (r.tan_off != GiState::kNoStream) {
-        const float* st = data + r.tan_off + 4 * (size_t)j;
+    if (st)
         tangents[4 * v] = st[0], tangents[4 * v + 1] = st[1], tangents[4 * v + 2] = st[2], tangents[4 * v + 3] = st[3];
-    }
     if (j == 0 && r.geom < n_geoms)
         geom_epoch[r.geom] = epoch;
 }
@@ -155,6 +177,100 @@ __device__ __forceinline__ float refit_min(float a, float b) { return refit_orde
 __device__ __forceinline__ float refit_max(float a, float b) { return refit_ordered(b) > refit_ordered(a) ? b : a; }
 __device__ __forceinline__ float refit_min4(const float4 v) { return refit_min(refit_min(v.x, v.y), refit_min(v.z, v.w)); }
 __device__ __forceinline__ float refit_max4(const float4 v) { return refit_max(refit_max(v.x, v.y), refit_max(v.z, v.w)); }
+
+// One lane per source vertex of a device-sourced update, the bisection of deform_scatter_kernel: what neb_gi_update_vertices checks
+// on the host -- the position is finite, and finite under the geometry's current matrix (bake_point's products, gi_bake_point's bound).
+// A failing lane sets the call's refusal word.
+__global__ void deform_check_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::DeformSource* __restrict__ sources,
+                                    uint32_t n_lanes, uint32_t n_geoms, const float* __restrict__ xf, uint32_t* __restrict__ refused)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    uint32_t lo = 0, hi = n_ranges;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[mid].first_lane <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const GiState::DeformRange r = ranges[lo];
+    const uint32_t j = k - r.first_lane;
+    if (j >= r.count || r.geom >= n_geoms)
+        return;
+    const GiState::DeformSource s = sources[lo];
+    const float* sp = reinterpret_cast<const float*>(s.pos + (size_t)j * s.pos_stride);
+    const float a[3] = {sp[0], sp[1], sp[2]};
+    const float3 w = bake_point(xf + 16 * (size_t)r.geom, a);
+    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
+                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
+    if (!ok)
+        atomicOr(refused, 1u);
+}
+
+// the result record of a call before its chain: {call, refusal word = 0, entries, 0}, every box word at the neutral element of atomicMin
+__global__ void result_init_kernel(uint32_t* __restrict__ res, uint32_t call, uint32_t n_entries)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < GiState::kResultHead + GiState::kResultEntry * n_entries)
+        res[i] = i == 0 ? call : i == 2 ? n_entries : i < GiState::kResultHead ? 0u : 0xffffffffu;
+}
+
+// The boxes of the listed geometries over their REFERENCED vertices (a vertex no triangle names is no part of the scene): an entry
+// owns `per_entry` consecutive blocks of the one-dimensional grid (no limit of 65535 entries as gridDim.y would set), the lanes of its
+// blocks stride over the geometry's referenced vertices, object space as stored and world space by bake_point under the current matrix.  The wave folds its 12 keys (refit_ordered; an upper bound as its complement, so that every
+// fold is a min) with __shfl_xor, and lane 0 issues one atomicMin per component: 12 atomics per wave, not per lane.
+__global__ __launch_bounds__(256) void geom_box_kernel(const uint32_t* __restrict__ list, uint32_t n_entries, uint32_t n_geoms,
+                                                       const uint2* __restrict__ ref_spans, const uint32_t* __restrict__ ref_verts, uint32_t n_ref_verts,
+                                                       const DevGeom* __restrict__ geoms, const float* __restrict__ pos, uint32_t n_pool,
+                                                       const float* __restrict__ xf, uint32_t* __restrict__ entries, uint32_t per_entry)
+{
+    const uint32_t e = blockIdx.x / per_entry, block = blockIdx.x - e * per_entry;
+    if (e >= n_entries)
+        return;
+    const uint32_t gi = list[e];
+    if (gi >= n_geoms)
+        return;
+    const uint2 span = ref_spans[gi];
+    const uint32_t vb = geoms[gi].vertexBase;
+    const float* m = xf + 16 * (size_t)gi;
+    uint32_t key[GiState::kResultEntry];
+#pragma unroll
+    for (int q = 0; q < (int)GiState::kResultEntry; ++q)
+        key[q] = 0xffffffffu;
+    bool any = false;
+    for (uint32_t r = block * blockDim.x + threadIdx.x; r < span.y; r += per_entry * blockDim.x) {
+        if ((uint64_t)span.x + r >= n_ref_verts)
+            break;
+        const size_t v = (size_t)vb + ref_verts[span.x + r];
+        if (v >= n_pool)
+            continue;
+        const float a[3] = {pos[3 * v], pos[3 * v + 1], pos[3 * v + 2]};
+        const float3 w3 = bake_point(m, a);
+        const float w[3] = {w3.x, w3.y, w3.z};
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            const uint32_t ka = refit_ordered(a[q]), kw = refit_ordered(w[q]);
+            key[q] = min(key[q], ka), key[3 + q] = min(key[3 + q], ~ka);
+            key[6 + q] = min(key[6 + q], kw), key[9 + q] = min(key[9 + q], ~kw);
+        }
+        any = true;
+    }
+    if (__ballot(any) == 0ull)
+        return; // (wave-uniform)
+#pragma unroll
+    for (int q = 0; q < (int)GiState::kResultEntry; ++q) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1)
+            key[q] = min(key[q], (uint32_t)__shfl_xor((int)key[q], off));
+    }
+    if ((threadIdx.x & 63u) == 0) {
+#pragma unroll
+        for (int q = 0; q < (int)GiState::kResultEntry; ++q)
+            atomicMin(entries + GiState::kResultEntry * (size_t)e + q, key[q]);
+    }
+}
 
 // One level of the tree, four lanes per node, one per child slot.  A leaf one of whose triangles moved takes the exact bounds of
 // its triangles -- the whole triangle also where the slot holds a clipped reference of the splitting pass: conservative.  An inner
@@ -249,6 +365,183 @@ static hipError_t refit_enqueue_levels(GiState* g, uint32_t call, hipStream_t st
     return gi_quantise_nodes(g->view.nodes, g->n_nodes, const_cast<Bvh4NodeQ*>(g->view.qnodes), stream);
 }
 
+// ---- boxes reduced on the device, result records ----
+static float refit_unordered(uint32_t k) // the float whose refit_ordered key is k
+{
+    const uint32_t u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+static size_t result_stride(const GiState* g) { return GiState::kResultHead + (size_t)GiState::kResultEntry * g->n_geoms; }
+
+hipError_t gi_harvest_results(GiState* g, bool block, uint32_t upto)
+{
+    for (;;) {
+        int s = -1;
+        for (int q = 0; q < GiState::kStageSlots; ++q)
+            if (g->result_rec[q].used && (s < 0 || g->result_rec[q].call < g->result_rec[s].call))
+                s = q;
+        if (s < 0 || g->result_rec[s].call > upto)
+            return hipSuccess;
+        GiState::ResultRecord& rec = g->result_rec[s];
+        if (block) {
+            if (hipError_t e = hipEventSynchronize(g->result_ev[s]); e != hipSuccess)
+                return e;
+        } else {
+            const hipError_t q = hipEventQuery(g->result_ev[s]);
+            if (q == hipErrorNotReady) {
+                (void)hipGetLastError(); // (an answer, not a failure)
+                return hipSuccess;
+            }
+            if (q != hipSuccess)
+                return q;
+        }
+        const uint32_t* h = g->h_result + (size_t)s * result_stride(g);
+        const bool refused = h[1] != 0u;
+        if (rec.device_sourced)
+            ++(refused ? g->device_updates_refused : g->device_updates_accepted);
+        if (!refused) { // (a refused update wrote nothing: every box stays)
+            for (size_t e = 0; e < rec.geoms.size(); ++e) {
+                GiState::HostGeom& hg = g->h_geoms[rec.geoms[e]];
+                const uint32_t* k = h + GiState::kResultHead + GiState::kResultEntry * e;
+                for (int q = 0; q < 3; ++q) {
+                    hg.obj_lo[q] = refit_unordered(k[q]), hg.obj_hi[q] = refit_unordered(~k[3 + q]);
+                    hg.world_lo[q] = refit_unordered(k[6 + q]), hg.world_hi[q] = refit_unordered(~k[9 + q]);
+                }
+            }
+            if (!rec.geoms.empty())
+                refit_scene_box(g);
+        }
+        rec.used = false;
+        rec.geoms.clear();
+    }
+}
+
+// what the first device-reduced update allocates: the device copy of the referenced-vertex lists, the result ring, the entry lists
+static hipError_t results_prepare(GiState* g)
+{
+    if (g->d_result)
+        return hipSuccess;
+    if (g->n_geoms > 0x7fffffffu) // (geom_box_kernel: at least one block per entry in a one-dimensional grid)
+        return hipErrorInvalidValue;
+    if (!g->d_ref_spans) {
+        std::vector<uint2> spans(g->n_geoms);
+        for (uint32_t gi = 0; gi < g->n_geoms; ++gi)
+            spans[gi] = make_uint2(g->h_geoms[gi].firstRef, g->h_geoms[gi].n_refs);
+        const uint2* d_spans = nullptr;
+        const uint32_t* d_refs = nullptr;
+        if (hipError_t e = upload(g, spans, &d_spans); e != hipSuccess)
+            return e;
+        g->d_ref_spans = const_cast<uint2*>(d_spans);
+        if (hipError_t e = upload(g, g->h_ref_verts, &d_refs); e != hipSuccess)
+            return e;
+        g->d_ref_verts = const_cast<uint32_t*>(d_refs);
+    }
+    const size_t bytes = GiState::kStageSlots * result_stride(g) * sizeof(uint32_t);
+    if (!g->h_result)
+        if (hipError_t e = hipHostMalloc((void**)&g->h_result, bytes, hipHostMallocDefault); e != hipSuccess)
+            return e;
+    if (!g->h_box_list)
+        if (hipError_t e = hipHostMalloc((void**)&g->h_box_list, (size_t)GiState::kStageSlots * g->n_geoms * sizeof(uint32_t), hipHostMallocDefault); e != hipSuccess)
+            return e;
+    void* d = nullptr;
+    if (hipError_t e = hipMalloc(&d, bytes); e != hipSuccess)
+        return e;
+    g->allocs.push_back(d);
+    g->d_result = (uint32_t*)d;
+    return hipSuccess;
+}
+// the slot's record of kStageSlots calls ago is applied before the slot is written again (long done unless the host runs that far ahead)
+static hipError_t results_acquire(GiState* g, int slot)
+{
+    if (!g->result_ev[slot])
+        if (hipError_t e = hipEventCreateWithFlags(&g->result_ev[slot], hipEventDisableTiming); e != hipSuccess)
+            return e;
+    return g->result_rec[slot].used ? gi_harvest_results(g, true, g->result_rec[slot].call) : hipSuccess;
+}
+static hipError_t results_enqueue_init(GiState* g, int slot, uint32_t call, uint32_t n_entries, hipStream_t stream)
+{
+    const uint32_t words = GiState::kResultHead + GiState::kResultEntry * n_entries;
+    hipLaunchKernelGGL(result_init_kernel, dim3((words + 255) / 256), dim3(256), 0, stream, g->d_result + (size_t)slot * result_stride(g), call, n_entries);
+    return hipGetLastError();
+}
+// geom_box_kernel over the slot's entry list (entry e = geometry h_box_list[slot][e]), about eight vertices per lane
+static hipError_t results_enqueue_boxes(GiState* g, int slot, uint32_t n_entries, hipStream_t stream)
+{
+    if (!n_entries)
+        return hipSuccess;
+    const uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
+    uint32_t most = 1;
+    for (uint32_t e = 0; e < n_entries; ++e)
+        most = std::max(most, g->h_geoms[list[e]].n_refs);
+    // blocks per entry, by the largest geometry (the blocks of a smaller one leave on the ballot); fewer where the grid would pass 2^31 - 1
+    // blocks: the lanes stride, any count from 1 up covers every vertex (n_entries <= n_geoms < 2^31: results_prepare)
+    const uint32_t per_entry = std::max(1u, std::min((most + 2047u) / 2048u, 0x7fffffffu / n_entries));
+    hipLaunchKernelGGL(geom_box_kernel, dim3(per_entry * n_entries), dim3(256), 0, stream, list, n_entries, g->n_geoms, (const uint2*)g->d_ref_spans,
+                       (const uint32_t*)g->d_ref_verts, (uint32_t)g->h_ref_verts.size(), g->view.geoms, (const float*)g->d_pos, (uint32_t)(g->h_pos.size() / 3),
+                       (const float*)g->d_xf, g->d_result + (size_t)slot * result_stride(g) + GiState::kResultHead, per_entry);
+    return hipGetLastError();
+}
+// the end of the chain: the record comes back to the pinned slot, the event says when
+static hipError_t results_enqueue_readback(GiState* g, int slot, uint32_t call, bool device_sourced, hipStream_t stream)
+{
+    GiState::ResultRecord& rec = g->result_rec[slot];
+    const size_t words = GiState::kResultHead + GiState::kResultEntry * rec.geoms.size();
+    if (hipError_t e = hipMemcpyAsync(g->h_result + (size_t)slot * result_stride(g), g->d_result + (size_t)slot * result_stride(g), words * sizeof(uint32_t),
+                                      hipMemcpyDeviceToHost, stream);
+        e != hipSuccess)
+        return e;
+    rec.used = true, rec.device_sourced = device_sourced, rec.call = call;
+    return hipEventRecord(g->result_ev[slot], stream);
+}
+
+// A source of neb_gi_update_vertices_device: `bytes` from p must be memory this context's device reads at the very address p --
+// device memory of this device (and then inside its allocation), managed memory, or pinned host memory mapped at its own address.
+static bool device_readable(const neb_ctx* ctx, const void* p, size_t bytes)
+{
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError(); // (how the runtime answers for plain host memory)
+        return false;
+    }
+    if (at.type == hipMemoryTypeDevice) {
+        if (at.device != ctx->device)
+            return false;
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)const_cast<void*>(p)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false; // (no allocation to check the range against: refused rather than trusted)
+        }
+        return (uintptr_t)p + bytes <= (uintptr_t)base + size;
+    }
+    if (at.type == hipMemoryTypeManaged)
+        return true;
+    return at.type == hipMemoryTypeHost && at.devicePointer == p;
+}
+
+// order: behind the last rewrite, and behind every stream that may still be reading what is about to be rewritten
+static int refit_order_behind_readers(neb_ctx* ctx, GiState* g, hipStream_t stream)
+{
+    GI_HIP(ctx, gi_sun_table_order(g, stream));
+    if (g->reader_overflow) {
+        GI_HIP(ctx, hipDeviceSynchronize());
+    } else {
+        for (int k = 0; k < g->n_reader_streams; ++k) {
+            if (g->reader_streams[k] == stream)
+                continue;
+            if (!g->reader_ev[k])
+                GI_HIP(ctx, hipEventCreateWithFlags(&g->reader_ev[k], hipEventDisableTiming));
+            GI_HIP(ctx, hipEventRecord(g->reader_ev[k], g->reader_streams[k]));
+            GI_HIP(ctx, hipStreamWaitEvent(stream, g->reader_ev[k], 0));
+        }
+    }
+    g->n_reader_streams = 0;
+    g->reader_overflow = false;
+    return NEB_OK;
+}
+
 } // namespace neb
 
 using namespace neb;
@@ -268,6 +561,7 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_transforms: null pointer");
     if (n > g->n_geoms)
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_transforms: more entries than geometries (an index is out of range or named twice)");
+    GI_HIP(ctx, gi_harvest_results(g, false));
     // ---- everything that can refuse the call comes before anything changes ----
     const uint32_t call = g->epoch + 1u;
     const uint32_t stamp = ++g->seen_stamp; // (one per call, accepted or not: h_seen needs no clearing)
@@ -278,6 +572,18 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         if (g->h_seen[gi] == stamp)
             return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_transforms: a geometry is named twice");
         g->h_seen[gi] = stamp;
+    }
+    // A geometry whose h_pos is stale (neb_gi_update_vertices_device) is checked by the corners of its object-space box alone -- current
+    // once every record has been harvested -- and takes its world box from geom_box_kernel and a result record, not from a host walk.
+    bool any_stale = false;
+    for (uint32_t k = 0; k < n; ++k)
+        any_stale = any_stale || g->h_geoms[geometry_indices[k]].host_stale;
+    if (any_stale) {
+        neb::DeviceGuard guard(ctx->device);
+        if (guard.err != hipSuccess)
+            return gi_fail(ctx, NEB_ERR_HIP, "hipSetDevice", guard.err);
+        GI_HIP(ctx, gi_harvest_results(g, true));
+        GI_HIP(ctx, results_prepare(g));
     }
     struct Box { float lo[3], hi[3]; };
     std::vector<Box> boxes(n);
@@ -304,7 +610,7 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         return NEB_OK; // every matrix is the one already set: nothing moves, nothing is enqueued, the sun table stays
     // the exact world-space box of every moved geometry: its referenced vertices in the bake's own arithmetic
     for (uint32_t k = 0; k < n; ++k) {
-        if (!changed[k])
+        if (!changed[k] || g->h_geoms[geometry_indices[k]].host_stale)
             continue;
         const GiState::HostGeom& hg = g->h_geoms[geometry_indices[k]];
         const float* m = surfaceToWorld + 16 * (size_t)k;
@@ -329,27 +635,16 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
     if (g->stage_used[slot])
         GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
-    // ---- order: behind the last rewrite, and behind every stream that may still be reading what is about to be rewritten ----
-    GI_HIP(ctx, gi_sun_table_order(g, stream));
-    if (g->reader_overflow) {
-        GI_HIP(ctx, hipDeviceSynchronize());
-    } else {
-        for (int k = 0; k < g->n_reader_streams; ++k) {
-            if (g->reader_streams[k] == stream)
-                continue;
-            if (!g->reader_ev[k])
-                GI_HIP(ctx, hipEventCreateWithFlags(&g->reader_ev[k], hipEventDisableTiming));
-            GI_HIP(ctx, hipEventRecord(g->reader_ev[k], g->reader_streams[k]));
-            GI_HIP(ctx, hipStreamWaitEvent(stream, g->reader_ev[k], 0));
-        }
-    }
-    g->n_reader_streams = 0;
-    g->reader_overflow = false;
+    if (any_stale)
+        GI_HIP(ctx, results_acquire(g, slot));
+    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+        return rc;
     // ---- commit the host side ----
     g->epoch = call;
     GiState::StageEntry* st = g->h_stage + (size_t)slot * g->n_geoms;
     uint32_t ns = 0;
     bool any_tris = false;
+    std::vector<uint32_t> boxed; // the stale geometries among the moved ones: entries of this call's result record
     for (uint32_t k = 0; k < n; ++k) {
         if (!changed[k])
             continue;
@@ -363,16 +658,24 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         if (hg.n_tris) {
             hg.dirty = true;
             any_tris = true;
-            memcpy(hg.world_lo, boxes[k].lo, 12);
-            memcpy(hg.world_hi, boxes[k].hi, 12);
+            if (hg.host_stale) {
+                boxed.push_back(gi);
+            } else {
+                memcpy(hg.world_lo, boxes[k].lo, 12);
+                memcpy(hg.world_hi, boxes[k].hi, 12);
+            }
         }
     }
+    if (!boxed.empty())
+        memcpy(g->h_box_list + (size_t)slot * g->n_geoms, boxed.data(), boxed.size() * sizeof(uint32_t));
     if (any_tris) {
         refit_scene_box(g);
         refit_drop_sun_table(g);
     }
     // ---- enqueue ----
     const uint32_t n_slots = g->view.n_tris;
+    if (!boxed.empty())
+        GI_HIP(ctx, results_enqueue_init(g, slot, call, (uint32_t)boxed.size(), stream));
     hipLaunchKernelGGL(refit_apply_kernel, dim3((ns + 63) / 64), dim3(64), 0, stream, (const GiState::StageEntry*)st, ns, g->n_geoms, call, g->d_xf,
                        const_cast<DevGeom*>(g->view.geoms), const_cast<ShadeHeader*>(g->shade_heads), g->d_geom_epoch);
     GI_HIP(ctx, hipGetLastError());
@@ -381,7 +684,12 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
     if (any_tris && n_slots) {
         hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
                            (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
+        GI_HIP(ctx, results_enqueue_boxes(g, slot, (uint32_t)boxed.size(), stream));
         GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
+    }
+    if (!boxed.empty()) {
+        g->result_rec[slot].geoms = std::move(boxed);
+        GI_HIP(ctx, results_enqueue_readback(g, slot, call, false, stream));
     }
     GI_HIP(ctx, mark_rewrite(g, stream));
     return NEB_OK;
@@ -398,6 +706,7 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         return NEB_OK;
     if (!updates)
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: null pointer");
+    GI_HIP(ctx, gi_harvest_results(g, false));
     // ---- everything that can refuse the call comes before anything changes ----
     struct Span { uint32_t geom, first, count, k; };
     std::vector<Span> spans;
@@ -445,6 +754,13 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         return NEB_OK; // every range is empty: nothing moves, nothing is enqueued, the sun table stays
     hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
+    // the touched geometries whose h_pos is stale (neb_gi_update_vertices_device): their boxes come from geom_box_kernel and a result record
+    std::vector<uint32_t> boxed;
+    for (size_t i = 0; i < spans.size(); ++i)
+        if ((!i || spans[i].geom != spans[i - 1].geom) && g->h_geoms[spans[i].geom].host_stale && g->h_geoms[spans[i].geom].n_tris)
+            boxed.push_back(spans[i].geom);
+    if (!boxed.empty())
+        GI_HIP(ctx, results_prepare(g));
     // ---- the staging slot: pinned host memory, {ranges | positions | normals | tangents}, grown to the largest update seen ----
     const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
     const size_t bytes = head + 4u * (3u * n_lanes + 3u * n_nrm + 4u * n_tan);
@@ -474,22 +790,10 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
     if (g->stage_used[slot])
         GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
-    // ---- order: behind the last rewrite, and behind every stream that may still be reading what is about to be rewritten ----
-    GI_HIP(ctx, gi_sun_table_order(g, stream));
-    if (g->reader_overflow) {
-        GI_HIP(ctx, hipDeviceSynchronize());
-    } else {
-        for (int k = 0; k < g->n_reader_streams; ++k) {
-            if (g->reader_streams[k] == stream)
-                continue;
-            if (!g->reader_ev[k])
-                GI_HIP(ctx, hipEventCreateWithFlags(&g->reader_ev[k], hipEventDisableTiming));
-            GI_HIP(ctx, hipEventRecord(g->reader_ev[k], g->reader_streams[k]));
-            GI_HIP(ctx, hipStreamWaitEvent(stream, g->reader_ev[k], 0));
-        }
-    }
-    g->n_reader_streams = 0;
-    g->reader_overflow = false;
+    if (!boxed.empty())
+        GI_HIP(ctx, results_acquire(g, slot));
+    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+        return rc;
     // ---- commit the host side: the slot, h_pos, the boxes ----
     g->epoch = call;
     uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
@@ -531,7 +835,7 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         if (i && spans[i].geom == spans[i - 1].geom)
             continue;
         GiState::HostGeom& hg = g->h_geoms[spans[i].geom];
-        if (!hg.n_tris)
+        if (!hg.n_tris || hg.host_stale)
             continue;
         for (int q = 0; q < 3; ++q) {
             hg.obj_lo[q] = hg.world_lo[q] = 3.4e38f;
@@ -556,13 +860,17 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
     // ---- enqueue ----
     const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
     const uint8_t* src = base;
+    if (!boxed.empty()) {
+        memcpy(g->h_box_list + (size_t)slot * g->n_geoms, boxed.data(), boxed.size() * sizeof(uint32_t));
+        GI_HIP(ctx, results_enqueue_init(g, slot, call, (uint32_t)boxed.size(), stream));
+    }
     if (g->deform_stage == 1) {
         GI_HIP(ctx, hipMemcpyAsync(g->d_vstage, base, bytes, hipMemcpyHostToDevice, stream));
         src = (const uint8_t*)g->d_vstage;
     }
-    hipLaunchKernelGGL(deform_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)src, n_ranges,
+    hipLaunchKernelGGL(deform_scatter_kernel<false>, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)src, n_ranges,
                        (const float*)(src + head), lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
-                       const_cast<float*>(g->view.tangents), g->d_geom_epoch);
+                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)nullptr, (const uint32_t*)nullptr);
     GI_HIP(ctx, hipGetLastError());
     GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
     g->stage_used[slot] = true;
@@ -573,9 +881,182 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
             hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
                                reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
                                (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->view.normals, g->view.tangents);
+        GI_HIP(ctx, results_enqueue_boxes(g, slot, (uint32_t)boxed.size(), stream));
         GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
     }
+    if (!boxed.empty()) {
+        g->result_rec[slot].geoms = std::move(boxed);
+        GI_HIP(ctx, results_enqueue_readback(g, slot, call, false, stream));
+    }
     GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_update_vertices_device: no built scene (neb_gi_set_scene + neb_gi_build_bvh first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!updates)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: null pointer");
+    GI_HIP(ctx, gi_harvest_results(g, false));
+    // ---- everything the HOST can refuse the call for comes before anything changes (the vertices themselves: deform_check_kernel) ----
+    struct Span { uint32_t geom, first, count, k; };
+    std::vector<Span> spans;
+    spans.reserve(n);
+    size_t n_lanes = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_vertex_update& u = updates[k];
+        if (!u.positions)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: null positions");
+        if (u.geometry >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: geometry index out of range");
+        const GiState::HostGeom& hg = g->h_geoms[u.geometry];
+        if ((uint64_t)u.firstVertex + u.numVertices > hg.n_verts)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: vertex range beyond the geometry's numVertices");
+        if ((u.normals || u.tangents) && !hg.valid)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: normals or tangents for a geometry that was set without its attribute streams");
+        if (u.positionStride < 12u || (u.normals && u.normalStride < 12u) || (u.tangents && u.tangentStride < 16u))
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: a stride is smaller than its element");
+        if ((((uintptr_t)u.positions | u.positionStride) & 3u) || (u.normals && (((uintptr_t)u.normals | u.normalStride) & 3u)) ||
+            (u.tangents && (((uintptr_t)u.tangents | u.tangentStride) & 3u)))
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: a pointer or a stride is not a multiple of 4");
+        if (u.numVertices == 0)
+            continue;
+        spans.push_back({u.geometry, u.firstVertex, u.numVertices, k});
+        n_lanes += u.numVertices;
+    }
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom != b.geom ? a.geom < b.geom : a.first < b.first; });
+    for (size_t i = 1; i < spans.size(); ++i)
+        if (spans[i].geom == spans[i - 1].geom && (uint64_t)spans[i - 1].first + spans[i - 1].count > spans[i].first)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: two ranges of one geometry overlap");
+    if (n_lanes > 0xffffffffull / 10u) // (the bound of neb_gi_update_vertices: lanes are 32-bit)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: too many vertices in one call");
+    if (spans.empty())
+        return NEB_OK; // every range is empty: nothing moves, nothing is enqueued, the sun table stays
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    for (const Span& sp : spans) { // a host pointer handed in by mistake would fault the device: every source is looked up first
+        const neb_vertex_update& u = updates[sp.k];
+        const size_t last = (size_t)sp.count - 1u;
+        if (!device_readable(ctx, u.positions, last * u.positionStride + 12u) || (u.normals && !device_readable(ctx, u.normals, last * u.normalStride + 12u)) ||
+            (u.tangents && !device_readable(ctx, u.tangents, last * u.tangentStride + 16u)))
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: a source is not memory this context's device can read (or the range leaves its allocation)");
+    }
+    GI_HIP(ctx, results_prepare(g));
+    // ---- the staging slot: pinned host memory, here {ranges | sources} only ----
+    const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
+    const size_t bytes = head + spans.size() * sizeof(GiState::DeformSource);
+    if (bytes > g->vstage_cap) {
+        for (int q = 0; q < GiState::kStageSlots; ++q) // (growing frees the ring: every update that may still read it has to be done)
+            if (g->stage_used[q])
+                GI_HIP(ctx, hipEventSynchronize(g->stage_ev[q]));
+        void* fresh = nullptr;
+        const size_t cap = (bytes + 4095u) & ~(size_t)4095u;
+        GI_HIP(ctx, hipHostMalloc(&fresh, cap * GiState::kStageSlots, hipHostMallocDefault));
+        if (g->h_vstage)
+            (void)hipHostFree(g->h_vstage);
+        g->h_vstage = fresh;
+        g->vstage_cap = cap;
+    }
+    const uint32_t call = g->epoch + 1u;
+    const int slot = (int)(call % (uint32_t)GiState::kStageSlots);
+    if (!g->stage_ev[slot])
+        GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
+    if (g->stage_used[slot])
+        GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
+    GI_HIP(ctx, results_acquire(g, slot));
+    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+        return rc;
+    // ---- commit the host side: the slot; h_pos is left behind (host_stale), the boxes follow with the result record ----
+    g->epoch = call;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    GiState::DeformRange* ranges = (GiState::DeformRange*)base;
+    GiState::DeformSource* sources = (GiState::DeformSource*)(base + head);
+    uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
+    GiState::ResultRecord& rec = g->result_rec[slot];
+    rec.geoms.clear();
+    uint32_t lane = 0;
+    bool any_tris = false, any_attr = false;
+    for (size_t i = 0; i < spans.size(); ++i) {
+        const Span& sp = spans[i];
+        const neb_vertex_update& u = updates[sp.k];
+        GiState::HostGeom& hg = g->h_geoms[sp.geom];
+        GiState::DeformRange& r = ranges[i];
+        r.first_lane = lane, r.count = sp.count, r.dst = hg.vertexBase + sp.first, r.geom = sp.geom, r.pad = 0;
+        r.pos_off = 0;
+        r.nrm_off = u.normals ? 0u : GiState::kNoStream; // (device sources: only "has the stream" is read)
+        r.tan_off = u.tangents ? 0u : GiState::kNoStream;
+        sources[i] = {(const uint8_t*)u.positions, (const uint8_t*)u.normals, (const uint8_t*)u.tangents, u.positionStride, u.normalStride, u.tangentStride, 0u};
+        lane += sp.count;
+        any_attr = any_attr || u.normals || u.tangents;
+        hg.host_stale = true;
+        if (hg.n_tris) {
+            hg.dirty = true;
+            any_tris = true;
+            if (rec.geoms.empty() || rec.geoms.back() != sp.geom) {
+                list[rec.geoms.size()] = sp.geom;
+                rec.geoms.push_back(sp.geom);
+            }
+        }
+    }
+    if (any_tris)
+        refit_drop_sun_table(g);
+    // ---- enqueue: check, scatter, bake, records, boxes, levels, quantise, the record back ----
+    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3), n_boxed = (uint32_t)rec.geoms.size();
+    uint32_t* d_res = g->d_result + (size_t)slot * result_stride(g);
+    GI_HIP(ctx, results_enqueue_init(g, slot, call, n_boxed, stream));
+    hipLaunchKernelGGL(deform_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)ranges, n_ranges,
+                       (const GiState::DeformSource*)sources, lane, g->n_geoms, (const float*)g->d_xf, d_res + 1);
+    hipLaunchKernelGGL(deform_scatter_kernel<true>, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)ranges, n_ranges,
+                       (const float*)nullptr, lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
+                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)sources, (const uint32_t*)(d_res + 1));
+    GI_HIP(ctx, hipGetLastError());
+    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
+    g->stage_used[slot] = true;
+    if (any_tris && n_slots) {
+        hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
+                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
+        if (any_attr)
+            hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
+                               reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
+                               (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->view.normals, g->view.tangents);
+        GI_HIP(ctx, results_enqueue_boxes(g, slot, n_boxed, stream));
+        GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
+    }
+    GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
+    GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+int neb_gi_update_status(neb_ctx* ctx, uint64_t out[2])
+{
+    if (!ctx || !out)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_update_status: no scene (call neb_gi_set_scene first)");
+    GI_GUARD(ctx);
+    GI_HIP(ctx, gi_harvest_results(g, true));
+    out[0] = g->device_updates_accepted, out[1] = g->device_updates_refused;
+    return NEB_OK;
+}
+
+int neb_gi_scene_box(neb_ctx* ctx, float lo[3], float hi[3])
+{
+    if (!ctx || !lo || !hi)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_scene_box: no scene (call neb_gi_set_scene first)");
+    GI_GUARD(ctx);
+    GI_HIP(ctx, gi_harvest_results(g, true));
+    memcpy(lo, g->scene_min, 12);
+    memcpy(hi, g->scene_max, 12);
     return NEB_OK;
 }
 

@@ -558,6 +558,10 @@ hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_
         if (++g->sun_seen < g->sun_hold)
             return hipSuccess;
     }
+    // A table is about to be built (or refused for the scene's size): the scene box has to be the exact one.  Boxes of updates reduced on
+    // the device (gi_refit.hip) arrive in result records; the last one was enqueued sun_hold dispatches ago, so this wait is short.
+    if (hipError_t eh = gi_harvest_results(g, true); eh != hipSuccess)
+        return eh;
     const float dd = key[0] * key[0] + key[1] * key[1] + key[2] * key[2];
     // The certificate's slack grows with the scene's coordinates (lit_predicate.h: an ulp there is what fp32 hit points and triangle tests
     // can be off by) while the ray offset stays 1e-2: past +-218 units the slack would eat a quarter of the offset and nothing could be proven

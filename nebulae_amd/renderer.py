@@ -150,6 +150,69 @@ class DeferredRenderer:
             full[first_vertex:first_vertex + n] = a
             gm[key] = full
 
+    def update_vertices_device(self, index, positions, normals=None, tangents=None, first_vertex=0, stream=None, mirror=True):
+        """update_vertices with sources in device memory (neb_gi_update_vertices_device): float32 torch tensors on this renderer's
+        device, n x 3 positions and, when given, n x 3 normals and n x 4 tangents.  A strided view is read where it lies (its row stride
+        goes to the library; the elements of a row must be contiguous): no hidden copy.  The call only enqueues; the sources are read in
+        stream order, so `stream` has to be ordered behind whatever wrote them and they must stay untouched until the stream has passed
+        the update (the caller keeps them alive, e.g. with Tensor.record_stream).  A position that is not finite is refused on the
+        device, later: see update_status.  mirror=True: the renderer's scene object follows from a .cpu() copy made after the enqueue
+        -- only if the device accepted the update, so the scene object never holds positions the library refused (the call waits for
+        the updates before it and for its own: for hosts that use the scene's G-buffer and oracle helpers); mirror=False: the scene
+        object keeps its arrays and nothing waits."""
+        if self._scene is None:
+            raise NebError("update_vertices_device: no scene (init_pathtracer_scene first)")
+        index, first_vertex = int(index), int(first_vertex)
+        if not 0 <= index < len(self._scene.geometries) or not 0 <= first_vertex <= 0xFFFFFFFF:
+            raise NebError("update_vertices_device: geometry index or first vertex out of range")
+        import torch
+        tensors = {"positions": positions}
+        if normals is not None:
+            tensors["normals"] = normals
+        if tangents is not None:
+            tensors["tangents"] = tangents
+        n = None
+        u = _lib.VertexUpdate(geometry=index, firstVertex=first_vertex)
+        for key, t in tensors.items():
+            width = 4 if key == "tangents" else 3
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != width:
+                raise NebError(f"update_vertices_device: {key} must be a float32 device tensor of shape (n, {width})")
+            if t.shape[0] and (t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < width)):
+                raise NebError(f"update_vertices_device: the rows of {key} must be contiguous and must not overlap")
+            if t.device.index != self.svgf.device:
+                raise NebError(f"update_vertices_device: {key} is on another device than the renderer")
+            if n is None:
+                n = t.shape[0]
+            elif t.shape[0] != n:
+                raise NebError(f"update_vertices_device: {n} positions but {t.shape[0]} {key}")
+            setattr(u, key, t.data_ptr())
+            setattr(u, key[:-1] + "Stride", 4 * (t.stride(0) if t.shape[0] > 1 else width))
+        if n == 0:
+            return  # (an empty range moves nothing; an empty tensor has no storage to point at)
+        u.numVertices = n
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        refused = self.update_status()["refused"] if mirror else 0  # (harvests every earlier update: the difference below is this call's)
+        self._check(self._lib.neb_gi_update_vertices_device(self._ctx, C.byref(u), 1, st), "neb_gi_update_vertices_device")
+        if mirror and self.update_status()["refused"] == refused:
+            gm = self._scene.geometries[index]
+            for key, t in tensors.items():
+                full = np.array(gm[key], np.float32, copy=True)
+                full[first_vertex:first_vertex + n] = t.cpu().numpy()
+                gm[key] = full
+
+    def update_status(self):
+        """{"accepted", "refused"}: device-sourced updates applied / refused on the device (a position that was not finite) since the scene
+        was set.  Waits for the updates enqueued so far."""
+        v = (C.c_uint64 * 2)()
+        self._check(self._lib.neb_gi_update_status(self._ctx, v), "neb_gi_update_status")
+        return {"accepted": int(v[0]), "refused": int(v[1])}
+
+    def scene_box(self):
+        """(lo, hi): the exact world-space box of the scene as the library holds it, two float32 arrays of 3.  Waits like update_status."""
+        lo, hi = (C.c_float * 3)(), (C.c_float * 3)()
+        self._check(self._lib.neb_gi_scene_box(self._ctx, lo, hi), "neb_gi_scene_box")
+        return np.array(lo[:], np.float32), np.array(hi[:], np.float32)
+
     def scene_info(self):
         t, n = C.c_uint32(), C.c_uint32()
         self._check(self._lib.neb_gi_scene_info(self._ctx, C.byref(t), C.byref(n)), "neb_gi_scene_info")

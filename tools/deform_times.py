@@ -1,7 +1,8 @@
 """Cost of deforming submeshes with neb_gi_update_vertices on the bench scene (sponza stand-in: 262 k triangles, 103 submeshes, six of
 them drapes), and what a refitted tree loses against a rebuilt one.
 
-  python tools/deform_times.py [--out profiles/deform_times.json] [--updates 50] [--warmup 5] [--triangles 262267]
+  python tools/deform_times.py [--out profiles/deform_times.json] [--device-out profiles/deform_device_times.json] [--updates 50]
+                               [--warmup 5] [--triangles 262267]
 
 For one drape, all drapes and every submesh -- one call each, positions + normals, a sine displacement along the normal with the normals
 recomputed from the deformed grid -- it records, for both arms of option "gi_deform_stage" (0: the scatter kernel reads the pinned staging,
@@ -12,6 +13,11 @@ recomputed from the deformed grid -- it records, for both arms of option "gi_def
                       neb_gi_set_scene + neb_gi_build_bvh -- what deforming a submesh cost before.
 And the loss in tree quality: node visits of the bounce rays per traced ray (neb_gi_traversal_stats, one 1080p dispatch) of the refitted
 tree against a tree built from the deformed scene, for a sine wave on the drapes of 3 cm and of 1 m amplitude.  Reported, not gated.
+A third arm, written to --device-out: the same three cases through neb_gi_update_vertices_device, the sources resident in device memory
+(uploaded once, outside the timed region) -- device interval and host time of the call beside the pinned arm's of this very run and the
+figures recorded before the device path existed.  And the all-submesh neb_gi_update_transforms of tools/refit_times.py twice: with the
+host's per-vertex box walk, and, after one device-sourced update has made every submesh's host positions stale, with the boxes reduced on
+the device.  An empty --out or --device-out writes no file.
 The JSON carries the library's build id (bench.library_build_id).  Needs a GPU; there is no CPU fallback.
 """
 import argparse
@@ -31,6 +37,7 @@ UNIT = 0.00800000037997961  # world units per object unit of the stand-in (its n
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "deform_times.json"))
+    ap.add_argument("--device-out", default=os.path.join(ROOT, "profiles", "deform_device_times.json"))
     ap.add_argument("--updates", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--triangles", type=int, default=262267)
@@ -162,6 +169,70 @@ def main():
                           "bounce_node_visits_per_ray_rebuilt": rebuilt, "ratio": refit / rebuilt}
         send(r, original(drapes))
     quality["restored"] = {"bounce_node_visits_per_ray_refit": visits_per_ray(r, mine)}
+
+    # ---- the third arm: sources resident in device memory (a fresh build first: no submesh is stale when an arm starts) ----
+    def timed(fn):
+        dev, host = [], []
+        for k in range(args.warmup + args.updates):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            h0 = time.perf_counter()
+            fn(k)
+            h1 = time.perf_counter()
+            e1.record()
+            torch.cuda.synchronize()
+            if k >= args.warmup:
+                dev.append(e0.elapsed_time(e1) * 1e3)
+                host.append((h1 - h0) * 1e6)
+        return {"update_device_us": float(np.median(dev)), "update_device_p10_p90_us": [float(np.percentile(dev, 10)), float(np.percentile(dev, 90))],
+                "update_host_us": float(np.median(host)), "device_over_build": float(np.median(dev)) / (build_ms * 1e3)}
+
+    def device_entries(indices, amplitude, phase):
+        tensors = [tuple(torch.from_numpy(a).cuda() for a in deformed(gi, amplitude, phase)) for gi in indices]
+        arr = (_lib.VertexUpdate * len(indices))()
+        for u, gi, (P, N) in zip(arr, indices, tensors):
+            u.geometry, u.firstVertex, u.numVertices = gi, 0, P.shape[0]
+            u.positions, u.positionStride, u.normals, u.normalStride = P.data_ptr(), 12, N.data_ptr(), 12
+        return arr, tensors
+
+    def send_device(arr):
+        r._check(r._lib.neb_gi_update_vertices_device(r._ctx, arr, len(arr), C.c_void_p(0)), "neb_gi_update_vertices_device")
+
+    recorded = {"one_drape": (116, 87), "all_drapes": (226, 182), "every_submesh": (1541, 1417)}  # profiles/deform_times.json before the device path
+    device_cases = {}
+    if args.device_out:
+        everything = list(range(n_geoms))
+        base = [sc.geometries[i]["M"].astype(np.float32) for i in everything]
+        idx = np.arange(n_geoms, dtype=np.uint32)
+        shift = [np.stack(base) for _ in range(2)]
+        for k in range(2):
+            shift[k][:, 3, 0] += np.float32(0.01 * (k + 1))  # every submesh 1 / 2 cm along x
+        moves = lambda k: r.update_transforms(idx, shift[k % 2], stream=0)
+        r.init_pathtracer_scene(mine)
+        torch.cuda.synchronize()
+        transforms = {"submeshes": n_geoms, "host_box_walk": timed(moves)}
+        for label, indices in (("one_drape", drapes[:1]), ("all_drapes", drapes), ("every_submesh", everything)):
+            r.init_pathtracer_scene(mine)
+            poses = [device_entries(indices, 3.0 + k, 0.9 * k) for k in range(2)]
+            torch.cuda.synchronize()
+            row = {k: v for k, v in cases[label].items() if k not in ("pinned", "device_copy")}
+            row["device_sources"] = timed(lambda k: send_device(poses[k % 2][0]))
+            row["host_sources_pinned_same_run"] = cases[label]["pinned"]
+            row["host_sources_pinned_recorded_before"] = {"update_device_us": recorded[label][0], "update_host_us": recorded[label][1]}
+            device_cases[label] = row
+        # (every submesh has just been updated from device memory: all 103 are stale)
+        transforms["device_reduced_boxes"] = timed(moves)
+        transforms["status"] = r.update_status()
+        out_dev = {"what": "neb_gi_update_vertices_device on the sponza stand-in, sources resident in device memory; device times between events, medians; "
+                           "beside the host-sourced pinned arm of the same run",
+                   "updates_per_case": args.updates, "warmup": args.warmup, "build_id": library_build_id(), "device": torch.cuda.get_device_name(0),
+                   "triangles": tris, "nodes": nodes, "submeshes": n_geoms, "drapes": drapes, "build_ms": build_ms,
+                   "cases": device_cases, "update_transforms_every_submesh": transforms}
+        print(json.dumps(out_dev, indent=1))
+        os.makedirs(os.path.dirname(os.path.abspath(args.device_out)), exist_ok=True)
+        with open(args.device_out, "w") as f:
+            json.dump(out_dev, f, indent=1)
 
     out = {"what": "neb_gi_update_vertices on the sponza stand-in; device times between events, medians; both arms of gi_deform_stage",
            "updates_per_case": args.updates, "warmup": args.warmup, "build_id": library_build_id(), "device": torch.cuda.get_device_name(0),
