@@ -65,6 +65,15 @@ typedef enum neb_plane {
  * when the option is turned off, re-created by neb_resize); neb_get_plane / uploads / downloads of it return NEB_ERR_STATE otherwise.
  * neb_gbuffer_raycast writes slot cur; a host with its own raster G-buffer uploads or writes it. */
 #define NEB_PLANE_SUBMESH_ID 12
+/* R32G32B32A32 16 B/px, ONE slot: per-vertex motion for the reprojecting temporal pass.  .xyz = the world point (fp32)
+ * where the surface point this pixel shows was when the PREVIOUS G-buffer was rendered; .w as uint32 = that point's previous geometric
+ * normal in the oct16 pair encoding of the normal plane's .xy (low half x, high half y).  .w == 0xFFFFFFFF (no encoded normal gives that
+ * word): no per-vertex motion for this pixel, the per-submesh rule of "svgf_motion" applies.  Behind the enum like the id plane: exists
+ * only while option "svgf_vertex_motion" is 1 (allocated with every byte 0xFF -- every pixel the sentinel -- freed with the option,
+ * re-created so by neb_resize).  neb_gbuffer_raycast
+ * writes it; a host with its own raster G-buffer uploads or writes it.  While the option is 0 every plane entry point refuses index 13
+ * with NEB_ERR_INVALID_ARG, the answer the index had before the option existed. */
+#define NEB_PLANE_PREV_POINT 13
 
 /* Slot selectors for the 2-slot (ping-pong) planes. */
 #define NEB_SLOT_CURRENT (-1) /* GetCurrentResourceIndex(), SVGFDenoiser.h:24 */
@@ -148,6 +157,10 @@ int neb_svgf_get_params(const neb_ctx* ctx, neb_svgf_params* out);
  *                       neb_svgf_set_camera.  NEB_ERR_STATE on a row-strip context.  1 allocates the (zeroed) history-length plane,
  *                       0 frees it: a context switched on and off again computes what a context that never had it on computes.
  *                       NEB_ERR_STATE for 0 while "svgf_motion" is 1 (turn that off first);
+ *   "svgf_vertex_motion": 0 (default) / 1 (opt-in, needs "svgf_motion" = 1, else NEB_ERR_STATE; "svgf_motion" cannot be turned off while
+ *                       it is 1): the temporal pass follows submeshes deformed by neb_gi_update_vertices / _device through
+ *                       NEB_PLANE_PREV_POINT, see neb_svgf_snapshot_vertices.  1 allocates the plane and, with a scene, the previous
+ *                       vertex pools; 0 frees them.  With the option 0 nothing changes;
  *   "svgf_motion":      0 (default) / 1 (opt-in, needs "svgf_reproject" = 1, else NEB_ERR_STATE): the reprojecting temporal pass follows
  *                       submeshes moved by neb_gi_update_transforms, see neb_svgf_snapshot_transforms.  1 allocates the (zeroed) submesh-id
  *                       plane and, with a scene set, two per-slot transform tables and the delta table; 0 frees them.  With 0 every
@@ -250,6 +263,26 @@ int neb_svgf_set_camera(neb_ctx* ctx, int slot, const struct neb_camera* cam);
  * (and fills the submesh-id plane of cur).  neb_gi_set_scene and neb_resize forget both snapshots; a context without a scene keeps none (NEB_OK:
  * nothing moved).  NEB_ERR_INVALID_ARG for a bad slot, NEB_ERR_STATE while "svgf_motion" is 0. */
 int neb_svgf_snapshot_transforms(neb_ctx* ctx, int slot, neb_stream stream);
+
+/* ---- Deforming submeshes under reprojection (option "svgf_vertex_motion" = 1 on top of "svgf_motion" = 1).  A vertex
+ * update (neb_gi_update_vertices, neb_gi_update_vertices_device) moves every surface point its own way, so the motion is one previous
+ * point per pixel: NEB_PLANE_PREV_POINT.  While the option is 1 and a scene is set the library keeps a previous copy of the position and
+ * normal pools -- the pools as they were when the most recent neb_gbuffer_raycast (or neb_svgf_snapshot_vertices) ran -- and a dirty word
+ * per geometry, set by an accepted vertex update.  neb_gbuffer_raycast writes {P_h, oct16(N_h)} for every hit pixel of a dirty, valid
+ * geometry when the history slot has a transform snapshot: the previous object-space vertices of the hit triangle interpolated at the
+ * hit's barycentrics, under the history slot's transform -- so a deformation and a neb_gi_update_transforms between the same two frames
+ * are followed at once -- and the sentinel everywhere else; behind the G-buffer kernel, on the same stream, it rolls the updated vertex
+ * ranges into the previous pools and clears the dirty words.  The temporal pass takes P and the geometric normal from the plane where
+ * .w is not the sentinel, and everything downstream of them is the pass of "svgf_motion".
+ * "Previous" is the preceding raycast: a host that raycasts twice into one slot between two temporal passes compares against the first
+ * of the two.  One raycast per frame is the contract.
+ * neb_svgf_snapshot_vertices runs that roll without a raycast (enqueue-only), for a host that renders its own G-buffer and fills
+ * NEB_PLANE_PREV_POINT itself: once per frame, after the frame's vertex updates.  NEB_ERR_STATE while "svgf_vertex_motion" is 0;
+ * NEB_OK and nothing enqueued without a scene or with nothing updated.
+ * The roll -- here and inside neb_gbuffer_raycast -- hands its vertex spans to the device in one of the four pinned argument slots of the
+ * update calls and follows their rule: no device synchronisation and no allocation, but the host waits when the slot's last user, an
+ * update or roll about a whole ring (kStageSlots = 4 calls) back, has not yet been read by the device. */
+int neb_svgf_snapshot_vertices(neb_ctx* ctx, neb_stream stream);
 /* Test / tooling aid: runs the delta kernel on the snapshots of (cur, hist) whether or not anything moved and downloads its table:
  * per geometry 32 floats = {flag as uint32 bits, 0, 0, 0 | D, 4 rows x 3 | K, 3 rows x 3 | zeros}; *n_out = entries written (the scene's
  * geometry count, which `capacity` must reach).  Synchronises `stream`.  host == NULL: the launch alone, enqueue-only (for timing it).
@@ -447,7 +480,8 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
  * No allocation once the pinned staging has reached the size of the largest update seen (it is allocated by the first call).
  * A later neb_gi_update_transforms applies its matrix to the deformed positions; a later neb_gi_build_bvh builds from them and packs the
  * records from the new normals and tangents.  "svgf_motion": a vertex update leaves the transform snapshots equal, so pixels of a deformed
- * submesh reproject as if static (the submesh-id test still applies).
+ * submesh reproject as if static (the submesh-id test still applies) -- unless "svgf_vertex_motion" is 1 as well: the update then marks the
+ * geometry, and neb_gbuffer_raycast writes where each of its pixels' points was one frame ago (neb_svgf_snapshot_vertices).
  * Refusals, each leaving everything unchanged: NEB_ERR_STATE before a successful neb_gi_build_bvh; NEB_ERR_INVALID_ARG for updates == NULL
  * with n > 0, NULL positions, a geometry >= n_geoms, a range beyond the geometry's numVertices, two overlapping ranges of one geometry in
  * the call, normals or tangents for a geometry set without all its attribute streams, a stride smaller than the element;

@@ -100,6 +100,16 @@ namespace Neb
             ThrowIfFailed(m_ctx, neb_get_plane(m_ctx, NEB_PLANE_SUBMESH_ID, slot, &p, pitchBytes, rows), "neb_get_plane");
             return p;
         }
+        // Option "svgf_vertex_motion" = 1 (SetOption, after "svgf_motion"): once per frame after the frame's vertex updates, for a host with
+        // its own raster G-buffer -- the updated vertices become the "previous" ones of the next frame (neb_svgf_snapshot_vertices) -- and
+        // the one-slot previous-point plane such a host fills (NEB_PLANE_PREV_POINT, behind the neb_plane enum as well)
+        void SnapshotVertices(neb_stream commandList) { ThrowIfFailed(m_ctx, neb_svgf_snapshot_vertices(m_ctx, commandList), "neb_svgf_snapshot_vertices"); }
+        void* GetPrevPointPlane(size_t* pitchBytes = nullptr, uint32_t* rows = nullptr)
+        {
+            void* p = nullptr;
+            ThrowIfFailed(m_ctx, neb_get_plane(m_ctx, NEB_PLANE_PREV_POINT, 0, &p, pitchBytes, rows), "neb_get_plane");
+            return p;
+        }
         // Durations (us) of the kernels of the last SubmitATrousComputeWavelet chain, after SetOption("svgf_profile", 1); returns how many
         uint32_t LevelTimes(float* outMicroseconds, uint32_t capacity)
         {

@@ -13,6 +13,7 @@ PLANE_RADIANCE, PLANE_NORMAL, PLANE_DEPTH, PLANE_MOMENTS, PLANE_VARIANCE, PLANE_
 PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY = 6, 7, 8, 9, 10
 PLANE_HISTORY_LENGTH = 11  # only while option svgf_reproject is 1
 PLANE_SUBMESH_ID = 12  # only while option svgf_motion is 1 (NEB_PLANE_SUBMESH_ID: behind the enum, not counted by NEB_PLANE_COUNT)
+PLANE_PREV_POINT = 13  # only while option svgf_vertex_motion is 1 (NEB_PLANE_PREV_POINT: behind the enum as well, one slot)
 SLOT_CURRENT, SLOT_HISTORY = -1, -2
 
 
@@ -61,6 +62,7 @@ _SIGS = {
     "neb_stream_synchronize": (C.c_int, [C.c_void_p, C.c_void_p]),
     "neb_svgf_reset_history": (C.c_int, [C.c_void_p, C.c_void_p]),
     "neb_svgf_snapshot_transforms": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "neb_svgf_snapshot_vertices": (C.c_int, [C.c_void_p, C.c_void_p]),
     "neb_svgf_debug_delta_table": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p]),
     "neb_svgf_level_times": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_uint32, C.POINTER(C.c_uint32)]),
     "neb_svgf_temporal": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -24,6 +24,7 @@ const PlaneInfo kPlaneInfo[kPlaneSlots] = {
     {16, 1}, // GEOMETRY     R32G32B32A32_FLOAT (decoded shading normal + depth of the current frame)
     {1, 2},  // HISTORY_LENGTH R8_UINT (only while option svgf_reproject is 1: alloc_history_length)
     {4, 2},  // SUBMESH_ID   R32_UINT (NEB_PLANE_SUBMESH_ID, behind the enum; only while option svgf_motion is 1: alloc_option_plane)
+    {16, 1}, // PREV_POINT   R32G32B32A32 (NEB_PLANE_PREV_POINT, behind the enum; only while option svgf_vertex_motion is 1: alloc_option_plane)
 };
 } // namespace neb
 
@@ -119,8 +120,9 @@ static int alloc_planes(neb_ctx* ctx)
     return NEB_OK;
 }
 
-// The two planes that exist only while their option is on, both slots zeroed: history length (svgf_reproject: no pixel has history
-// yet) and submesh id (svgf_motion).
+// The planes that exist only while their option is on: history length (svgf_reproject; zeroed: no pixel has history yet), submesh id
+// (svgf_motion; zeroed) and previous point (svgf_vertex_motion: one slot, every byte 0xFF -- .w is then the sentinel "no per-vertex motion"
+// and .xyz is never read, where a zeroed entry would be a valid point at the origin).
 static void free_option_plane(neb_ctx* ctx, int plane)
 {
     for (int s = 0; s < 2; ++s)
@@ -133,10 +135,10 @@ static void free_option_plane(neb_ctx* ctx, int plane)
 static int alloc_option_plane(neb_ctx* ctx, int plane)
 {
     const size_t bytes = (size_t)ctx->W * (ctx->row_end - ctx->row_begin) * kPlaneInfo[plane].bytes_per_px;
-    for (int s = 0; s < 2; ++s) {
+    for (int s = 0; s < (int)kPlaneInfo[plane].slots; ++s) {
         if (!ctx->planes[plane][s])
             NEB_HIP(ctx, hipMalloc(&ctx->planes[plane][s], bytes));
-        NEB_HIP(ctx, hipMemset(ctx->planes[plane][s], 0, bytes));
+        NEB_HIP(ctx, hipMemset(ctx->planes[plane][s], plane == NEB_PLANE_PREV_POINT ? 0xFF : 0, bytes));
     }
     NEB_HIP(ctx, hipDeviceSynchronize());
     return NEB_OK;
@@ -219,7 +221,10 @@ int neb_resize(neb_ctx* ctx, uint32_t width, uint32_t height)
     if (ctx->reproject)
         if (int rc = alloc_history_length(ctx))
             return rc;
-    return ctx->motion ? alloc_option_plane(ctx, NEB_PLANE_SUBMESH_ID) : NEB_OK;
+    if (ctx->motion)
+        if (int rc = alloc_option_plane(ctx, NEB_PLANE_SUBMESH_ID))
+            return rc;
+    return ctx->vertex_motion ? alloc_option_plane(ctx, NEB_PLANE_PREV_POINT) : NEB_OK;
 }
 
 int neb_destroy(neb_ctx* ctx)
@@ -237,6 +242,7 @@ int neb_destroy(neb_ctx* ctx)
     if (ctx->strip.xstream)
         (void)hipStreamDestroy(ctx->strip.xstream);
     gi_motion_tables_free(ctx);
+    gi_vertex_motion_free(ctx);
     gi_destroy(ctx->gi);
     delete ctx;
     return NEB_OK;
@@ -360,6 +366,8 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
             return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_motion needs svgf_reproject = 1");
         if (value == ctx->motion)
             return NEB_OK;
+        if (!value && ctx->vertex_motion)
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_motion cannot be turned off while svgf_vertex_motion is 1 (turn svgf_vertex_motion off first)");
         NEB_GUARD(ctx);
         if (value) {
             int rc = alloc_option_plane(ctx, NEB_PLANE_SUBMESH_ID);
@@ -376,6 +384,31 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
             gi_motion_tables_free(ctx);
         }
         ctx->motion = value;
+        return NEB_OK;
+    }
+    if (!strcmp(key, "svgf_vertex_motion")) {
+        if (value < 0 || value > 1)
+            return fail(ctx, NEB_ERR_INVALID_ARG, "neb_set_option: svgf_vertex_motion must be 0 or 1");
+        if (value && !ctx->motion)
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_vertex_motion needs svgf_motion = 1");
+        if (value == ctx->vertex_motion)
+            return NEB_OK;
+        NEB_GUARD(ctx);
+        if (value) {
+            int rc = alloc_option_plane(ctx, NEB_PLANE_PREV_POINT);
+            if (rc == NEB_OK)
+                rc = gi_vertex_motion_alloc(ctx);
+            if (rc != NEB_OK) {
+                free_option_plane(ctx, NEB_PLANE_PREV_POINT);
+                gi_vertex_motion_free(ctx);
+                return rc;
+            }
+        } else {
+            NEB_HIP(ctx, hipDeviceSynchronize()); // (work already enqueued may still read the plane and the pools)
+            free_option_plane(ctx, NEB_PLANE_PREV_POINT);
+            gi_vertex_motion_free(ctx);
+        }
+        ctx->vertex_motion = value;
         return NEB_OK;
     }
     if (!strcmp(key, "gi_sort_rays")) {
@@ -430,6 +463,8 @@ static int resolve_slot(const neb_ctx* ctx, int plane, int slot)
 {
     if (plane < 0 || plane >= kPlaneSlots)
         return -1;
+    if (plane == NEB_PLANE_PREV_POINT && !ctx->vertex_motion)
+        return -1; // (no such plane while its option is off: the index answers as it did before the option existed)
     if (kPlaneInfo[plane].slots == 1)
         return (slot == 0 || slot == NEB_SLOT_CURRENT) ? 0 : -1;
     if (slot == NEB_SLOT_CURRENT)
@@ -445,10 +480,13 @@ int neb_get_plane(neb_ctx* ctx, int plane, int slot, void** dptr, size_t* pitch_
         return fail(ctx, NEB_ERR_INVALID_ARG, "neb_get_plane: null argument");
     const int s = resolve_slot(ctx, plane, slot);
     if (s < 0)
-        return fail(ctx, NEB_ERR_INVALID_ARG, "neb_get_plane: bad plane/slot");
+        return fail(ctx, NEB_ERR_INVALID_ARG, plane == NEB_PLANE_PREV_POINT && !ctx->vertex_motion
+                                                  ? "neb_get_plane: the previous-point plane exists only while option svgf_vertex_motion is 1"
+                                                  : "neb_get_plane: bad plane/slot");
     if (!ctx->planes[plane][s])
-        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_SUBMESH_ID ? "neb_get_plane: the submesh-id plane exists only while option svgf_motion is 1"
-                                                                      : "neb_get_plane: the history-length plane exists only while option svgf_reproject is 1");
+        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_PREV_POINT ? "neb_get_plane: the previous-point plane is missing (a failed resize?)"
+                                        : plane == NEB_PLANE_SUBMESH_ID ? "neb_get_plane: the submesh-id plane exists only while option svgf_motion is 1"
+                                                                        : "neb_get_plane: the history-length plane exists only while option svgf_reproject is 1");
     if (int rc = svgf_flush_pending(ctx))
         return rc;
     if (plane == NEB_PLANE_NORMAL || plane == NEB_PLANE_DEPTH)
@@ -468,10 +506,13 @@ static int copy_rows(neb_ctx* ctx, int plane, int slot, uint32_t row0, uint32_t 
         return fail(ctx, NEB_ERR_INVALID_ARG, "copy rows: null argument");
     const int s = resolve_slot(ctx, plane, slot);
     if (s < 0)
-        return fail(ctx, NEB_ERR_INVALID_ARG, "copy rows: bad plane/slot");
+        return fail(ctx, NEB_ERR_INVALID_ARG, plane == NEB_PLANE_PREV_POINT && !ctx->vertex_motion
+                                                  ? "copy rows: the previous-point plane exists only while option svgf_vertex_motion is 1"
+                                                  : "copy rows: bad plane/slot");
     if (!ctx->planes[plane][s])
-        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_SUBMESH_ID ? "copy rows: the submesh-id plane exists only while option svgf_motion is 1"
-                                                                      : "copy rows: the history-length plane exists only while option svgf_reproject is 1");
+        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_PREV_POINT ? "copy rows: the previous-point plane is missing (a failed resize?)"
+                                        : plane == NEB_PLANE_SUBMESH_ID ? "copy rows: the submesh-id plane exists only while option svgf_motion is 1"
+                                                                        : "copy rows: the history-length plane exists only while option svgf_reproject is 1");
     if (row0 < ctx->row_begin || row0 + nrows > ctx->row_end)
         return fail(ctx, NEB_ERR_OUT_OF_RANGE, "copy rows: rows not resident in this context");
     if (int rc = svgf_flush_pending(ctx))
@@ -642,6 +683,11 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
             mo.id_hist = (const uint32_t*)ctx->planes[NEB_PLANE_SUBMESH_ID][h];
             mo.delta = ctx->motion_delta;
             mo.n_delta = 0;
+            if (ctx->vertex_motion) { // the third arm: P and the geometric normal from the plane where it holds them
+                if (!ctx->planes[NEB_PLANE_PREV_POINT][0])
+                    return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal: the previous-point plane is missing (a failed resize?)");
+                mo.prev_point = (const float4*)ctx->planes[NEB_PLANE_PREV_POINT][0];
+            }
             // a slot without a snapshot, no scene, or no update enqueued between the two snapshots: nothing moved, no delta launch
             if (ctx->motion_delta && ctx->has_snap[c] && ctx->has_snap[h] && ctx->snap_epoch[c] != ctx->snap_epoch[h]) {
                 hipError_t de = launch_reproj_delta(ctx->xf_snap[c], ctx->xf_snap[h], ctx->motion_delta, ctx->motion_geoms, (hipStream_t)stream);
@@ -880,6 +926,17 @@ int neb_svgf_snapshot_transforms(neb_ctx* ctx, int slot, neb_stream stream)
     if (int rc = svgf_flush_pending(ctx))
         return rc;
     return gi_snapshot_transforms(ctx, s, (hipStream_t)stream);
+}
+
+int neb_svgf_snapshot_vertices(neb_ctx* ctx, neb_stream stream)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    if (!ctx->vertex_motion)
+        return fail(ctx, NEB_ERR_STATE, "neb_svgf_snapshot_vertices: option svgf_vertex_motion is 0");
+    if (int rc = svgf_flush_pending(ctx))
+        return rc;
+    return gi_roll_vertices(ctx, (hipStream_t)stream);
 }
 
 int neb_svgf_debug_delta_table(neb_ctx* ctx, float* host, uint32_t capacity, uint32_t* n_out, neb_stream stream)

@@ -713,6 +713,14 @@ struct GbufArgs {
     uint32_t* depth;
     uint32_t W, H, row_begin, row0, row1, tiles_x;
     uint32_t* submesh_id; // option svgf_motion: geometry index of the primary hit (0xFFFFFFFF: no surface); null otherwise -- nothing stored
+    // option svgf_vertex_motion, all null / 0 otherwise -- nothing stored: NEB_PLANE_PREV_POINT, the per-geometry dirty
+    // words, the position and normal pools as the previous raycast saw them, and the history slot's transform snapshot (0: it has none)
+    float4* prev_point;
+    const uint32_t* deform_dirty;
+    const float* pos_prev;
+    const float* nrm_prev;
+    const float* xf_hist;
+    uint32_t has_xf_hist;
 };
 
 __global__ __launch_bounds__(64) void gbuffer_kernel(GbufArgs a)
@@ -799,6 +807,37 @@ __global__ __launch_bounds__(64) void gbuffer_kernel(GbufArgs a)
     a.depth[i] = ds;
     if (a.submesh_id)
         a.submesh_id[i] = geom;
+    if (a.prev_point) {
+        // Where the surface point this pixel shows was when the previous G-buffer was rendered: the hit triangle's three PREVIOUS
+        // object-space vertices (through the index pool, as rebake_kernel takes them; a split reference keeps the whole triangle, so
+        // h.u / h.v are the whole triangle's barycentrics) interpolated in object space, q = b0 p0 + b1 p1 + b2 p2 as
+        // fmaf(b2, p2, fmaf(b1, p1, b0 * p0)), then under the history slot's transform, P_h = (q, 1) . M as
+        // fmaf(q.z, M[2][j], fmaf(q.y, M[1][j], fmaf(q.x, M[0][j], M[3][j]))).  The normal: GN's own sequence on the previous vertex
+        // normals and M's upper 3x3.  Only for a hit on a valid geometry an accepted vertex update has marked since the last roll.
+        float4 out = make_float4(0.f, 0.f, 0.f, __uint_as_float(kReprojNoPrevPoint));
+        if (hit && a.has_xf_hist && a.deform_dirty[geom] != 0u) {
+            const DevGeom g = a.S.geoms[geom];
+            if (g.valid) {
+                const uint32_t prim = __float_as_uint(a.S.tris[3 * h.tri + 2].z);
+                const uint32_t first = g.firstIndex + 3u * prim;
+                const uint32_t v0 = g.vertexBase + a.S.indices[first], v1 = g.vertexBase + a.S.indices[first + 1], v2 = g.vertexBase + a.S.indices[first + 2];
+                const float b1 = h.u, b2 = h.v, b0 = 1.0f - (b1 + b2);
+                const float3 p0 = load3(a.pos_prev, v0), p1 = load3(a.pos_prev, v1), p2 = load3(a.pos_prev, v2);
+                const float qx = fmaf(b2, p2.x, fmaf(b1, p1.x, b0 * p0.x));
+                const float qy = fmaf(b2, p2.y, fmaf(b1, p1.y, b0 * p0.y));
+                const float qz = fmaf(b2, p2.z, fmaf(b1, p1.z, b0 * p0.z));
+                const float* M = a.xf_hist + 16 * (size_t)geom;
+                const float m3[9] = {M[0], M[1], M[2], M[4], M[5], M[6], M[8], M[9], M[10]};
+                const float3 w0 = normalize3(xform_dir(m3, load3(a.nrm_prev, v0))), w1 = normalize3(xform_dir(m3, load3(a.nrm_prev, v1))),
+                             w2 = normalize3(xform_dir(m3, load3(a.nrm_prev, v2)));
+                const float2 en = oct_pack(normalize3(w0 * b0 + w1 * b1 + w2 * b2));
+                out = make_float4(fmaf(qz, M[8], fmaf(qy, M[4], fmaf(qx, M[0], M[12]))), fmaf(qz, M[9], fmaf(qy, M[5], fmaf(qx, M[1], M[13]))),
+                                  fmaf(qz, M[10], fmaf(qy, M[6], fmaf(qx, M[2], M[14]))),
+                                  __uint_as_float(float_to_half_bits(en.x) | (float_to_half_bits(en.y) << 16)));
+            }
+        }
+        a.prev_point[i] = out;
+    }
 }
 
 // The reference adds the indirect term into radiance[cur] in a separate step (nrc Resolve, DeferredRenderer.cpp:586).
@@ -1480,8 +1519,19 @@ int neb_gbuffer_raycast(neb_ctx* ctx, const neb_camera* cam, neb_stream stream)
     ctx->cams[ctx->cur] = *cam; // (what the reprojecting temporal pass maps depth[cur] back with)
     ctx->has_cam[ctx->cur] = true;
     a.submesh_id = ctx->motion ? (uint32_t*)ctx->planes[NEB_PLANE_SUBMESH_ID][ctx->cur] : nullptr;
+    // option svgf_vertex_motion with a scene's pools present: the kernel also writes the previous-point plane
+    const bool vertex_motion = ctx->vertex_motion && g->d_pos_prev && ctx->planes[NEB_PLANE_PREV_POINT][0];
+    a.prev_point = vertex_motion ? (float4*)ctx->planes[NEB_PLANE_PREV_POINT][0] : nullptr;
+    a.deform_dirty = vertex_motion ? g->d_deform_dirty : nullptr;
+    a.pos_prev = vertex_motion ? g->d_pos_prev : nullptr;
+    a.nrm_prev = vertex_motion ? g->d_nrm_prev : nullptr;
+    a.xf_hist = vertex_motion && ctx->has_snap[ctx->hist] && ctx->motion_geoms == g->n_geoms ? ctx->xf_snap[ctx->hist] : nullptr;
+    a.has_xf_hist = a.xf_hist ? 1u : 0u;
     hipLaunchKernelGGL(gbuffer_kernel, dim3(a.tiles_x * tiles_y), dim3(64), 0, (hipStream_t)stream, a);
     GI_HIP(ctx, hipGetLastError());
+    if (vertex_motion) // (behind the kernel that read them: the updated vertex ranges become "previous", the dirty words are cleared)
+        if (int rc = neb::gi_roll_vertices(ctx, (hipStream_t)stream))
+            return rc;
     if (ctx->motion) // (the transforms this G-buffer was rendered with: what the temporal pass follows moved submeshes by)
         return neb::gi_snapshot_transforms(ctx, ctx->cur, (hipStream_t)stream);
     return NEB_OK;

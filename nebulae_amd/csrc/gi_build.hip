@@ -1210,6 +1210,7 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     GI_GUARD(ctx);
     GI_HIP(ctx, hipDeviceSynchronize());
     gi_motion_tables_free(ctx); // (option svgf_motion: both transform snapshots belonged to the old scene)
+    gi_vertex_motion_free(ctx); // (option svgf_vertex_motion: so did the previous vertex pools and the dirty spans)
     gi_destroy(ctx->gi);
     ctx->gi = nullptr;
     GiState* g = new GiState();
@@ -1500,7 +1501,10 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     g->d_ray_counter = (unsigned long long*)ctr;
     g->view.n_tris = g->n_tris;
     ctx->gi = g;
-    return ctx->motion ? gi_motion_tables_alloc(ctx) : NEB_OK;
+    if (ctx->motion)
+        if (int rc = gi_motion_tables_alloc(ctx))
+            return rc;
+    return ctx->vertex_motion ? gi_vertex_motion_alloc(ctx) : NEB_OK;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -310,6 +310,19 @@ struct GiState {
         std::vector<uint32_t> geoms;  // entry e holds the boxes of geometry geoms[e]
     } result_rec[kStageSlots];
     uint64_t device_updates_accepted = 0, device_updates_refused = 0; // as harvested
+    // ---- deforming submeshes under reprojection: option svgf_vertex_motion (gi_refit.hip) ----
+    // While the option is on: the position and normal pools as they were when the most recent neb_gbuffer_raycast (or
+    // neb_svgf_snapshot_vertices) ran, and one word per geometry that deform_scatter_kernel sets and deform_roll_kernel clears.
+    // All three null with the option off: every kernel that takes them stores nothing then.
+    float* d_pos_prev = nullptr;
+    float* d_nrm_prev = nullptr;
+    uint32_t* d_deform_dirty = nullptr;
+    // per geometry, the union [x, y) of the vertex ranges (in the geometry's own numbering) passed to an update call since the last roll;
+    // x >= y: none.  One span per geometry however many updates arrive.
+    std::vector<uint2> roll_span;
+    bool roll_pending = false;
+    // One span of a roll in the pinned slot: lanes [first_lane, first_lane + count) copy pool vertices dst .. of geometry geom.
+    struct RollSpan { uint32_t first_lane, count, dst, geom; };
     // Streams that have read triangles / nodes / geometry tables since the last update: an update on another stream orders itself
     // behind them (an event recorded on each, waited for on its own stream).  More than kReaderStreams: it waits for the device.
     static constexpr int kReaderStreams = 4;

@@ -94,11 +94,14 @@ __global__ void rebake_kernel(float4* __restrict__ tris, uint32_t n_slots, uint3
 // DEVICE_SRC: the vertices are not in the slot but where sources[range] points (strided device memory), and the whole launch leaves
 // at once when deform_check_kernel has set the call's refusal word -- nothing is written, no geometry is stamped, and every kernel
 // behind this one acts on stamped geometries only: a refused update is a no-op on the device.
+// deform_dirty (option svgf_vertex_motion, null with the option off): where the lane stamps its geometry it also sets the geometry's
+// dirty word, which gbuffer_kernel reads and deform_roll_kernel clears.
 template <bool DEVICE_SRC>
 __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const float* __restrict__ data, uint32_t n_lanes,
                                       uint32_t n_pool, uint32_t n_geoms, uint32_t epoch, float* __restrict__ pos, float* __restrict__ normals,
                                       float* __restrict__ tangents, uint32_t* __restrict__ geom_epoch,
-                                      const GiState::DeformSource* __restrict__ sources, const uint32_t* __restrict__ refused)
+                                      const GiState::DeformSource* __restrict__ sources, const uint32_t* __restrict__ refused,
+                                      uint32_t* __restrict__ deform_dirty)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_lanes)
@@ -139,8 +142,40 @@ __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ r
         normals[3 * v] = sn[0], normals[3 * v + 1] = sn[1], normals[3 * v + 2] = sn[2];
     if (st)
         tangents[4 * v] = st[0], tangents[4 * v + 1] = st[1], tangents[4 * v + 2] = st[2], tangents[4 * v + 3] = st[3];
-    if (j == 0 && r.geom < n_geoms)
+    if (j == 0 && r.geom < n_geoms) {
         geom_epoch[r.geom] = epoch;
+        if (deform_dirty)
+            deform_dirty[r.geom] = 1u;
+    }
+}
+
+// Option svgf_vertex_motion: one lane per vertex of the spans updated since the last roll, found by the scatter's bisection over the
+// spans' first lanes (n spans, ascending, none empty).  The lane copies its vertex's position and normal from the live pools to the
+// previous pools; lane 0 of a span clears its geometry's dirty word.  Enqueued behind gbuffer_kernel, which has read both.
+__global__ void deform_roll_kernel(const GiState::RollSpan* __restrict__ spans, uint32_t n_spans, uint32_t n_lanes, uint32_t n_pool, uint32_t n_geoms,
+                                   const float* __restrict__ pos, const float* __restrict__ normals, float* __restrict__ pos_prev,
+                                   float* __restrict__ nrm_prev, uint32_t* __restrict__ deform_dirty)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    uint32_t lo = 0, hi = n_spans; // the last span with first_lane <= k
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (spans[mid].first_lane <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    const GiState::RollSpan r = spans[lo];
+    const uint32_t j = k - r.first_lane;
+    if (j >= r.count || r.dst + j >= n_pool)
+        return;
+    const size_t v = (size_t)r.dst + j;
+    pos_prev[3 * v] = pos[3 * v], pos_prev[3 * v + 1] = pos[3 * v + 1], pos_prev[3 * v + 2] = pos[3 * v + 2];
+    nrm_prev[3 * v] = normals[3 * v], nrm_prev[3 * v + 1] = normals[3 * v + 1], nrm_prev[3 * v + 2] = normals[3 * v + 2];
+    if (j == 0 && r.geom < n_geoms)
+        deform_dirty[r.geom] = 0u;
 }
 
 // One lane per leaf-order slot: the record of a slot whose geometry is stamped gets its normal and tangent words again from the pools,
@@ -542,6 +577,103 @@ static int refit_order_behind_readers(neb_ctx* ctx, GiState* g, hipStream_t stre
     return NEB_OK;
 }
 
+// ---- option svgf_vertex_motion: previous pools, dirty spans, the roll ----
+// an update call names vertices [first, first + count) of geometry gi: the union per geometry is what the next roll copies
+static void roll_mark(GiState* g, uint32_t gi, uint32_t first, uint32_t count)
+{
+    if (!g->d_pos_prev || !count)
+        return;
+    uint2& sp = g->roll_span[gi];
+    if (sp.x >= sp.y)
+        sp = make_uint2(first, first + count);
+    else
+        sp = make_uint2(std::min(sp.x, first), std::max(sp.y, first + count));
+    g->roll_pending = true;
+}
+
+void gi_vertex_motion_free(neb_ctx* ctx)
+{
+    GiState* g = ctx->gi;
+    if (!g)
+        return;
+    for (void* p : {(void*)g->d_pos_prev, (void*)g->d_nrm_prev, (void*)g->d_deform_dirty})
+        if (p)
+            (void)hipFree(p);
+    g->d_pos_prev = g->d_nrm_prev = nullptr;
+    g->d_deform_dirty = nullptr;
+    g->roll_span.clear();
+    g->roll_pending = false;
+}
+
+int gi_vertex_motion_alloc(neb_ctx* ctx)
+{
+    gi_vertex_motion_free(ctx);
+    GiState* g = ctx->gi;
+    if (!g || !g->n_geoms || !g->d_pos || !g->view.normals || !g->h_stage || g->h_pos.empty())
+        return NEB_OK; // no scene: nothing can deform
+    GI_GUARD(ctx);
+    const size_t bytes = g->h_pos.size() * sizeof(float); // (the normal pool holds three floats per vertex as well)
+    hipError_t e = hipDeviceSynchronize(); // (an update still in flight would be copied half done)
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&g->d_pos_prev, bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&g->d_nrm_prev, bytes);
+    if (e == hipSuccess)
+        e = hipMalloc((void**)&g->d_deform_dirty, (size_t)g->n_geoms * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipMemcpy(g->d_pos_prev, g->d_pos, bytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess)
+        e = hipMemcpy(g->d_nrm_prev, g->view.normals, bytes, hipMemcpyDeviceToDevice);
+    if (e == hipSuccess)
+        e = hipMemset(g->d_deform_dirty, 0, (size_t)g->n_geoms * sizeof(uint32_t));
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize();
+    if (e != hipSuccess) {
+        gi_vertex_motion_free(ctx);
+        return gi_fail(ctx, NEB_ERR_HIP, "svgf_vertex_motion: previous vertex pools", e);
+    }
+    g->roll_span.assign(g->n_geoms, make_uint2(0u, 0u));
+    return NEB_OK;
+}
+
+// The spans travel in the ring of pinned argument slots (h_stage, stage_ev): the slot two calls ahead of the last update's, the one
+// furthest from the slots the updates around this roll use, under the ring's own rule -- whoever writes a slot waits for the event of
+// its last user first (long passed unless the host runs a whole ring ahead).  Enqueue only, nothing allocated.
+int gi_roll_vertices(neb_ctx* ctx, hipStream_t stream)
+{
+    GiState* g = ctx->gi;
+    if (!g || !g->d_pos_prev || !g->roll_pending)
+        return NEB_OK;
+    GI_GUARD(ctx);
+    static_assert(sizeof(GiState::RollSpan) <= sizeof(GiState::StageEntry), "a slot of h_stage holds one span per geometry");
+    const int slot = (int)((g->epoch + 2u) % (uint32_t)GiState::kStageSlots);
+    if (!g->stage_ev[slot])
+        GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
+    if (g->stage_used[slot])
+        GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot]));
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // an update enqueued on another stream comes first; a later one waits for this roll
+    GiState::RollSpan* spans = reinterpret_cast<GiState::RollSpan*>(g->h_stage + (size_t)slot * g->n_geoms);
+    const uint32_t n_pool = (uint32_t)(g->h_pos.size() / 3);
+    uint32_t n_spans = 0, lane = 0;
+    for (uint32_t gi = 0; gi < g->n_geoms; ++gi) {
+        uint2& sp = g->roll_span[gi];
+        if (sp.x < sp.y) {
+            spans[n_spans++] = {lane, sp.y - sp.x, g->h_geoms[gi].vertexBase + sp.x, gi};
+            lane += sp.y - sp.x;
+        }
+        sp = make_uint2(0u, 0u);
+    }
+    g->roll_pending = false;
+    if (!lane)
+        return NEB_OK;
+    hipLaunchKernelGGL(deform_roll_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::RollSpan*)spans, n_spans, lane, n_pool,
+                       g->n_geoms, (const float*)g->d_pos, g->view.normals, g->d_pos_prev, g->d_nrm_prev, g->d_deform_dirty);
+    GI_HIP(ctx, hipGetLastError());
+    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
+    g->stage_used[slot] = true;
+    return NEB_OK;
+}
+
 } // namespace neb
 
 using namespace neb;
@@ -807,6 +939,7 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         GiState::HostGeom& hg = g->h_geoms[sp.geom];
         GiState::DeformRange& r = ranges[i];
         r.first_lane = lane, r.count = sp.count, r.dst = hg.vertexBase + sp.first, r.geom = sp.geom, r.pad = 0;
+        roll_mark(g, sp.geom, sp.first, sp.count);
         r.pos_off = off_p;
         r.nrm_off = u.normals ? off_n : GiState::kNoStream;
         r.tan_off = u.tangents ? off_t : GiState::kNoStream;
@@ -870,7 +1003,8 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
     }
     hipLaunchKernelGGL(deform_scatter_kernel<false>, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)src, n_ranges,
                        (const float*)(src + head), lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
-                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)nullptr, (const uint32_t*)nullptr);
+                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)nullptr, (const uint32_t*)nullptr,
+                       g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
     GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
     g->stage_used[slot] = true;
@@ -988,6 +1122,7 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
         GiState::HostGeom& hg = g->h_geoms[sp.geom];
         GiState::DeformRange& r = ranges[i];
         r.first_lane = lane, r.count = sp.count, r.dst = hg.vertexBase + sp.first, r.geom = sp.geom, r.pad = 0;
+        roll_mark(g, sp.geom, sp.first, sp.count); // (the host cannot know of a refusal on the device: the roll then copies equal values)
         r.pos_off = 0;
         r.nrm_off = u.normals ? 0u : GiState::kNoStream; // (device sources: only "has the stream" is read)
         r.tan_off = u.tangents ? 0u : GiState::kNoStream;
@@ -1014,7 +1149,8 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
                        (const GiState::DeformSource*)sources, lane, g->n_geoms, (const float*)g->d_xf, d_res + 1);
     hipLaunchKernelGGL(deform_scatter_kernel<true>, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)ranges, n_ranges,
                        (const float*)nullptr, lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
-                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)sources, (const uint32_t*)(d_res + 1));
+                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)sources, (const uint32_t*)(d_res + 1),
+                       g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
     GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
     g->stage_used[slot] = true;

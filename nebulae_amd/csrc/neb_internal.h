@@ -14,8 +14,8 @@ struct PlaneInfo {
     uint32_t bytes_per_px;
     uint32_t slots;
 };
-// the reference-format planes of the enum, and behind them NEB_PLANE_SUBMESH_ID (not counted by NEB_PLANE_COUNT)
-constexpr int kPlaneSlots = NEB_PLANE_COUNT + 1;
+// the reference-format planes of the enum, and behind them NEB_PLANE_SUBMESH_ID and NEB_PLANE_PREV_POINT (not counted by NEB_PLANE_COUNT)
+constexpr int kPlaneSlots = NEB_PLANE_COUNT + 2;
 extern const PlaneInfo kPlaneInfo[kPlaneSlots];
 
 // Every entry point that launches or copies runs on its context's device whatever device the calling thread had
@@ -124,13 +124,16 @@ hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam
                                      const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
                                      const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s);
 
-// Option svgf_motion: the motion arm of the same kernel (svgf_temporal_reproject_kernel<true>) -- id planes of the two slots, and
+// Option svgf_motion: the motion arm of the same kernel (svgf_temporal_reproject_kernel<ReprojMode::Submesh>) -- id planes of the two slots, and
 // the per-geometry delta table launch_reproj_delta wrote in front of it (n_delta = 0: nothing moved between the two snapshots).
 struct ReprojMotion {
     const uint32_t* id_cur;
     const uint32_t* id_hist;
     const float4* delta; // n_delta entries of kReprojDeltaFloat4 float4 (svgf_reproject.h)
     uint32_t n_delta;
+    // Option svgf_vertex_motion: NEB_PLANE_PREV_POINT, {P_h.xyz, oct16(N_h) | kReprojNoPrevPoint} per pixel.  Non-null picks the third arm
+    // of the kernel (ReprojMode::Vertex), which takes P and the geometric normal from it where .w is not the sentinel.
+    const float4* prev_point = nullptr;
 };
 hipError_t launch_temporal_reproject_motion(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
                                             const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
@@ -171,6 +174,11 @@ int gi_set_deform_stage(neb_ctx* ctx, int mode);
 int gi_motion_tables_alloc(neb_ctx* ctx); // NEB_OK also without a scene (nothing to allocate); forgets both snapshots
 void gi_motion_tables_free(neb_ctx* ctx);
 int gi_snapshot_transforms(neb_ctx* ctx, int s, hipStream_t stream); // s = 0 / 1, resolved
+// option svgf_vertex_motion (gi_refit.hip): the previous position / normal pools and the per-geometry dirty words exist while the option
+// is on and a scene is set
+int gi_vertex_motion_alloc(neb_ctx* ctx); // NEB_OK also without a scene (nothing to allocate); the pools start as copies of the live ones
+void gi_vertex_motion_free(neb_ctx* ctx);
+int gi_roll_vertices(neb_ctx* ctx, hipStream_t stream); // live -> previous for the vertex spans updated since the last roll; enqueue only
 
 } // namespace neb
 
@@ -198,6 +206,7 @@ struct neb_ctx {
     uint32_t snap_epoch[2] = {0, 0};   // updates enqueued before the snapshot: equal for both slots = nothing moved between them
     float4* motion_delta = nullptr;    // reproj_delta_kernel's output, n_geoms entries
     uint32_t motion_geoms = 0;         // geometries the three tables were sized for
+    int vertex_motion = 0;             // option svgf_vertex_motion: the temporal pass follows deformed submeshes (planes[NEB_PLANE_PREV_POINT] exists only then)
     neb::GiState* gi = nullptr;
     // neb_strip_frame* (strips.hip): a side stream for the halo exchange beside level 0, and the events that order it -- created on first use
     struct StripSync {

@@ -329,10 +329,15 @@ hipError_t launch_reproj_delta(const float* xf_cur, const float* xf_hist, float4
 
 // MOTION (option svgf_motion): the pixel's world point and geometric normal are carried to where that surface point
 // was in the history frame by its submesh's delta entry before anything else looks at them, and a tap counts only if the history
-// frame saw the same submesh there.  MOTION = false is the kernel as it was: `m` is not read and the code is the same.
-template <bool MOTION>
+// frame saw the same submesh there.  MODE = Off is the kernel as it was: `m` is not read and the code is the same.
+// MODE = Vertex (option svgf_vertex_motion) on top of Submesh: the pixel's entry of NEB_PLANE_PREV_POINT is read in the
+// same round trip as its id; where its .w is not the sentinel it IS the previous point and geometric normal and the delta entry is not
+// read, where it is the sentinel the Submesh rule applies unchanged.  Everything behind P and Ng is shared by the three arms.
+enum class ReprojMode { Off, Submesh, Vertex };
+template <ReprojMode MODE>
 __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs a, ReprojMotion m)
 {
+    constexpr bool MOTION = MODE != ReprojMode::Off, VERTEX = MODE == ReprojMode::Vertex;
     const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (tile >= a.n_tiles)
         return;
@@ -347,6 +352,9 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
     uint32_t g = kReprojNoSubmesh;
     if constexpr (MOTION)
         g = m.id_cur[i];
+    float4 pv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if constexpr (VERTEX)
+        pv = m.prev_point[i];
     const float zc = depth_unorm24(dc);
 
     float4 Ch = Cc; // (with no history: a = 0 and lerp(Cc, Cc, 0) = Cc exactly)
@@ -356,8 +364,16 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
         float3 P = reproj_world_point(a.cc, a.inv_W, a.inv_H, x, y, zc);
         float3 Ng = oct16_unpack_zw(nc.x); // geometric normal (.xy)
         bool frozen = false; // MOTION: the submesh's transform cannot be inverted -- no history
+        bool per_vertex = false; // VERTEX: the plane holds this pixel's previous point and normal
+        if constexpr (VERTEX) {
+            per_vertex = __float_as_uint(pv.w) != kReprojNoPrevPoint;
+            if (per_vertex) {
+                P = make_float3(pv.x, pv.y, pv.z);
+                Ng = oct16_unpack_zw(__float_as_uint(pv.w));
+            }
+        }
         if constexpr (MOTION) {
-            if (g < m.n_delta) { // (no entry, no id: the point did not move -- P and Ng as they are)
+            if (!per_vertex && g < m.n_delta) { // (no entry, no id: the point did not move -- P and Ng as they are)
                 const float4* e = m.delta + (size_t)kReprojDeltaFloat4 * g;
                 const uint32_t flag = __float_as_uint(e[0].x);
                 frozen = flag == kReprojDeltaSingular;
@@ -508,10 +524,12 @@ static hipError_t launch_reproject(const SvgfLaunch& L, const CameraBasis& cam_c
     a.hist_ok = cam_hist != nullptr;
     a.cc = reproj_cam(cam_cur);
     a.ch = reproj_cam(cam_hist ? *cam_hist : cam_cur);
-    if (motion)
-        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<true>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, *motion);
+    if (motion && motion->prev_point)
+        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::Vertex>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, *motion);
+    else if (motion)
+        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::Submesh>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, *motion);
     else
-        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<false>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, ReprojMotion{});
+        hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::Off>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, ReprojMotion{});
     return hipGetLastError();
 }
 

@@ -65,6 +65,10 @@ class DeferredRenderer:
         # writes the ids and takes the transform snapshot; a caller that uploads its own G-buffer uploads PLANE_SUBMESH_ID too and
         # calls svgf.snapshot_transforms(SLOT_CURRENT) once the frame's update_transforms has been made.
         self.motion_vectors = False
+        # ... and submeshes deformed by update_vertices (option svgf_vertex_motion, set at init; needs motion_vectors): submit_commands_gbuffer
+        # also writes PLANE_PREV_POINT, where each pixel's surface point was one frame ago, from the previous vertices it keeps.  A caller
+        # that uploads its own G-buffer uploads that plane too and calls svgf.snapshot_vertices() once per frame.
+        self.vertex_motion = False
         self.info = None
 
     # ---- DeferredRenderer::Init (src/DeferredRenderer.cpp:26-57) ----
@@ -73,10 +77,15 @@ class DeferredRenderer:
         if self.motion_vectors and not self.temporal_reprojection:
             self.svgf.destroy()
             raise NebError("DeferredRenderer.init: motion_vectors needs temporal_reprojection")
+        if self.vertex_motion and not self.motion_vectors:
+            self.svgf.destroy()
+            raise NebError("DeferredRenderer.init: vertex_motion needs motion_vectors")
         if self.temporal_reprojection:
             self.svgf.set_option("svgf_reproject", 1)
         if self.motion_vectors:
             self.svgf.set_option("svgf_motion", 1)
+        if self.vertex_motion:
+            self.svgf.set_option("svgf_vertex_motion", 1)
         self.width, self.height = width, height
         return True
 

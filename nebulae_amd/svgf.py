@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from ._lib import (PLANE_DEPTH, PLANE_MOMENTS, PLANE_NORMAL, PLANE_RADIANCE, PLANE_SCRATCH, PLANE_VARIANCE,  # noqa: F401
                    PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY, PLANE_HISTORY_LENGTH, PLANE_SUBMESH_ID,
-                   SLOT_CURRENT, SLOT_HISTORY, NebError)
+                   PLANE_PREV_POINT, SLOT_CURRENT, SLOT_HISTORY, NebError)
 
 # plane -> (numpy dtype, channels)
 PLANE_LAYOUT = {
@@ -24,6 +24,7 @@ PLANE_LAYOUT = {
     PLANE_ALBEDO: (np.uint32, 1), PLANE_ROUGH_METAL: (np.float16, 2), PLANE_WORLDPOS: (np.float16, 4),
     PLANE_LDR: (np.uint32, 1), PLANE_GEOMETRY: (np.float32, 4), PLANE_HISTORY_LENGTH: (np.uint8, 1),
     PLANE_SUBMESH_ID: (np.uint32, 1),
+    PLANE_PREV_POINT: (np.float32, 4),  # .w holds uint32 bits: the oct16 pair of the previous normal, 0xFFFFFFFF = no per-vertex motion
 }
 
 
@@ -169,6 +170,12 @@ class SVGFDenoiser:
         """neb_svgf_snapshot_transforms: remember the scene's transforms as those slot `slot`'s G-buffer was rendered with (option
         svgf_motion; submit_commands_gbuffer takes its own).  A caller that uploads its own G-buffer calls it next to set_camera."""
         self._check(self._lib.neb_svgf_snapshot_transforms(self._ctx, int(slot), C.c_void_p(stream)), "neb_svgf_snapshot_transforms")
+
+    def snapshot_vertices(self, stream=0):
+        """neb_svgf_snapshot_vertices: the vertex ranges updated since the last call (or submit_commands_gbuffer, which does this by
+        itself) become the "previous" vertices of option svgf_vertex_motion.  A caller that uploads its own G-buffer and
+        PLANE_PREV_POINT calls it once per frame, after the frame's vertex updates."""
+        self._check(self._lib.neb_svgf_snapshot_vertices(self._ctx, C.c_void_p(stream)), "neb_svgf_snapshot_vertices")
 
     def debug_delta_table(self, n_geoms, stream=0):
         """neb_svgf_debug_delta_table -> float32 [n, 32]: the delta kernel's entries for the snapshots of (cur, hist)"""
