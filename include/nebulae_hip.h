@@ -519,6 +519,63 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
  * NEB_ERR_INVALID_ARG for a pointer or stride that is not a multiple of 4 and for a pointer hipPointerGetAttributes does not report as
  * memory of this context's device (or managed / mapped pinned memory), or whose range leaves its allocation. */
 int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream);
+/* Skinned submeshes: the producer neb_gi_update_vertices_device otherwise leaves to the host.  NO reference counterpart
+ * (the reference has no compute skinning).  neb_gi_set_skin binds, per entry, four joint indices and four weights to EVERY vertex of a
+ * geometry (all its numVertices; glTF JOINTS_0 as uint16 x 4 and WEIGHTS_0 as float x 4, HOST pointers, strides in bytes).  It is a set-up
+ * call: it may allocate and wait.  It copies joints and weights to the device, repacked tight, and captures the BIND POSE: a
+ * device-to-device copy, in stream order on `stream` and behind any rewrite enqueued on another stream, of the geometry's spans of the
+ * live position, normal and tangent pools as they are at the call -- so binding after a neb_gi_update_vertices binds the deformed pose.
+ * It also reserves the geometry's share (numJoints x 64 bytes, plus 64 bytes for its range) of the context's one device palette buffer:
+ * neb_gi_skin_vertices never allocates.  Binding again replaces the previous skin and bind pose; joints == NULL removes the geometry's
+ * skin and gives its memory back.  neb_gi_set_scene and neb_destroy forget and free every skin; neb_gi_build_bvh keeps them.
+ * Weights are used as given (not renormalised).
+ * Refusals, each leaving everything unchanged: NEB_ERR_STATE without a scene; NEB_ERR_INVALID_ARG for skins == NULL with n > 0, a geometry
+ * >= n_geoms or named twice, numJoints of 0 or above 65535, NULL weights with joints, a stride below the element size (8 / 16), a joint
+ * index >= numJoints (an influence of weight zero counts: the kernel reads its matrix); NEB_ERR_OUT_OF_RANGE for a weight that is not
+ * finite.  n == 0: NEB_OK. */
+typedef struct neb_skin_desc {
+    uint32_t geometry;      /* index into neb_gi_set_scene's geometries */
+    uint32_t numJoints;     /* size of the palette later handed to neb_gi_skin_vertices; 1 .. 65535 */
+    const void* joints;     /* HOST, uint16 x 4 per vertex (glTF JOINTS_0); NULL = remove this geometry's skin */
+    uint32_t jointStride;   /* bytes, >= 8 */
+    const void* weights;    /* HOST, float x 4 per vertex (glTF WEIGHTS_0), used as given (not renormalised) */
+    uint32_t weightStride;  /* bytes, >= 16 */
+} neb_skin_desc;
+int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_stream stream);
+/* The per-frame call: one palette of joint matrices per named geometry, the library does the rest.  Enqueue only; it never allocates after
+ * the first call has sized the pinned ring.  The palettes travel through the four-slot pinned ring of the other update calls and reach the
+ * device palette buffer in ONE hipMemcpyAsync: the kernels gather four matrices per vertex from device memory, never across the host link.
+ * The chain on `stream`, in the ordering bracket of neb_gi_update_vertices_device: skin_check_kernel (one lane per vertex: the skinned
+ * position and its world point under the geometry's current matrix must be finite, |x| <= 3.0e38, or the WHOLE call is refused on the
+ * device: nothing is written, NEB_OK has long been returned, neb_gi_update_status counts it), skin_scatter_kernel (position, normal and
+ * tangent from the BIND POSE, never from the live pools -- a chain of calls does not drift -- into the pools; a geometry set without its
+ * attribute streams gets positions only), then the kernels of a vertex update unchanged: re-bake, record rewrite (always: normals always
+ * change), boxes, refit levels, requantise, result record.
+ * Arithmetic, one written-down order, every product and every sum rounded by itself (no fused multiply-add): with the four influences
+ * i = 0..3 in the order stored, for rows 0-3 and columns 0-2 of the matrices,  S[q] = ((w0 J0[q] + w1 J1[q]) + w2 J2[q]) + w3 J3[q];
+ * position = (p, 1) * S in the operation order of the bake; normal n'[c] = (n.x S[0][c] + n.y S[1][c]) + n.z S[2][c] (the upper 3x3,
+ * NOT renormalised: the shading normalises each vertex normal at the hit); tangent .xyz as the normal, .w copied.
+ * Host state, sun table, strips, svgf_vertex_motion: exactly a device-sourced update of the whole geometry -- the host copy of its positions
+ * is stale from the enqueue on, its boxes come back in the result record, neb_gi_update_status counts the call once (accepted or refused),
+ * the sun table is dropped and rebuilt by the hold policy against the harvested box, the denoiser follows the figure.
+ * A later neb_gi_update_vertices / _device on a skinned geometry overwrites the pools but NOT the bind pose: the next skin call starts
+ * from the bind pose again.  neb_gi_update_transforms composes (the skin lives in object space).
+ * Refusals at the call, each leaving everything unchanged: NEB_ERR_STATE before a successful neb_gi_build_bvh or for a geometry without
+ * a skin; NEB_ERR_INVALID_ARG for a null pointer with n > 0, a geometry >= n_geoms or named twice; NEB_ERR_OUT_OF_RANGE for a matrix
+ * entry in columns 0-2 that is not finite.  n == 0: NEB_OK, nothing enqueued. */
+typedef struct neb_skin_update {
+    uint32_t geometry;
+    const float* jointMatrices; /* HOST, numJoints x 16: layout and row-vector convention of surfaceToWorld, in the geometry's OBJECT
+                                   space (glTF: inverseBind * jointGlobal * inverse(meshGlobal) in this convention); column 3 is ignored */
+} neb_skin_update;
+int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t n, neb_stream stream);
+/* Copies the current contents of a geometry's spans of the device pools to host arrays: what a host whose own copy has gone stale (a
+ * device-sourced update, a skin call) reads back.  Ordered behind rewrites enqueued on other streams, and it waits for the copies.  Any
+ * geometry, skinned or not; a geometry set without its attribute streams reads zeros for normals and tangents.
+ * Refusals: NEB_ERR_STATE without a scene; NEB_ERR_INVALID_ARG for a geometry >= n_geoms, a range beyond the geometry's numVertices, or
+ * NULL positions with numVertices > 0.  numVertices == 0: NEB_OK. */
+int neb_gi_download_vertices(neb_ctx* ctx, uint32_t geometry, uint32_t firstVertex, uint32_t numVertices, float* positions /* n x 3 */,
+                             float* normals /* n x 3 or NULL */, float* tangents /* n x 4 or NULL */, neb_stream stream);
 /* out = {device-sourced updates accepted, refused on the device} since neb_gi_set_scene.  Waits for every outstanding result record and
  * applies it first, so the counts include every neb_gi_update_vertices_device enqueued before the call. */
 int neb_gi_update_status(neb_ctx* ctx, uint64_t out[2]);

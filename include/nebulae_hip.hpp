@@ -165,6 +165,23 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_update_vertices_device(m_svgf.Context(), updates, n, commandList), "neb_gi_update_vertices_device");
         }
+        // Skinned submeshes: bind joints + weights to every vertex of a geometry (the bind pose is the pools as they are, in stream order) ...
+        void SetSkin(const neb_skin_desc* skins, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_set_skin(m_svgf.Context(), skins, n, commandList), "neb_gi_set_skin");
+        }
+        // ... then one palette of joint matrices per geometry and frame: blended on the device from the bind pose, the tree refitted in place
+        void SkinVertices(const neb_skin_update* updates, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_skin_vertices(m_svgf.Context(), updates, n, commandList), "neb_gi_skin_vertices");
+        }
+        // the pools' current contents of a geometry's vertices (normals / tangents may be null); waits for the copies
+        void DownloadVertices(uint32_t geometry, uint32_t firstVertex, uint32_t numVertices, float* positions, float* normals, float* tangents,
+                              neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_download_vertices(m_svgf.Context(), geometry, firstVertex, numVertices, positions, normals, tangents, commandList),
+                          "neb_gi_download_vertices");
+        }
         // {device-sourced updates accepted, refused on the device}; waits for the updates enqueued so far
         void UpdateStatus(uint64_t out[2]) { ThrowIfFailed(m_svgf.Context(), neb_gi_update_status(m_svgf.Context(), out), "neb_gi_update_status"); }
         // the exact world-space box of the scene; waits like UpdateStatus

@@ -99,6 +99,17 @@ class VertexUpdate(C.Structure):
                 ("tangents", C.c_void_p), ("tangentStride", C.c_uint32)]
 
 
+class SkinDesc(C.Structure):
+    """neb_skin_desc"""
+    _fields_ = [("geometry", C.c_uint32), ("numJoints", C.c_uint32), ("joints", C.c_void_p), ("jointStride", C.c_uint32),
+                ("weights", C.c_void_p), ("weightStride", C.c_uint32)]
+
+
+class SkinUpdate(C.Structure):
+    """neb_skin_update"""
+    _fields_ = [("geometry", C.c_uint32), ("jointMatrices", C.POINTER(C.c_float))]
+
+
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -112,6 +123,10 @@ def _gi_sigs():
         "neb_gi_update_transforms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
         "neb_gi_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_update_vertices_device": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
+        "neb_gi_set_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinDesc), C.c_uint32, C.c_void_p]),
+        "neb_gi_skin_vertices": (C.c_int, [C.c_void_p, C.POINTER(SkinUpdate), C.c_uint32, C.c_void_p]),
+        "neb_gi_download_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                               C.POINTER(C.c_float), C.c_void_p]),
         "neb_gi_update_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
         "neb_gi_scene_box": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
         "neb_gi_scene_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

@@ -76,6 +76,11 @@ void gi_destroy(GiState* g)
         (void)hipHostFree(g->h_vstage);
     if (g->d_vstage)
         (void)hipFree(g->d_vstage);
+    for (GiState::Skin& sk : g->skins)
+        if (sk.d_block)
+            (void)hipFree(sk.d_block);
+    if (g->d_skin_args)
+        (void)hipFree(g->d_skin_args);
     delete g;
 }
 

@@ -323,6 +323,22 @@ struct GiState {
     bool roll_pending = false;
     // One span of a roll in the pinned slot: lanes [first_lane, first_lane + count) copy pool vertices dst .. of geometry geom.
     struct RollSpan { uint32_t first_lane, count, dst, geom; };
+    // ---- skinned submeshes: neb_gi_set_skin / neb_gi_skin_vertices (gi_refit.hip) ----
+    // What neb_gi_set_skin keeps of a geometry, one device allocation of 64 bytes per vertex, every stream tight and 16-byte streams first:
+    // {weights float4 | bind tangents float4 | joints uint16 x 4 | bind positions float3 | bind normals float3} x n_verts.
+    struct Skin {
+        void* d_block = nullptr;
+        uint32_t n_joints = 0; // 0: the geometry has no skin
+    };
+    std::vector<Skin> skins;          // per geometry; empty until the first neb_gi_set_skin
+    uint32_t n_skins = 0, skin_joints = 0; // bound geometries, the sum of their numJoints
+    // One range of a skin call beside its DeformRange: the geometry's block and where its palette starts among the call's matrices.
+    struct SkinSource { const uint8_t* block; uint32_t n_verts, pal_first, n_joints, attrs, pad[2]; };
+    // The per-context palette buffer: what a skin call copies to the device in ONE hipMemcpyAsync from its pinned slot --
+    // {DeformRange x n | SkinSource x n | 16 floats x the joints of the n geometries}.  Sized by neb_gi_set_skin for a call that names
+    // every bound geometry (64 bytes of ranges + 64 bytes per joint: the geometry's share), so a skin call never allocates.
+    void* d_skin_args = nullptr;
+    size_t skin_args_cap = 0;
     // Streams that have read triangles / nodes / geometry tables since the last update: an update on another stream orders itself
     // behind them (an event recorded on each, waited for on its own stream).  More than kReaderStreams: it waits for the device.
     static constexpr int kReaderStreams = 4;

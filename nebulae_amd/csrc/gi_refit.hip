@@ -14,6 +14,10 @@
 // neb_gi_update_vertices_device is that update with sources the host never reads: a check kernel validates them, the
 // scatter reads them where they lie, geom_box_kernel reduces the boxes the host used to fold from h_pos, and one small copy at the end
 // of the chain brings {refusal word, boxes} back to a pinned result record the host harvests later (gi_harvest_results).
+//
+// neb_gi_set_skin / neb_gi_skin_vertices are the producer such a host otherwise brings itself: joints, weights and the
+// bind pose of a geometry stay on the device, a call hands over one palette of joint matrices per geometry, skin_check_kernel and
+// skin_scatter_kernel stand where the check and the scatter of the device-sourced update stand, and the rest of its chain follows.
 #include <algorithm>
 
 #include "gi_device.h"
@@ -244,6 +248,128 @@ __global__ void deform_check_kernel(const GiState::DeformRange* __restrict__ ran
         atomicOr(refused, 1u);
 }
 
+// ---- skinning ----
+// The lane's range by the scatter's bisection, its source and its vertex inside the geometry; false: the lane has nothing to do.
+__device__ __forceinline__ bool skin_lane(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::SkinSource* __restrict__ sources,
+                                          uint32_t k, uint32_t n_geoms, GiState::DeformRange& r, GiState::SkinSource& s, uint32_t& j)
+{
+    uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[mid].first_lane <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    r = ranges[lo];
+    s = sources[lo];
+    j = k - r.first_lane;
+    return j < r.count && j < s.n_verts && r.geom < n_geoms && s.n_joints != 0u;
+}
+// The blended matrix of vertex j, THE written order: S[q] = ((w0 J0[q] + w1 J1[q]) + w2 J2[q]) + w3 J3[q] for rows 0-3, columns 0-2, every
+// product and every sum rounded by itself (rounded_product, __fadd_rn).  Column 3 of the joint matrices is never read.  A joint index is
+// clamped to the palette (neb_gi_set_skin refused the skin that has one beyond it: the clamp only keeps the read inside the buffer).
+__device__ __forceinline__ void skin_blend(const GiState::SkinSource& s, const float* __restrict__ palette, uint32_t j, float S[16])
+{
+    const float4 w = reinterpret_cast<const float4*>(s.block)[j];
+    const uint2 jj = reinterpret_cast<const uint2*>(s.block + 32 * (size_t)s.n_verts)[j];
+    const uint32_t last = s.n_joints - 1u;
+    // (a matrix is one 64-byte line of the palette buffer: four 16-byte loads each; column 3 comes along and is dropped)
+    const float4* J0 = reinterpret_cast<const float4*>(palette) + 4 * (size_t)(s.pal_first + min(jj.x & 0xffffu, last));
+    const float4* J1 = reinterpret_cast<const float4*>(palette) + 4 * (size_t)(s.pal_first + min(jj.x >> 16, last));
+    const float4* J2 = reinterpret_cast<const float4*>(palette) + 4 * (size_t)(s.pal_first + min(jj.y & 0xffffu, last));
+    const float4* J3 = reinterpret_cast<const float4*>(palette) + 4 * (size_t)(s.pal_first + min(jj.y >> 16, last));
+#pragma unroll
+    for (int row = 0; row < 4; ++row) {
+        const float4 a = J0[row], b = J1[row], c = J2[row], d = J3[row];
+        S[4 * row] = __fadd_rn(__fadd_rn(__fadd_rn(rounded_product(w.x, a.x), rounded_product(w.y, b.x)), rounded_product(w.z, c.x)), rounded_product(w.w, d.x));
+        S[4 * row + 1] = __fadd_rn(__fadd_rn(__fadd_rn(rounded_product(w.x, a.y), rounded_product(w.y, b.y)), rounded_product(w.z, c.y)), rounded_product(w.w, d.y));
+        S[4 * row + 2] = __fadd_rn(__fadd_rn(__fadd_rn(rounded_product(w.x, a.z), rounded_product(w.y, b.z)), rounded_product(w.z, c.z)), rounded_product(w.w, d.z));
+        S[4 * row + 3] = 0.f;
+    }
+}
+__device__ __forceinline__ const float* skin_bind_pos(const GiState::SkinSource& s, uint32_t j)
+{
+    return reinterpret_cast<const float*>(s.block + 40 * (size_t)s.n_verts) + 3 * (size_t)j;
+}
+// n' = n * upper 3x3 of S, left to right, not renormalised (the shading normalises every vertex normal at the hit)
+__device__ __forceinline__ float3 skin_direction(const float* S, float x, float y, float z)
+{
+    float3 d;
+    d.x = __fadd_rn(__fadd_rn(rounded_product(x, S[0]), rounded_product(y, S[4])), rounded_product(z, S[8]));
+    d.y = __fadd_rn(__fadd_rn(rounded_product(x, S[1]), rounded_product(y, S[5])), rounded_product(z, S[9]));
+    d.z = __fadd_rn(__fadd_rn(rounded_product(x, S[2]), rounded_product(y, S[6])), rounded_product(z, S[10]));
+    return d;
+}
+
+// One lane per vertex of the skinned geometries a call names: the skinned position, and the world point under the geometry's current
+// matrix, must be finite within gi_bake_point's bound; a failing lane sets the call's refusal word (deform_check_kernel's contract).
+__global__ void skin_check_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::SkinSource* __restrict__ sources,
+                                  const float* __restrict__ palette, uint32_t n_lanes, uint32_t n_geoms, const float* __restrict__ xf,
+                                  uint32_t* __restrict__ refused)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    GiState::DeformRange r;
+    GiState::SkinSource s;
+    uint32_t j;
+    if (!skin_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j))
+        return;
+    float S[16];
+    skin_blend(s, palette, j, S);
+    const float* bp = skin_bind_pos(s, j);
+    const float p[3] = {bp[0], bp[1], bp[2]};
+    const float3 a3 = bake_point(S, p);
+    const float a[3] = {a3.x, a3.y, a3.z};
+    const float3 w = bake_point(xf + 16 * (size_t)r.geom, a);
+    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
+                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
+    if (!ok)
+        atomicOr(refused, 1u);
+}
+
+// One lane per vertex: position, normal and tangent from the BIND pose (never the live pools: a chain of calls does not drift) under the
+// blended matrix, into the pools.  The whole launch leaves at once when skin_check_kernel has set the refusal word.  Lane 0 of a range
+// stamps its geometry and, with option svgf_vertex_motion, sets its dirty word -- as deform_scatter_kernel does.  A geometry set without
+// its attribute streams (attrs == 0) gets positions only.
+__global__ void skin_scatter_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::SkinSource* __restrict__ sources,
+                                    const float* __restrict__ palette, uint32_t n_lanes, uint32_t n_pool, uint32_t n_geoms, uint32_t epoch,
+                                    float* __restrict__ pos, float* __restrict__ normals, float* __restrict__ tangents, uint32_t* __restrict__ geom_epoch,
+                                    const uint32_t* __restrict__ refused, uint32_t* __restrict__ deform_dirty)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    if (*refused)
+        return;
+    GiState::DeformRange r;
+    GiState::SkinSource s;
+    uint32_t j;
+    if (!skin_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || r.dst + j >= n_pool)
+        return;
+    const size_t v = (size_t)r.dst + j;
+    float S[16];
+    skin_blend(s, palette, j, S);
+    const float* bp = skin_bind_pos(s, j);
+    const float p[3] = {bp[0], bp[1], bp[2]};
+    const float3 a = bake_point(S, p);
+    pos[3 * v] = a.x, pos[3 * v + 1] = a.y, pos[3 * v + 2] = a.z;
+    if (s.attrs) {
+        const float* bn = reinterpret_cast<const float*>(s.block + 52 * (size_t)s.n_verts) + 3 * (size_t)j;
+        const float4 bt = reinterpret_cast<const float4*>(s.block + 16 * (size_t)s.n_verts)[j];
+        const float3 n = skin_direction(S, bn[0], bn[1], bn[2]);
+        const float3 t = skin_direction(S, bt.x, bt.y, bt.z);
+        normals[3 * v] = n.x, normals[3 * v + 1] = n.y, normals[3 * v + 2] = n.z;
+        tangents[4 * v] = t.x, tangents[4 * v + 1] = t.y, tangents[4 * v + 2] = t.z, tangents[4 * v + 3] = bt.w;
+    }
+    if (j == 0) {
+        geom_epoch[r.geom] = epoch;
+        if (deform_dirty)
+            deform_dirty[r.geom] = 1u;
+    }
+}
+
 // the result record of a call before its chain: {call, refusal word = 0, entries, 0}, every box word at the neutral element of atomicMin
 __global__ void result_init_kernel(uint32_t* __restrict__ res, uint32_t call, uint32_t n_entries)
 {
@@ -398,6 +524,56 @@ static hipError_t refit_enqueue_levels(GiState* g, uint32_t call, hipStream_t st
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
     return gi_quantise_nodes(g->view.nodes, g->n_nodes, const_cast<Bvh4NodeQ*>(g->view.qnodes), stream);
+}
+
+// ---- what every update call does with the ring and with the end of its chain ----
+// The pinned vertex staging holds at least `bytes` per slot; when it has to grow it grows to `want` (>= bytes), rounded up to pages.
+// Growing frees the ring: every update that may still read it has to be done first.
+static hipError_t vstage_reserve(GiState* g, size_t bytes, size_t want)
+{
+    if (bytes <= g->vstage_cap)
+        return hipSuccess;
+    for (int q = 0; q < GiState::kStageSlots; ++q)
+        if (g->stage_used[q])
+            if (hipError_t e = hipEventSynchronize(g->stage_ev[q]); e != hipSuccess)
+                return e;
+    void* fresh = nullptr;
+    const size_t cap = (std::max(bytes, want) + 4095u) & ~(size_t)4095u;
+    if (hipError_t e = hipHostMalloc(&fresh, cap * GiState::kStageSlots, hipHostMallocDefault); e != hipSuccess)
+        return e;
+    if (g->h_vstage)
+        (void)hipHostFree(g->h_vstage);
+    g->h_vstage = fresh;
+    g->vstage_cap = cap;
+    return hipSuccess;
+}
+// the slot of update `call`: its event exists, and the update kStageSlots calls ago has read it (long done unless the host runs that far ahead)
+static hipError_t stage_slot_acquire(GiState* g, uint32_t call, int* slot)
+{
+    const int s = (int)(call % (uint32_t)GiState::kStageSlots);
+    *slot = s;
+    if (!g->stage_ev[s])
+        if (hipError_t e = hipEventCreateWithFlags(&g->stage_ev[s], hipEventDisableTiming); e != hipSuccess)
+            return e;
+    return g->stage_used[s] ? hipEventSynchronize(g->stage_ev[s]) : hipSuccess;
+}
+static hipError_t results_enqueue_boxes(GiState* g, int slot, uint32_t n_entries, hipStream_t stream);
+// what follows the kernel that stamped the geometries: their triangles baked again, the normal and tangent words of their records where
+// these changed, the boxes of the slot's entry list, the levels of the tree, the 64-byte nodes
+static hipError_t refit_enqueue_rewrite(GiState* g, int slot, uint32_t call, bool repack, uint32_t n_boxed, hipStream_t stream)
+{
+    const uint32_t n_slots = g->view.n_tris;
+    hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
+                       (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
+    if (repack)
+        hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
+                           reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
+                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->view.normals, g->view.tangents);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    if (hipError_t e = results_enqueue_boxes(g, slot, n_boxed, stream); e != hipSuccess)
+        return e;
+    return refit_enqueue_levels(g, call, stream);
 }
 
 // ---- boxes reduced on the device, result records ----
@@ -762,11 +938,8 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
     hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
     // ---- the argument slot: pinned host memory the first kernel reads ----
-    const int slot = (int)(call % (uint32_t)GiState::kStageSlots);
-    if (!g->stage_ev[slot])
-        GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
-    if (g->stage_used[slot])
-        GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
+    int slot = 0;
+    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
     if (any_stale)
         GI_HIP(ctx, results_acquire(g, slot));
     if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
@@ -814,10 +987,7 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
     GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
     g->stage_used[slot] = true;
     if (any_tris && n_slots) {
-        hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
-                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
-        GI_HIP(ctx, results_enqueue_boxes(g, slot, (uint32_t)boxed.size(), stream));
-        GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
+        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, false, (uint32_t)boxed.size(), stream));
     }
     if (!boxed.empty()) {
         g->result_rec[slot].geoms = std::move(boxed);
@@ -896,18 +1066,7 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
     // ---- the staging slot: pinned host memory, {ranges | positions | normals | tangents}, grown to the largest update seen ----
     const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
     const size_t bytes = head + 4u * (3u * n_lanes + 3u * n_nrm + 4u * n_tan);
-    if (bytes > g->vstage_cap) {
-        for (int q = 0; q < GiState::kStageSlots; ++q) // (growing frees the ring: every update that may still read it has to be done)
-            if (g->stage_used[q])
-                GI_HIP(ctx, hipEventSynchronize(g->stage_ev[q]));
-        void* fresh = nullptr;
-        const size_t cap = (bytes + 4095u) & ~(size_t)4095u;
-        GI_HIP(ctx, hipHostMalloc(&fresh, cap * GiState::kStageSlots, hipHostMallocDefault));
-        if (g->h_vstage)
-            (void)hipHostFree(g->h_vstage);
-        g->h_vstage = fresh;
-        g->vstage_cap = cap;
-    }
+    GI_HIP(ctx, vstage_reserve(g, bytes, bytes));
     if (g->deform_stage == 1 && g->vstage_cap > g->d_vstage_cap) {
         void* fresh = nullptr;
         GI_HIP(ctx, hipMalloc(&fresh, g->vstage_cap));
@@ -917,11 +1076,8 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         g->d_vstage_cap = g->vstage_cap;
     }
     const uint32_t call = g->epoch + 1u;
-    const int slot = (int)(call % (uint32_t)GiState::kStageSlots);
-    if (!g->stage_ev[slot])
-        GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
-    if (g->stage_used[slot])
-        GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
+    int slot = 0;
+    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
     if (!boxed.empty())
         GI_HIP(ctx, results_acquire(g, slot));
     if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
@@ -1009,14 +1165,7 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
     GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
     g->stage_used[slot] = true;
     if (any_tris && n_slots) {
-        hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
-                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
-        if (any_attr)
-            hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
-                               reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
-                               (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->view.normals, g->view.tangents);
-        GI_HIP(ctx, results_enqueue_boxes(g, slot, (uint32_t)boxed.size(), stream));
-        GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
+        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, any_attr, (uint32_t)boxed.size(), stream));
     }
     if (!boxed.empty()) {
         g->result_rec[slot].geoms = std::move(boxed);
@@ -1085,24 +1234,10 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
     // ---- the staging slot: pinned host memory, here {ranges | sources} only ----
     const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
     const size_t bytes = head + spans.size() * sizeof(GiState::DeformSource);
-    if (bytes > g->vstage_cap) {
-        for (int q = 0; q < GiState::kStageSlots; ++q) // (growing frees the ring: every update that may still read it has to be done)
-            if (g->stage_used[q])
-                GI_HIP(ctx, hipEventSynchronize(g->stage_ev[q]));
-        void* fresh = nullptr;
-        const size_t cap = (bytes + 4095u) & ~(size_t)4095u;
-        GI_HIP(ctx, hipHostMalloc(&fresh, cap * GiState::kStageSlots, hipHostMallocDefault));
-        if (g->h_vstage)
-            (void)hipHostFree(g->h_vstage);
-        g->h_vstage = fresh;
-        g->vstage_cap = cap;
-    }
+    GI_HIP(ctx, vstage_reserve(g, bytes, bytes));
     const uint32_t call = g->epoch + 1u;
-    const int slot = (int)(call % (uint32_t)GiState::kStageSlots);
-    if (!g->stage_ev[slot])
-        GI_HIP(ctx, hipEventCreateWithFlags(&g->stage_ev[slot], hipEventDisableTiming));
-    if (g->stage_used[slot])
-        GI_HIP(ctx, hipEventSynchronize(g->stage_ev[slot])); // (the update kStageSlots calls ago: long done unless the host runs that far ahead)
+    int slot = 0;
+    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
     GI_HIP(ctx, results_acquire(g, slot));
     if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
         return rc;
@@ -1155,17 +1290,281 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
     GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
     g->stage_used[slot] = true;
     if (any_tris && n_slots) {
-        hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
-                           (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
-        if (any_attr)
-            hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
-                               reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
-                               (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, g->view.normals, g->view.tangents);
-        GI_HIP(ctx, results_enqueue_boxes(g, slot, n_boxed, stream));
-        GI_HIP(ctx, refit_enqueue_levels(g, call, stream));
+        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, any_attr, n_boxed, stream));
     }
     GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
     GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+// ---- skinned submeshes ----
+int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_set_skin: no scene (call neb_gi_set_scene first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!skins)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: null pointer");
+    if (n > g->n_geoms)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: more entries than geometries (an index is out of range or named twice)");
+    // ---- everything that can refuse the call comes before anything changes ----
+    const uint32_t stamp = ++g->seen_stamp;
+    uint32_t n_skins = g->n_skins, n_joints = g->skin_joints;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_skin_desc& d = skins[k];
+        if (d.geometry >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: geometry index out of range");
+        if (g->h_seen[d.geometry] == stamp)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: a geometry is named twice");
+        g->h_seen[d.geometry] = stamp;
+        if (!g->skins.empty() && g->skins[d.geometry].n_joints)
+            n_skins -= 1u, n_joints -= g->skins[d.geometry].n_joints;
+        if (!d.joints)
+            continue; // (remove)
+        if (d.numJoints == 0 || d.numJoints > 65535u)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: numJoints must be 1 .. 65535");
+        if (!d.weights)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: joints without weights");
+        if (d.jointStride < 8u || d.weightStride < 16u)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: a stride is smaller than its element");
+        n_skins += 1u, n_joints += d.numJoints;
+        const uint32_t nv = g->h_geoms[d.geometry].n_verts;
+        for (uint32_t v = 0; v < nv; ++v) {
+            uint16_t j4[4];
+            float w4[4];
+            memcpy(j4, (const uint8_t*)d.joints + (size_t)v * d.jointStride, 8);
+            memcpy(w4, (const uint8_t*)d.weights + (size_t)v * d.weightStride, 16);
+            for (int q = 0; q < 4; ++q) {
+                if (j4[q] >= d.numJoints) // (an influence of weight zero counts: the kernel reads its matrix)
+                    return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: a joint index is not below numJoints");
+                if (!std::isfinite(w4[q]))
+                    return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_set_skin: a weight is not a finite number");
+            }
+        }
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    // ---- what the call needs is allocated before anything is let go of ----
+    std::vector<void*> fresh(n, nullptr);
+    void* fresh_args = nullptr;
+    const size_t args_cap = (size_t)64 * n_skins + (size_t)64 * n_joints;
+    hipError_t e = hipSuccess;
+    for (uint32_t k = 0; k < n && e == hipSuccess; ++k)
+        if (skins[k].joints)
+            e = hipMalloc(&fresh[k], std::max<size_t>(64, (size_t)64 * g->h_geoms[skins[k].geometry].n_verts));
+    if (e == hipSuccess && args_cap && args_cap != g->skin_args_cap)
+        e = hipMalloc(&fresh_args, args_cap);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize(); // (a set-up call: a skin call still in flight reads the blocks and the palette buffer about to be replaced)
+    // Everything that can still fail fills the FRESH blocks: joints and weights repacked tight, and the bind pose -- read behind a rewrite
+    // enqueued on another stream (gi_scene_reader; a later rewrite waits for the copies).  Nothing of the context has changed yet.
+    if (e == hipSuccess)
+        e = gi_scene_reader(g, stream);
+    std::vector<uint16_t> hj;
+    std::vector<float> hw;
+    for (uint32_t k = 0; k < n && e == hipSuccess; ++k) {
+        const neb_skin_desc& d = skins[k];
+        const GiState::HostGeom& hg = g->h_geoms[d.geometry];
+        const size_t nv = hg.n_verts;
+        if (!d.joints || !nv)
+            continue;
+        hj.resize(4 * nv), hw.resize(4 * nv);
+        for (size_t v = 0; v < nv; ++v) {
+            memcpy(&hj[4 * v], (const uint8_t*)d.joints + v * d.jointStride, 8);
+            memcpy(&hw[4 * v], (const uint8_t*)d.weights + v * d.weightStride, 16);
+        }
+        uint8_t* b = (uint8_t*)fresh[k];
+        e = hipMemcpy(b, hw.data(), 16 * nv, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpy(b + 32 * nv, hj.data(), 8 * nv, hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b + 40 * nv, g->d_pos + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b + 52 * nv, g->view.normals + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b + 16 * nv, g->view.tangents + 4 * (size_t)hg.vertexBase, 16 * nv, hipMemcpyDeviceToDevice, stream);
+    }
+    if (e != hipSuccess) {
+        for (void* p : fresh)
+            if (p)
+                (void)hipFree(p); // (waits for the device: a copy into the block that was enqueued is done)
+        if (fresh_args)
+            (void)hipFree(fresh_args);
+        return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_skin: device memory", e);
+    }
+    // ---- commit: nothing below can fail ----
+    if (g->skins.empty())
+        g->skins.resize(g->n_geoms);
+    if (args_cap != g->skin_args_cap) {
+        if (g->d_skin_args)
+            (void)hipFree(g->d_skin_args);
+        g->d_skin_args = fresh_args;
+        g->skin_args_cap = args_cap;
+    }
+    g->n_skins = n_skins, g->skin_joints = n_joints;
+    for (uint32_t k = 0; k < n; ++k) {
+        GiState::Skin& sk = g->skins[skins[k].geometry];
+        if (sk.d_block)
+            (void)hipFree(sk.d_block);
+        sk = GiState::Skin();
+        if (skins[k].joints) {
+            sk.d_block = fresh[k];
+            sk.n_joints = skins[k].numJoints;
+        }
+    }
+    return NEB_OK;
+}
+
+int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_skin_vertices: no built scene (neb_gi_set_scene + neb_gi_build_bvh first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!updates)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: null pointer");
+    if (n > g->n_geoms)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: more entries than geometries (an index is out of range or named twice)");
+    GI_HIP(ctx, gi_harvest_results(g, false));
+    // ---- everything the HOST can refuse the call for comes before anything changes (the skinned vertices themselves: skin_check_kernel) ----
+    const uint32_t stamp = ++g->seen_stamp;
+    struct Span { uint32_t geom, k; };
+    std::vector<Span> spans;
+    spans.reserve(n);
+    size_t n_lanes = 0, n_mats = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_skin_update& u = updates[k];
+        if (u.geometry >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: geometry index out of range");
+        if (g->h_seen[u.geometry] == stamp)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: a geometry is named twice");
+        g->h_seen[u.geometry] = stamp;
+        if (!u.jointMatrices)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: null jointMatrices");
+        if (g->skins.empty() || !g->skins[u.geometry].n_joints)
+            return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_skin_vertices: the geometry has no skin (neb_gi_set_skin first)");
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_skin_update& u = updates[k];
+        const uint32_t nj = g->skins[u.geometry].n_joints;
+        for (uint32_t q = 0; q < 16u * nj; ++q)
+            if ((q & 3u) != 3u && !std::isfinite(u.jointMatrices[q]))
+                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_skin_vertices: a joint matrix entry (columns 0-2) is not a finite number");
+        if (g->h_geoms[u.geometry].n_verts == 0)
+            continue; // (no lane: a range is never empty)
+        spans.push_back({u.geometry, k});
+        n_lanes += g->h_geoms[u.geometry].n_verts;
+        n_mats += nj;
+    }
+    if (n_lanes > 0xffffffffull / 10u) // (the bound of neb_gi_update_vertices: lanes are 32-bit)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: too many vertices in one call");
+    if (spans.empty())
+        return NEB_OK;
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom < b.geom; });
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    GI_HIP(ctx, results_prepare(g));
+    // ---- the staging slot: pinned host memory, {ranges | sources | palettes}, copied to the palette buffer in one piece ----
+    const size_t head = spans.size() * sizeof(GiState::DeformRange), src_bytes = spans.size() * sizeof(GiState::SkinSource);
+    const size_t bytes = head + src_bytes + 64u * n_mats;
+    static_assert(sizeof(GiState::DeformRange) == 32 && sizeof(GiState::SkinSource) == 32, "64 bytes of ranges per bound geometry (neb_gi_set_skin)");
+    if (bytes > g->skin_args_cap)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_skin_vertices: the palette buffer is smaller than the call (internal)");
+    GI_HIP(ctx, vstage_reserve(g, bytes, std::max(bytes, g->skin_args_cap))); // (at once for a call that names every skin)
+    const uint32_t call = g->epoch + 1u;
+    int slot = 0;
+    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
+    GI_HIP(ctx, results_acquire(g, slot));
+    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+        return rc;
+    // ---- commit the host side: the slot; h_pos is left behind (host_stale), the boxes follow with the result record ----
+    g->epoch = call;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    GiState::DeformRange* ranges = (GiState::DeformRange*)base;
+    GiState::SkinSource* sources = (GiState::SkinSource*)(base + head);
+    float* palette = (float*)(base + head + src_bytes);
+    uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
+    GiState::ResultRecord& rec = g->result_rec[slot];
+    rec.geoms.clear();
+    uint32_t lane = 0, mat = 0;
+    bool any_tris = false;
+    for (size_t i = 0; i < spans.size(); ++i) {
+        const uint32_t gi = spans[i].geom;
+        GiState::HostGeom& hg = g->h_geoms[gi];
+        const GiState::Skin& sk = g->skins[gi];
+        ranges[i] = {lane, hg.n_verts, hg.vertexBase, gi, 0u, hg.valid ? 0u : GiState::kNoStream, hg.valid ? 0u : GiState::kNoStream, 0u};
+        sources[i] = {(const uint8_t*)sk.d_block, hg.n_verts, mat, sk.n_joints, hg.valid ? 1u : 0u, {0u, 0u}};
+        memcpy(palette + 16 * (size_t)mat, updates[spans[i].k].jointMatrices, 64 * (size_t)sk.n_joints);
+        roll_mark(g, gi, 0, hg.n_verts); // (the host cannot know of a refusal on the device: the roll then copies equal values)
+        lane += hg.n_verts, mat += sk.n_joints;
+        hg.host_stale = true;
+        if (hg.n_tris) {
+            hg.dirty = true;
+            any_tris = true;
+            list[rec.geoms.size()] = gi;
+            rec.geoms.push_back(gi);
+        }
+    }
+    if (any_tris)
+        refit_drop_sun_table(g);
+    // ---- enqueue: arguments, check, skin, bake, records, boxes, levels, quantise, the record back ----
+    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3), n_boxed = (uint32_t)rec.geoms.size();
+    uint32_t* d_res = g->d_result + (size_t)slot * result_stride(g);
+    const uint8_t* d_args = (const uint8_t*)g->d_skin_args;
+    GI_HIP(ctx, results_enqueue_init(g, slot, call, n_boxed, stream));
+    GI_HIP(ctx, hipMemcpyAsync(g->d_skin_args, base, bytes, hipMemcpyHostToDevice, stream));
+    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
+    g->stage_used[slot] = true;
+    hipLaunchKernelGGL(skin_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+                       (const GiState::SkinSource*)(d_args + head), (const float*)(d_args + head + src_bytes), lane, g->n_geoms, (const float*)g->d_xf,
+                       d_res + 1);
+    hipLaunchKernelGGL(skin_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+                       (const GiState::SkinSource*)(d_args + head), (const float*)(d_args + head + src_bytes), lane, n_pool, g->n_geoms, call, g->d_pos,
+                       const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)(d_res + 1),
+                       g->d_deform_dirty);
+    GI_HIP(ctx, hipGetLastError());
+    if (any_tris && n_slots) {
+        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, true, n_boxed, stream));
+    }
+    GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
+    GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+int neb_gi_download_vertices(neb_ctx* ctx, uint32_t geometry, uint32_t firstVertex, uint32_t numVertices, float* positions, float* normals,
+                             float* tangents, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_download_vertices: no scene (call neb_gi_set_scene first)");
+    if (geometry >= g->n_geoms)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_download_vertices: geometry index out of range");
+    const GiState::HostGeom& hg = g->h_geoms[geometry];
+    if ((uint64_t)firstVertex + numVertices > hg.n_verts)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_download_vertices: vertex range beyond the geometry's numVertices");
+    if (numVertices == 0)
+        return NEB_OK;
+    if (!positions)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_download_vertices: null positions");
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // a rewrite enqueued on another stream comes first; a later one waits for these copies
+    const size_t v = (size_t)hg.vertexBase + firstVertex;
+    GI_HIP(ctx, hipMemcpyAsync(positions, g->d_pos + 3 * v, 12 * (size_t)numVertices, hipMemcpyDeviceToHost, stream));
+    if (normals)
+        GI_HIP(ctx, hipMemcpyAsync(normals, g->view.normals + 3 * v, 12 * (size_t)numVertices, hipMemcpyDeviceToHost, stream));
+    if (tangents)
+        GI_HIP(ctx, hipMemcpyAsync(tangents, g->view.tangents + 4 * v, 16 * (size_t)numVertices, hipMemcpyDeviceToHost, stream));
+    GI_HIP(ctx, hipStreamSynchronize(stream));
     return NEB_OK;
 }
 

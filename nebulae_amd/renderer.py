@@ -209,6 +209,89 @@ class DeferredRenderer:
                 full[first_vertex:first_vertex + n] = t.cpu().numpy()
                 gm[key] = full
 
+    # ---- skinned submeshes (neb_gi_set_skin / neb_gi_skin_vertices: DESIGN.md 3.4d); nothing here computes a skin on the CPU ----
+    def set_skin(self, index, joints, weights, num_joints, stream=None):
+        """Bind a skin to geometry `index`: joints (n x 4 integers below num_joints, glTF JOINTS_0) and weights (n x 4 float32, used as
+        given) for every one of its vertices.  The bind pose is what the device pools hold at the call (neb_gi_set_skin)."""
+        if self._scene is None:
+            raise NebError("set_skin: no scene (init_pathtracer_scene first)")
+        index, num_joints = int(index), int(num_joints)
+        if not 0 <= index < len(self._scene.geometries) or not 0 <= num_joints <= 0xFFFFFFFF:
+            raise NebError("set_skin: geometry index or num_joints out of range")
+        j = np.asarray(joints).reshape(-1, 4)
+        if j.size and (j.min() < 0 or j.max() > 0xFFFF):
+            raise NebError("set_skin: a joint index does not fit 16 bits")
+        j = np.ascontiguousarray(j.astype(np.uint16))
+        w = np.ascontiguousarray(np.asarray(weights, np.float32).reshape(-1, 4))
+        nv = len(self._scene.geometries[index]["positions"])
+        if j.shape[0] != nv or w.shape[0] != nv:
+            raise NebError(f"set_skin: the geometry has {nv} vertices but {j.shape[0]} joints / {w.shape[0]} weights rows were given")
+        d = _lib.SkinDesc(geometry=index, numJoints=num_joints, joints=j.ctypes.data, jointStride=8, weights=w.ctypes.data, weightStride=16)
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        self._check(self._lib.neb_gi_set_skin(self._ctx, C.byref(d), 1, st), "neb_gi_set_skin")
+
+    def remove_skin(self, index, stream=None):
+        """Let go of geometry `index`'s skin and bind pose (the pools keep what they hold)."""
+        if self._scene is None:
+            raise NebError("remove_skin: no scene (init_pathtracer_scene first)")
+        index = int(index)
+        if not 0 <= index < len(self._scene.geometries):
+            raise NebError("remove_skin: geometry index out of range")
+        d = _lib.SkinDesc(geometry=index)
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        self._check(self._lib.neb_gi_set_skin(self._ctx, C.byref(d), 1, st), "neb_gi_set_skin")
+
+    def skin_vertices(self, index, joint_matrices, stream=None, mirror=False):
+        """Skin geometries on the device (neb_gi_skin_vertices): `index` is one geometry or a sequence of them, `joint_matrices` its palette
+        (num_joints x 4 x 4, layout and convention of Scene.add_geometry's M, object space) or one palette per geometry -- all in ONE call.
+        The call only enqueues; a skinned vertex that is not finite refuses the whole call on the device, later: see update_status.
+        mirror=True follows update_vertices_device: after the enqueue, and only if the device accepted, the scene object's arrays are
+        refreshed through download_vertices (the call then waits)."""
+        if self._scene is None:
+            raise NebError("skin_vertices: no scene (init_pathtracer_scene first)")
+        if np.ndim(index) == 0:
+            index, joint_matrices = [index], [joint_matrices]
+        idx = [int(i) for i in index]
+        if len(idx) != len(joint_matrices):
+            raise NebError(f"skin_vertices: {len(idx)} geometries but {len(joint_matrices)} palettes")
+        if any(not 0 <= i < len(self._scene.geometries) for i in idx):
+            raise NebError("skin_vertices: geometry index out of range")
+        pals = [np.ascontiguousarray(np.asarray(m, np.float32).reshape(-1, 16)) for m in joint_matrices]
+        ups = (_lib.SkinUpdate * max(len(idx), 1))()
+        for k, (i, p) in enumerate(zip(idx, pals)):
+            ups[k].geometry = i
+            ups[k].jointMatrices = p.ctypes.data_as(C.POINTER(C.c_float))
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        refused = self.update_status()["refused"] if mirror else 0  # (harvests every earlier update: the difference below is this call's)
+        self._check(self._lib.neb_gi_skin_vertices(self._ctx, ups, len(idx), st), "neb_gi_skin_vertices")
+        if mirror and self.update_status()["refused"] == refused:
+            for i in idx:
+                gm = self._scene.geometries[i]
+                p, n, t = self.download_vertices(i, stream=st.value or 0)
+                gm["positions"] = p
+                if all(gm.get(key) is not None for key in ("normals", "uvs", "tangents")):  # (else the library skins positions only)
+                    gm["normals"], gm["tangents"] = n, t
+
+    def download_vertices(self, index, first_vertex=0, n=None, stream=None):
+        """-> positions (n x 3), normals (n x 3), tangents (n x 4): what the device pools hold now of geometry `index`'s vertices
+        [first_vertex, first_vertex + n) (n=None: to its end).  Waits for the copies (neb_gi_download_vertices)."""
+        if self._scene is None:
+            raise NebError("download_vertices: no scene (init_pathtracer_scene first)")
+        index, first_vertex = int(index), int(first_vertex)
+        if not 0 <= index < len(self._scene.geometries) or not 0 <= first_vertex <= 0xFFFFFFFF:
+            raise NebError("download_vertices: geometry index or first vertex out of range")
+        if n is None:
+            n = max(len(self._scene.geometries[index]["positions"]) - first_vertex, 0)
+        n = int(n)
+        if not 0 <= n <= 0xFFFFFFFF:
+            raise NebError("download_vertices: vertex count out of range")
+        p, nr, t = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 4), np.float32)
+        fp = C.POINTER(C.c_float)
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        self._check(self._lib.neb_gi_download_vertices(self._ctx, index, first_vertex, n, p.ctypes.data_as(fp), nr.ctypes.data_as(fp),
+                                                       t.ctypes.data_as(fp), st), "neb_gi_download_vertices")
+        return p, nr, t
+
     def update_status(self):
         """{"accepted", "refused"}: device-sourced updates applied / refused on the device (a position that was not finite) since the scene
         was set.  Waits for the updates enqueued so far."""
