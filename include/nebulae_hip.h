@@ -569,6 +569,59 @@ typedef struct neb_skin_update {
                                    space (glTF: inverseBind * jointGlobal * inverse(meshGlobal) in this convention); column 3 is ignored */
 } neb_skin_update;
 int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t n, neb_stream stream);
+/* Morph targets: the other half of glTF mesh animation, blended by the library, alone or under a skin.  NO reference
+ * counterpart.  neb_gi_set_morph_targets binds, per entry, numTargets targets to EVERY vertex of a geometry: per target one float3 stream
+ * of position deltas (glTF target POSITION; required), and optionally of normal and of tangent deltas (glTF: vec3, .w is not morphed) --
+ * arrays of numTargets HOST pointers, strides in bytes.  It is a set-up call: it may allocate and wait.  It uploads the deltas repacked
+ * tight and target-major, and captures the REST POSE: a device-to-device copy, in stream order on `stream` and behind any rewrite
+ * enqueued on another stream, of the geometry's spans of the live position, normal and tangent pools as they are at the call -- so
+ * binding after a neb_gi_update_vertices binds the deformed pose.  It also reserves the geometry's share of the context's one device
+ * argument buffer (the palette buffer of the skin calls: 96 bytes, 8 per target, and its joints' share if it is skinned, whichever of the
+ * two set-up calls comes first): neb_gi_morph_vertices never allocates.  Binding again replaces targets and rest pose; numTargets == 0
+ * removes them and gives the memory back.  neb_gi_set_scene and neb_destroy free everything; neb_gi_build_bvh keeps the targets.
+ * Refusals, each leaving everything unchanged (the previous targets stay in force): NEB_ERR_STATE without a scene; NEB_ERR_INVALID_ARG
+ * for descs == NULL with n > 0, a geometry >= n_geoms or named twice, numTargets above 65535, NULL positionDeltas or a NULL entry of a
+ * given array, a stride below 12, normal or tangent deltas for a geometry set without its attribute streams; NEB_ERR_OUT_OF_RANGE for a
+ * delta that is not finite.  n == 0: NEB_OK. */
+typedef struct neb_morph_desc {
+    uint32_t geometry;                   /* index into neb_gi_set_scene's geometries */
+    uint32_t numTargets;                 /* 1 .. 65535; 0 = remove this geometry's targets and rest pose */
+    const void* const* positionDeltas;   /* HOST: numTargets pointers, each float3 per vertex (glTF target POSITION); required */
+    uint32_t positionStride;             /* bytes, >= 12 */
+    const void* const* normalDeltas;     /* HOST: numTargets pointers, float3 per vertex; NULL = the targets carry none */
+    uint32_t normalStride;
+    const void* const* tangentDeltas;    /* HOST: numTargets pointers, float3 per vertex (glTF: vec3, .w is not morphed); NULL = none */
+    uint32_t tangentStride;
+} neb_morph_desc;
+int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t n, neb_stream stream);
+/* The per-frame call: one weight per target and named geometry and, for a skinned geometry, optionally its palette.  Enqueue only; it
+ * never allocates once the pinned ring is sized.  The host compacts each geometry's weights to its ACTIVE LIST -- the pairs {target,
+ * weight} with weight != 0 (+0 and -0 both drop out), in target order -- so the cost follows the active targets, not numTargets.  Ranges,
+ * active lists and palettes travel through the pinned ring of the other update calls and reach device memory in ONE hipMemcpyAsync.
+ * The chain on `stream`, in the ordering bracket of neb_gi_skin_vertices: morph_check_kernel (one lane per vertex: the final position,
+ * skinned where a palette is given, and its world point under the geometry's current matrix must be finite, |x| <= 3.0e38, or the WHOLE
+ * call is refused on the device: nothing is written, NEB_OK has long been returned, neb_gi_update_status counts it),
+ * morph_scatter_kernel, then the kernels of a vertex update unchanged: re-bake, record rewrite (always), boxes, refit levels,
+ * requantise, result record.
+ * Arithmetic, one written-down order, every product and every sum rounded by itself (no fused multiply-add):
+ *     m = rest position;  for each active {k, w} in target order:  m[c] = m[c] + w * dP_k[c]
+ *     n, t.xyz likewise with dN_k, dT_k where the targets carry them (otherwise the rest value, its bits kept);  t.w copied
+ * A target of weight zero contributes nothing, not even the sum: a -0.0 of the rest pose stays -0.0.  Nothing is renormalised (the
+ * shading normalises each vertex normal at the hit).  jointMatrices == NULL: the pools get m, n, t.  With a palette, m, n, t take the
+ * place of the bind pose in neb_gi_skin_vertices' order (glTF: morph, then skin): joints and weights come from the geometry's skin, the
+ * skin's own bind pose is neither read nor changed, and nothing passes through an intermediate vertex buffer.  The blend always starts
+ * from the REST pose, never from the live pools: a chain of calls does not drift, and all-zero weights restore the rest pose bit for bit.
+ * neb_gi_skin_vertices on a geometry that also has targets behaves as without them (it reads its bind pose).
+ * Host state, sun table, strips, svgf_vertex_motion: exactly a device-sourced update of the whole geometry, as neb_gi_skin_vertices.
+ * Refusals at the call, each leaving everything unchanged: NEB_ERR_STATE before a successful neb_gi_build_bvh, for a geometry without
+ * targets, for jointMatrices != NULL on a geometry without a skin; NEB_ERR_INVALID_ARG for a null pointer with n > 0, a geometry >=
+ * n_geoms or named twice; NEB_ERR_OUT_OF_RANGE for a weight, or a matrix entry in columns 0-2, that is not finite.  n == 0: NEB_OK. */
+typedef struct neb_morph_update {
+    uint32_t geometry;
+    const float* weights;        /* HOST, numTargets floats */
+    const float* jointMatrices;  /* HOST, numJoints x 16 as in neb_skin_update, or NULL = do not skin */
+} neb_morph_update;
+int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_t n, neb_stream stream);
 /* Copies the current contents of a geometry's spans of the device pools to host arrays: what a host whose own copy has gone stale (a
  * device-sourced update, a skin call) reads back.  Ordered behind rewrites enqueued on other streams, and it waits for the copies.  Any
  * geometry, skinned or not; a geometry set without its attribute streams reads zeros for normals and tangents.

@@ -175,6 +175,16 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_skin_vertices(m_svgf.Context(), updates, n, commandList), "neb_gi_skin_vertices");
         }
+        // Morph targets: bind per-target delta streams to every vertex of a geometry (the rest pose is the pools as they are, in stream order) ...
+        void SetMorphTargets(const neb_morph_desc* descs, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_set_morph_targets(m_svgf.Context(), descs, n, commandList), "neb_gi_set_morph_targets");
+        }
+        // ... then one weight per target and frame, and the palette of a skinned geometry: blended (and skinned) on the device from the rest pose
+        void MorphVertices(const neb_morph_update* updates, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_morph_vertices(m_svgf.Context(), updates, n, commandList), "neb_gi_morph_vertices");
+        }
         // the pools' current contents of a geometry's vertices (normals / tangents may be null); waits for the copies
         void DownloadVertices(uint32_t geometry, uint32_t firstVertex, uint32_t numVertices, float* positions, float* normals, float* tangents,
                               neb_stream commandList)

@@ -110,6 +110,18 @@ class SkinUpdate(C.Structure):
     _fields_ = [("geometry", C.c_uint32), ("jointMatrices", C.POINTER(C.c_float))]
 
 
+class MorphDesc(C.Structure):
+    """neb_morph_desc"""
+    _fields_ = [("geometry", C.c_uint32), ("numTargets", C.c_uint32), ("positionDeltas", C.POINTER(C.c_void_p)), ("positionStride", C.c_uint32),
+                ("normalDeltas", C.POINTER(C.c_void_p)), ("normalStride", C.c_uint32), ("tangentDeltas", C.POINTER(C.c_void_p)),
+                ("tangentStride", C.c_uint32)]
+
+
+class MorphUpdate(C.Structure):
+    """neb_morph_update"""
+    _fields_ = [("geometry", C.c_uint32), ("weights", C.POINTER(C.c_float)), ("jointMatrices", C.POINTER(C.c_float))]
+
+
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -125,6 +137,8 @@ def _gi_sigs():
         "neb_gi_update_vertices_device": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_set_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinDesc), C.c_uint32, C.c_void_p]),
         "neb_gi_skin_vertices": (C.c_int, [C.c_void_p, C.POINTER(SkinUpdate), C.c_uint32, C.c_void_p]),
+        "neb_gi_set_morph_targets": (C.c_int, [C.c_void_p, C.POINTER(MorphDesc), C.c_uint32, C.c_void_p]),
+        "neb_gi_morph_vertices": (C.c_int, [C.c_void_p, C.POINTER(MorphUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_download_vertices": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                                C.POINTER(C.c_float), C.c_void_p]),
         "neb_gi_update_status": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

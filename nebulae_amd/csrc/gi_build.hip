@@ -79,6 +79,9 @@ void gi_destroy(GiState* g)
     for (GiState::Skin& sk : g->skins)
         if (sk.d_block)
             (void)hipFree(sk.d_block);
+    for (GiState::Morph& mo : g->morphs)
+        if (mo.d_block)
+            (void)hipFree(mo.d_block);
     if (g->d_skin_args)
         (void)hipFree(g->d_skin_args);
     delete g;

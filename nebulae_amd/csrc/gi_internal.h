@@ -337,8 +337,36 @@ struct GiState {
     // The per-context palette buffer: what a skin call copies to the device in ONE hipMemcpyAsync from its pinned slot --
     // {DeformRange x n | SkinSource x n | 16 floats x the joints of the n geometries}.  Sized by neb_gi_set_skin for a call that names
     // every bound geometry (64 bytes of ranges + 64 bytes per joint: the geometry's share), so a skin call never allocates.
+    // The morph calls copy their arguments into the same buffer: its capacity is args_capacity() below, whichever set-up call sizes it.
     void* d_skin_args = nullptr;
     size_t skin_args_cap = 0;
+    // ---- morph targets: neb_gi_set_morph_targets / neb_gi_morph_vertices (gi_refit.hip) ----
+    // What neb_gi_set_morph_targets keeps of a geometry, one device allocation, every stream tight, the 16-byte stream first:
+    // {rest tangents float4 | rest positions float3 | rest normals float3} x n_verts, then target-major float3 streams:
+    // position deltas [n_targets][n_verts], normal deltas likewise (has_n), tangent deltas likewise (has_t).
+    struct Morph {
+        void* d_block = nullptr;
+        uint32_t n_targets = 0; // 0: the geometry has no targets
+        bool has_n = false, has_t = false;
+    };
+    std::vector<Morph> morphs;        // per geometry; empty until the first neb_gi_set_morph_targets
+    uint32_t n_morphs = 0, morph_targets = 0; // bound geometries, the sum of their numTargets
+    // One range of a morph call beside its DeformRange: the geometry's block, its active list among the call's pairs, and -- where the
+    // call skins it -- the block of its skin and where its palette starts among the call's matrices (n_joints == 0: not skinned).
+    struct MorphSource {
+        const uint8_t *block, *skin_block;
+        uint32_t n_verts, n_targets, act_first, n_active, pal_first, n_joints, flags, pad;
+    };
+    static constexpr uint32_t kMorphAttrs = 1u, kMorphNormals = 2u, kMorphTangents = 4u; // MorphSource::flags
+    struct MorphPair { uint32_t target; float weight; }; // one entry of an active list
+    // A morph call copies {DeformRange x n | MorphSource x n | MorphPair x active, padded to 16 B | 16 floats x the joints of the skinned
+    // ones} into d_skin_args in ONE hipMemcpyAsync.  The buffer serves both kinds of call, and both set-up calls size it by this one
+    // formula from the four sums, so the order they come in does not matter: a skin call needs 64 bytes per bound skin and 64 per joint,
+    // a morph call 80 bytes per geometry, 8 per target, at most 8 of padding, and the joints' share where it skins.
+    static size_t args_capacity(uint32_t n_skins, uint32_t skin_joints, uint32_t n_morphs, uint32_t morph_targets)
+    {
+        return (size_t)64 * n_skins + (size_t)64 * skin_joints + (size_t)96 * n_morphs + (size_t)8 * morph_targets;
+    }
     // Streams that have read triangles / nodes / geometry tables since the last update: an update on another stream orders itself
     // behind them (an event recorded on each, waited for on its own stream).  More than kReaderStreams: it waits for the device.
     static constexpr int kReaderStreams = 4;

@@ -18,6 +18,11 @@
 // neb_gi_set_skin / neb_gi_skin_vertices are the producer such a host otherwise brings itself: joints, weights and the
 // bind pose of a geometry stay on the device, a call hands over one palette of joint matrices per geometry, skin_check_kernel and
 // skin_scatter_kernel stand where the check and the scatter of the device-sourced update stand, and the rest of its chain follows.
+//
+// neb_gi_set_morph_targets / neb_gi_morph_vertices are the same producer for glTF morph targets: per-target delta streams
+// and the rest pose of a geometry stay on the device, a call hands over one weight per target -- compacted on the host to the targets
+// that act -- and, for a skinned geometry, optionally its palette: morph_check_kernel and morph_scatter_kernel blend the rest pose and,
+// with a palette, put the blend through the skin's own arithmetic in the place of its bind pose (glTF's order: morph, then skin).
 #include <algorithm>
 
 #include "gi_device.h"
@@ -362,6 +367,165 @@ __global__ void skin_scatter_kernel(const GiState::DeformRange* __restrict__ ran
         const float3 t = skin_direction(S, bt.x, bt.y, bt.z);
         normals[3 * v] = n.x, normals[3 * v + 1] = n.y, normals[3 * v + 2] = n.z;
         tangents[4 * v] = t.x, tangents[4 * v + 1] = t.y, tangents[4 * v + 2] = t.z, tangents[4 * v + 3] = bt.w;
+    }
+    if (j == 0) {
+        geom_epoch[r.geom] = epoch;
+        if (deform_dirty)
+            deform_dirty[r.geom] = 1u;
+    }
+}
+
+// ---- morph targets ----
+// The lane's range by the scatter's bisection, its source and its vertex inside the geometry; false: the lane has nothing to do.
+__device__ __forceinline__ bool morph_lane(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::MorphSource* __restrict__ sources,
+                                           uint32_t k, uint32_t n_geoms, GiState::DeformRange& r, GiState::MorphSource& s, uint32_t& j)
+{
+    uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[mid].first_lane <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    r = ranges[lo];
+    s = sources[lo];
+    j = k - r.first_lane;
+    return j < r.count && j < s.n_verts && r.geom < n_geoms && s.n_targets != 0u;
+}
+// THE written order of one float3 stream: v[c] = v[c] + w * d_k[c] for each pair {k, w} of the lane's active list, in the list's order,
+// every product and every sum rounded by itself.  The order of the sums is fixed, the loads are not: four targets' deltas are fetched
+// before the first of their dependent adds, so that four round trips are in flight, not one.  `deltas` is the target-major stream
+// [n_targets][n_verts] float3; a target index is clamped to the stream (the host writes none beyond it: the clamp only keeps the read inside).
+__device__ __forceinline__ void morph_accumulate(const float* __restrict__ deltas, const GiState::MorphSource& s, uint32_t j, const uint2* __restrict__ act,
+                                                 float& x, float& y, float& z)
+{
+    const uint32_t last = s.n_targets - 1u;
+    uint32_t a = 0;
+    for (; a + 4u <= s.n_active; a += 4u) {
+        float w[4], d[4][3];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const uint2 p = act[a + q];
+            const float* sp = deltas + 3 * ((size_t)min(p.x, last) * s.n_verts + j);
+            w[q] = __uint_as_float(p.y);
+            d[q][0] = sp[0], d[q][1] = sp[1], d[q][2] = sp[2];
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            x = __fadd_rn(x, rounded_product(w[q], d[q][0]));
+            y = __fadd_rn(y, rounded_product(w[q], d[q][1]));
+            z = __fadd_rn(z, rounded_product(w[q], d[q][2]));
+        }
+    }
+    for (; a < s.n_active; ++a) {
+        const uint2 p = act[a];
+        const float* sp = deltas + 3 * ((size_t)min(p.x, last) * s.n_verts + j);
+        const float w = __uint_as_float(p.y), d0 = sp[0], d1 = sp[1], d2 = sp[2];
+        x = __fadd_rn(x, rounded_product(w, d0));
+        y = __fadd_rn(y, rounded_product(w, d1));
+        z = __fadd_rn(z, rounded_product(w, d2));
+    }
+}
+// the streams of a geometry's block (GiState::Morph)
+__device__ __forceinline__ const float* morph_rest_pos(const GiState::MorphSource& s) { return reinterpret_cast<const float*>(s.block + 16 * (size_t)s.n_verts); }
+__device__ __forceinline__ const float* morph_rest_nrm(const GiState::MorphSource& s) { return reinterpret_cast<const float*>(s.block + 28 * (size_t)s.n_verts); }
+__device__ __forceinline__ const float* morph_deltas(const GiState::MorphSource& s, uint32_t stream)
+{
+    return reinterpret_cast<const float*>(s.block + 40 * (size_t)s.n_verts) + 3 * (size_t)stream * s.n_targets * s.n_verts;
+}
+__device__ __forceinline__ float3 morph_position(const GiState::MorphSource& s, const uint2* __restrict__ act, uint32_t j)
+{
+    const float* rp = morph_rest_pos(s) + 3 * (size_t)j;
+    float3 m = make_float3(rp[0], rp[1], rp[2]);
+    morph_accumulate(morph_deltas(s, 0), s, j, act + s.act_first, m.x, m.y, m.z);
+    return m;
+}
+__device__ __forceinline__ GiState::SkinSource morph_skin(const GiState::MorphSource& s)
+{
+    return {s.skin_block, s.n_verts, s.pal_first, s.n_joints, 0u, {0u, 0u}};
+}
+
+// One lane per vertex of the geometries a morph call names: the final position -- the blend, skinned where the call hands a palette --
+// and its world point under the geometry's current matrix must be finite within gi_bake_point's bound; a failing lane sets the call's
+// refusal word (deform_check_kernel's contract).
+__global__ void morph_check_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::MorphSource* __restrict__ sources,
+                                   const uint2* __restrict__ act, const float* __restrict__ palette, uint32_t n_lanes, uint32_t n_geoms,
+                                   const float* __restrict__ xf, uint32_t* __restrict__ refused)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    GiState::DeformRange r;
+    GiState::MorphSource s;
+    uint32_t j;
+    if (!morph_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j))
+        return;
+    const float3 m = morph_position(s, act, j);
+    float a[3] = {m.x, m.y, m.z};
+    if (s.n_joints) {
+        float S[16];
+        skin_blend(morph_skin(s), palette, j, S);
+        const float3 a3 = bake_point(S, a);
+        a[0] = a3.x, a[1] = a3.y, a[2] = a3.z;
+    }
+    const float3 w = bake_point(xf + 16 * (size_t)r.geom, a);
+    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
+                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
+    if (!ok)
+        atomicOr(refused, 1u);
+}
+
+// One lane per vertex: m, n, t = the REST pose (never the live pools: a chain of calls does not drift) plus the active targets in the
+// written order; into the pools as they are, or -- with a palette -- in the place of the bind pose in skin_scatter_kernel's order, through
+// no buffer in between.  The whole launch leaves at once when morph_check_kernel has set the refusal word.  Lane 0 of a range stamps its
+// geometry and, with option svgf_vertex_motion, sets its dirty word.  A geometry set without its attribute streams gets positions only;
+// targets that carry no normal (tangent) deltas leave the rest normal (tangent), its bits kept.
+__global__ void morph_scatter_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::MorphSource* __restrict__ sources,
+                                     const uint2* __restrict__ act, const float* __restrict__ palette, uint32_t n_lanes, uint32_t n_pool, uint32_t n_geoms,
+                                     uint32_t epoch, float* __restrict__ pos, float* __restrict__ normals, float* __restrict__ tangents,
+                                     uint32_t* __restrict__ geom_epoch, const uint32_t* __restrict__ refused, uint32_t* __restrict__ deform_dirty)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n_lanes)
+        return;
+    if (*refused)
+        return;
+    GiState::DeformRange r;
+    GiState::MorphSource s;
+    uint32_t j;
+    if (!morph_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || r.dst + j >= n_pool)
+        return;
+    const size_t v = (size_t)r.dst + j;
+    float3 m = morph_position(s, act, j);
+    const bool attrs = (s.flags & GiState::kMorphAttrs) != 0u;
+    float3 n = make_float3(0.f, 0.f, 0.f);
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (attrs) {
+        const float* rn = morph_rest_nrm(s) + 3 * (size_t)j;
+        n = make_float3(rn[0], rn[1], rn[2]);
+        t = reinterpret_cast<const float4*>(s.block)[j];
+        uint32_t stream = 1;
+        if (s.flags & GiState::kMorphNormals)
+            morph_accumulate(morph_deltas(s, stream++), s, j, act + s.act_first, n.x, n.y, n.z);
+        if (s.flags & GiState::kMorphTangents)
+            morph_accumulate(morph_deltas(s, stream), s, j, act + s.act_first, t.x, t.y, t.z);
+    }
+    if (s.n_joints) {
+        float S[16];
+        skin_blend(morph_skin(s), palette, j, S);
+        const float p[3] = {m.x, m.y, m.z};
+        m = bake_point(S, p);
+        if (attrs) {
+            n = skin_direction(S, n.x, n.y, n.z);
+            const float3 td = skin_direction(S, t.x, t.y, t.z);
+            t.x = td.x, t.y = td.y, t.z = td.z;
+        }
+    }
+    pos[3 * v] = m.x, pos[3 * v + 1] = m.y, pos[3 * v + 2] = m.z;
+    if (attrs) {
+        normals[3 * v] = n.x, normals[3 * v + 1] = n.y, normals[3 * v + 2] = n.z;
+        tangents[4 * v] = t.x, tangents[4 * v + 1] = t.y, tangents[4 * v + 2] = t.z, tangents[4 * v + 3] = t.w;
     }
     if (j == 0) {
         geom_epoch[r.geom] = epoch;
@@ -1351,7 +1515,7 @@ int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_st
     // ---- what the call needs is allocated before anything is let go of ----
     std::vector<void*> fresh(n, nullptr);
     void* fresh_args = nullptr;
-    const size_t args_cap = (size_t)64 * n_skins + (size_t)64 * n_joints;
+    const size_t args_cap = GiState::args_capacity(n_skins, n_joints, g->n_morphs, g->morph_targets); // (the buffer is shared with the morph calls)
     hipError_t e = hipSuccess;
     for (uint32_t k = 0; k < n && e == hipSuccess; ++k)
         if (skins[k].joints)
@@ -1527,6 +1691,275 @@ int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t 
                        d_res + 1);
     hipLaunchKernelGGL(skin_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
                        (const GiState::SkinSource*)(d_args + head), (const float*)(d_args + head + src_bytes), lane, n_pool, g->n_geoms, call, g->d_pos,
+                       const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)(d_res + 1),
+                       g->d_deform_dirty);
+    GI_HIP(ctx, hipGetLastError());
+    if (any_tris && n_slots) {
+        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, true, n_boxed, stream));
+    }
+    GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
+    GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+// ---- morph targets ----
+int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_set_morph_targets: no scene (call neb_gi_set_scene first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!descs)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: null pointer");
+    if (n > g->n_geoms)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: more entries than geometries (an index is out of range or named twice)");
+    // ---- everything that can refuse the call comes before anything changes ----
+    const uint32_t stamp = ++g->seen_stamp;
+    uint32_t n_morphs = g->n_morphs, n_targets = g->morph_targets;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_morph_desc& d = descs[k];
+        if (d.geometry >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: geometry index out of range");
+        if (g->h_seen[d.geometry] == stamp)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: a geometry is named twice");
+        g->h_seen[d.geometry] = stamp;
+        if (!g->morphs.empty() && g->morphs[d.geometry].n_targets)
+            n_morphs -= 1u, n_targets -= g->morphs[d.geometry].n_targets;
+        if (d.numTargets == 0)
+            continue; // (remove)
+        if (d.numTargets > 65535u)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: numTargets must be 0 .. 65535");
+        if (!d.positionDeltas)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: null positionDeltas");
+        if ((d.normalDeltas || d.tangentDeltas) && !g->h_geoms[d.geometry].valid)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: normal or tangent deltas for a geometry that was set without its attribute streams");
+        if (d.positionStride < 12u || (d.normalDeltas && d.normalStride < 12u) || (d.tangentDeltas && d.tangentStride < 12u))
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: a stride is smaller than its element");
+        for (uint32_t t = 0; t < d.numTargets; ++t)
+            if (!d.positionDeltas[t] || (d.normalDeltas && !d.normalDeltas[t]) || (d.tangentDeltas && !d.tangentDeltas[t]))
+                return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: a null target pointer");
+        n_morphs += 1u, n_targets += d.numTargets;
+    }
+    // the deltas repacked tight and target-major, {positions | normals | tangents}, and looked at on the way
+    std::vector<std::vector<float>> packed(n);
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_morph_desc& d = descs[k];
+        if (d.numTargets == 0)
+            continue;
+        const size_t nv = g->h_geoms[d.geometry].n_verts;
+        const void* const* streams[3] = {d.positionDeltas, d.normalDeltas, d.tangentDeltas};
+        const uint32_t strides[3] = {d.positionStride, d.normalStride, d.tangentStride};
+        std::vector<float>& out = packed[k];
+        out.resize(3 * nv * d.numTargets * (1u + (d.normalDeltas ? 1u : 0u) + (d.tangentDeltas ? 1u : 0u)));
+        float* dst = out.data();
+        for (int q = 0; q < 3; ++q) {
+            if (!streams[q])
+                continue;
+            for (uint32_t t = 0; t < d.numTargets; ++t)
+                for (size_t v = 0; v < nv; ++v, dst += 3) {
+                    memcpy(dst, (const uint8_t*)streams[q][t] + v * strides[q], 12);
+                    if (!(std::isfinite(dst[0]) && std::isfinite(dst[1]) && std::isfinite(dst[2])))
+                        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_set_morph_targets: a delta is not a finite number");
+                }
+        }
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    // ---- what the call needs is allocated before anything is let go of ----
+    std::vector<void*> fresh(n, nullptr);
+    void* fresh_args = nullptr;
+    const size_t args_cap = GiState::args_capacity(g->n_skins, g->skin_joints, n_morphs, n_targets);
+    hipError_t e = hipSuccess;
+    for (uint32_t k = 0; k < n && e == hipSuccess; ++k)
+        if (descs[k].numTargets)
+            e = hipMalloc(&fresh[k], std::max<size_t>(64, (size_t)40 * g->h_geoms[descs[k].geometry].n_verts + packed[k].size() * sizeof(float)));
+    if (e == hipSuccess && args_cap && args_cap != g->skin_args_cap)
+        e = hipMalloc(&fresh_args, args_cap);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize(); // (a set-up call: a call still in flight reads the blocks and the argument buffer about to be replaced)
+    // Everything that can still fail fills the FRESH blocks: the deltas, and the rest pose -- read behind a rewrite enqueued on another
+    // stream (gi_scene_reader; a later rewrite waits for the copies).  Nothing of the context has changed yet.
+    if (e == hipSuccess)
+        e = gi_scene_reader(g, stream);
+    for (uint32_t k = 0; k < n && e == hipSuccess; ++k) {
+        const GiState::HostGeom& hg = g->h_geoms[descs[k].geometry];
+        const size_t nv = hg.n_verts;
+        if (!descs[k].numTargets || !nv)
+            continue;
+        uint8_t* b = (uint8_t*)fresh[k];
+        e = hipMemcpy(b + 40 * nv, packed[k].data(), packed[k].size() * sizeof(float), hipMemcpyHostToDevice);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b, g->view.tangents + 4 * (size_t)hg.vertexBase, 16 * nv, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b + 16 * nv, g->d_pos + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(b + 28 * nv, g->view.normals + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
+    }
+    if (e != hipSuccess) {
+        for (void* p : fresh)
+            if (p)
+                (void)hipFree(p); // (waits for the device: a copy into the block that was enqueued is done)
+        if (fresh_args)
+            (void)hipFree(fresh_args);
+        return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_morph_targets: device memory", e);
+    }
+    // ---- commit: nothing below can fail ----
+    if (g->morphs.empty())
+        g->morphs.resize(g->n_geoms);
+    if (args_cap != g->skin_args_cap) {
+        if (g->d_skin_args)
+            (void)hipFree(g->d_skin_args);
+        g->d_skin_args = fresh_args;
+        g->skin_args_cap = args_cap;
+    }
+    g->n_morphs = n_morphs, g->morph_targets = n_targets;
+    for (uint32_t k = 0; k < n; ++k) {
+        GiState::Morph& mo = g->morphs[descs[k].geometry];
+        if (mo.d_block)
+            (void)hipFree(mo.d_block);
+        mo = GiState::Morph();
+        if (descs[k].numTargets) {
+            mo.d_block = fresh[k];
+            mo.n_targets = descs[k].numTargets;
+            mo.has_n = descs[k].normalDeltas != nullptr, mo.has_t = descs[k].tangentDeltas != nullptr;
+        }
+    }
+    return NEB_OK;
+}
+
+int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_morph_vertices: no built scene (neb_gi_set_scene + neb_gi_build_bvh first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!updates)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: null pointer");
+    if (n > g->n_geoms)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: more entries than geometries (an index is out of range or named twice)");
+    GI_HIP(ctx, gi_harvest_results(g, false));
+    // ---- everything the HOST can refuse the call for comes before anything changes (the blended vertices themselves: morph_check_kernel) ----
+    const uint32_t stamp = ++g->seen_stamp;
+    struct Span { uint32_t geom, k; };
+    std::vector<Span> spans;
+    spans.reserve(n);
+    size_t n_lanes = 0, n_mats = 0, n_active = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_morph_update& u = updates[k];
+        if (u.geometry >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: geometry index out of range");
+        if (g->h_seen[u.geometry] == stamp)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: a geometry is named twice");
+        g->h_seen[u.geometry] = stamp;
+        if (!u.weights)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: null weights");
+        if (g->morphs.empty() || !g->morphs[u.geometry].n_targets)
+            return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_morph_vertices: the geometry has no targets (neb_gi_set_morph_targets first)");
+        if (u.jointMatrices && (g->skins.empty() || !g->skins[u.geometry].n_joints))
+            return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_morph_vertices: jointMatrices for a geometry without a skin (neb_gi_set_skin first)");
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_morph_update& u = updates[k];
+        const uint32_t nt = g->morphs[u.geometry].n_targets, nj = u.jointMatrices ? g->skins[u.geometry].n_joints : 0u;
+        uint32_t active = 0;
+        for (uint32_t t = 0; t < nt; ++t) {
+            if (!std::isfinite(u.weights[t]))
+                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_morph_vertices: a weight is not a finite number");
+            active += u.weights[t] != 0.f ? 1u : 0u; // (+0 and -0 both drop out)
+        }
+        for (uint32_t q = 0; q < 16u * nj; ++q)
+            if ((q & 3u) != 3u && !std::isfinite(u.jointMatrices[q]))
+                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_morph_vertices: a joint matrix entry (columns 0-2) is not a finite number");
+        if (g->h_geoms[u.geometry].n_verts == 0)
+            continue; // (no lane: a range is never empty)
+        spans.push_back({u.geometry, k});
+        n_lanes += g->h_geoms[u.geometry].n_verts;
+        n_mats += nj;
+        n_active += active;
+    }
+    if (n_lanes > 0xffffffffull / 10u) // (the bound of neb_gi_update_vertices: lanes are 32-bit)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: too many vertices in one call");
+    if (spans.empty())
+        return NEB_OK;
+    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom < b.geom; });
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    GI_HIP(ctx, results_prepare(g));
+    // ---- the staging slot: pinned host memory, {ranges | sources | active lists | palettes}, copied to the argument buffer in one piece ----
+    static_assert(sizeof(GiState::DeformRange) == 32 && sizeof(GiState::MorphSource) == 48 && sizeof(GiState::MorphPair) == 8,
+                  "80 bytes of ranges per bound geometry, 8 per target (GiState::args_capacity)");
+    const size_t head = spans.size() * sizeof(GiState::DeformRange), src_bytes = spans.size() * sizeof(GiState::MorphSource);
+    const size_t act_bytes = (n_active * sizeof(GiState::MorphPair) + 15u) & ~(size_t)15u; // (the palette is read in 16-byte pieces)
+    const size_t bytes = head + src_bytes + act_bytes + 64u * n_mats;
+    if (bytes > g->skin_args_cap)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_morph_vertices: the argument buffer is smaller than the call (internal)");
+    GI_HIP(ctx, vstage_reserve(g, bytes, std::max(bytes, g->skin_args_cap))); // (at once for a call that names every geometry)
+    const uint32_t call = g->epoch + 1u;
+    int slot = 0;
+    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
+    GI_HIP(ctx, results_acquire(g, slot));
+    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+        return rc;
+    // ---- commit the host side: the slot; h_pos is left behind (host_stale), the boxes follow with the result record ----
+    g->epoch = call;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    GiState::DeformRange* ranges = (GiState::DeformRange*)base;
+    GiState::MorphSource* sources = (GiState::MorphSource*)(base + head);
+    GiState::MorphPair* pairs = (GiState::MorphPair*)(base + head + src_bytes);
+    float* palette = (float*)(base + head + src_bytes + act_bytes);
+    uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
+    GiState::ResultRecord& rec = g->result_rec[slot];
+    rec.geoms.clear();
+    uint32_t lane = 0, mat = 0, act = 0;
+    bool any_tris = false;
+    for (size_t i = 0; i < spans.size(); ++i) {
+        const uint32_t gi = spans[i].geom;
+        const neb_morph_update& u = updates[spans[i].k];
+        GiState::HostGeom& hg = g->h_geoms[gi];
+        const GiState::Morph& mo = g->morphs[gi];
+        const uint32_t nj = u.jointMatrices ? g->skins[gi].n_joints : 0u, act_first = act;
+        for (uint32_t t = 0; t < mo.n_targets; ++t)
+            if (u.weights[t] != 0.f)
+                pairs[act++] = {t, u.weights[t]};
+        ranges[i] = {lane, hg.n_verts, hg.vertexBase, gi, 0u, hg.valid ? 0u : GiState::kNoStream, hg.valid ? 0u : GiState::kNoStream, 0u};
+        sources[i] = {(const uint8_t*)mo.d_block, nj ? (const uint8_t*)g->skins[gi].d_block : nullptr, hg.n_verts, mo.n_targets, act_first, act - act_first,
+                      mat, nj, (hg.valid ? GiState::kMorphAttrs : 0u) | (mo.has_n ? GiState::kMorphNormals : 0u) | (mo.has_t ? GiState::kMorphTangents : 0u), 0u};
+        if (nj)
+            memcpy(palette + 16 * (size_t)mat, u.jointMatrices, 64 * (size_t)nj);
+        roll_mark(g, gi, 0, hg.n_verts); // (the host cannot know of a refusal on the device: the roll then copies equal values)
+        lane += hg.n_verts, mat += nj;
+        hg.host_stale = true;
+        if (hg.n_tris) {
+            hg.dirty = true;
+            any_tris = true;
+            list[rec.geoms.size()] = gi;
+            rec.geoms.push_back(gi);
+        }
+    }
+    if (act_bytes > (size_t)act * sizeof(GiState::MorphPair))
+        pairs[act] = {0u, 0.f}; // (the padding travels too)
+    if (any_tris)
+        refit_drop_sun_table(g);
+    // ---- enqueue: arguments, check, blend, bake, records, boxes, levels, quantise, the record back ----
+    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3), n_boxed = (uint32_t)rec.geoms.size();
+    uint32_t* d_res = g->d_result + (size_t)slot * result_stride(g);
+    const uint8_t* d_args = (const uint8_t*)g->d_skin_args;
+    GI_HIP(ctx, results_enqueue_init(g, slot, call, n_boxed, stream));
+    GI_HIP(ctx, hipMemcpyAsync(g->d_skin_args, base, bytes, hipMemcpyHostToDevice, stream));
+    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
+    g->stage_used[slot] = true;
+    hipLaunchKernelGGL(morph_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+                       (const GiState::MorphSource*)(d_args + head), (const uint2*)(d_args + head + src_bytes),
+                       (const float*)(d_args + head + src_bytes + act_bytes), lane, g->n_geoms, (const float*)g->d_xf, d_res + 1);
+    hipLaunchKernelGGL(morph_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+                       (const GiState::MorphSource*)(d_args + head), (const uint2*)(d_args + head + src_bytes),
+                       (const float*)(d_args + head + src_bytes + act_bytes), lane, n_pool, g->n_geoms, call, g->d_pos,
                        const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)(d_res + 1),
                        g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());

@@ -49,6 +49,7 @@ class DeferredRenderer:
         self.sun = SceneSunUI()
         self.gi_ui = GlobalIlluminationUI()
         self._scene = None
+        self._morph_counts = {}  # geometry -> numTargets, as bound through set_morph_targets
         self._eye = None
         self._sun_key = None
         self.dynamic_scene_this_frame = False
@@ -103,6 +104,7 @@ class DeferredRenderer:
     # ---- DeferredRenderer::InitPathtracerScene + InitRTAccelerationStructures (:978-1030,1083-1086) ----
     def init_pathtracer_scene(self, scene, stream=0):
         G, ng, M, nm, T, nt = scene.descs()
+        self._morph_counts = {}
         self._scene = None  # (neb_gi_set_scene lets go of the old scene first: if the new one is refused the context has none)
         self._check(self._lib.neb_gi_set_scene(self._ctx, G, ng, M, nm, T, nt), "neb_gi_set_scene")
         self._check(self._lib.neb_gi_build_bvh(self._ctx, C.c_void_p(stream)), "neb_gi_build_bvh")
@@ -270,6 +272,91 @@ class DeferredRenderer:
                 p, n, t = self.download_vertices(i, stream=st.value or 0)
                 gm["positions"] = p
                 if all(gm.get(key) is not None for key in ("normals", "uvs", "tangents")):  # (else the library skins positions only)
+                    gm["normals"], gm["tangents"] = n, t
+
+    # ---- morph targets (neb_gi_set_morph_targets / neb_gi_morph_vertices: DESIGN.md 3.4e); nothing here blends on the CPU ----
+    def set_morph_targets(self, index, position_deltas, normal_deltas=None, tangent_deltas=None, stream=None):
+        """Bind morph targets to geometry `index`: position_deltas of shape T x n x 3 float32 (glTF target POSITION) for every one of its
+        n vertices, and optionally normal and tangent deltas of the same shape.  The rest pose is what the device pools hold at the call
+        (neb_gi_set_morph_targets)."""
+        if self._scene is None:
+            raise NebError("set_morph_targets: no scene (init_pathtracer_scene first)")
+        index = int(index)
+        if not 0 <= index < len(self._scene.geometries):
+            raise NebError("set_morph_targets: geometry index out of range")
+        nv = len(self._scene.geometries[index]["positions"])
+        streams = []
+        for what, a in (("position", position_deltas), ("normal", normal_deltas), ("tangent", tangent_deltas)):
+            if a is None:
+                streams.append(None)
+                continue
+            a = np.ascontiguousarray(np.asarray(a, np.float32))
+            if a.ndim != 3 or a.shape[1:] != (nv, 3):
+                raise NebError(f"set_morph_targets: {what} deltas of shape {a.shape}, the geometry has {nv} vertices (T x {nv} x 3 expected)")
+            streams.append(a)
+        if streams[0] is None:
+            raise NebError("set_morph_targets: position deltas are required")
+        T = streams[0].shape[0]
+        if not 1 <= T <= 0xFFFF or any(a is not None and a.shape[0] != T for a in streams):
+            raise NebError("set_morph_targets: 1 .. 65535 targets, the same number in every stream")
+        d = _lib.MorphDesc(geometry=index, numTargets=T, positionStride=12, normalStride=12, tangentStride=12)
+        for key, a in zip(("positionDeltas", "normalDeltas", "tangentDeltas"), streams):
+            if a is not None:
+                setattr(d, key, (C.c_void_p * T)(*[a[t].ctypes.data for t in range(T)]))
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        self._check(self._lib.neb_gi_set_morph_targets(self._ctx, C.byref(d), 1, st), "neb_gi_set_morph_targets")
+        self._morph_counts[index] = T
+
+    def remove_morph_targets(self, index, stream=None):
+        """Let go of geometry `index`'s targets and rest pose (the pools keep what they hold)."""
+        if self._scene is None:
+            raise NebError("remove_morph_targets: no scene (init_pathtracer_scene first)")
+        index = int(index)
+        if not 0 <= index < len(self._scene.geometries):
+            raise NebError("remove_morph_targets: geometry index out of range")
+        d = _lib.MorphDesc(geometry=index)
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        self._check(self._lib.neb_gi_set_morph_targets(self._ctx, C.byref(d), 1, st), "neb_gi_set_morph_targets")
+        self._morph_counts.pop(index, None)
+
+    def morph_vertices(self, index, weights, joint_matrices=None, stream=None, mirror=False):
+        """Blend morph targets on the device (neb_gi_morph_vertices): `index` is one geometry or a sequence of them, `weights` its T weights
+        or one array per geometry, `joint_matrices` None, or the palette of a skinned geometry (one entry per geometry, None where it is
+        not to be skinned) -- all in ONE call.  The call only enqueues; a vertex that is not finite refuses the whole call on the device,
+        later: see update_status.  mirror=True follows skin_vertices: after the enqueue, and only if the device accepted, the scene
+        object's arrays are refreshed through download_vertices (the call then waits)."""
+        if self._scene is None:
+            raise NebError("morph_vertices: no scene (init_pathtracer_scene first)")
+        if np.ndim(index) == 0:
+            index, weights, joint_matrices = [index], [weights], [joint_matrices]
+        idx = [int(i) for i in index]
+        if joint_matrices is None:
+            joint_matrices = [None] * len(idx)
+        if len(idx) != len(weights) or len(idx) != len(joint_matrices):
+            raise NebError(f"morph_vertices: {len(idx)} geometries but {len(weights)} weight arrays / {len(joint_matrices)} palettes")
+        if any(not 0 <= i < len(self._scene.geometries) for i in idx):
+            raise NebError("morph_vertices: geometry index out of range")
+        ws = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in weights]
+        for i, w in zip(idx, ws):  # (the library reads numTargets floats: a shorter array is refused here)
+            if i in self._morph_counts and len(w) != self._morph_counts[i]:
+                raise NebError(f"morph_vertices: geometry {i} has {self._morph_counts[i]} targets but {len(w)} weights were given")
+        pals = [None if m is None else np.ascontiguousarray(np.asarray(m, np.float32).reshape(-1, 16)) for m in joint_matrices]
+        fp = C.POINTER(C.c_float)
+        ups = (_lib.MorphUpdate * max(len(idx), 1))()
+        for k, (i, w, p) in enumerate(zip(idx, ws, pals)):
+            ups[k].geometry = i
+            ups[k].weights = w.ctypes.data_as(fp)
+            if p is not None:
+                ups[k].jointMatrices = p.ctypes.data_as(fp)
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        refused = self.update_status()["refused"] if mirror else 0  # (harvests every earlier update: the difference below is this call's)
+        self._check(self._lib.neb_gi_morph_vertices(self._ctx, ups, len(idx), st), "neb_gi_morph_vertices")
+        if mirror and self.update_status()["refused"] == refused:
+            for i in idx:
+                gm = self._scene.geometries[i]
+                p, n, t = self.download_vertices(i, stream=st.value or 0)
+                gm["positions"] = p
+                if all(gm.get(key) is not None for key in ("normals", "uvs", "tangents")):  # (else the library blends positions only)
                     gm["normals"], gm["tangents"] = n, t
 
     def download_vertices(self, index, first_vertex=0, n=None, stream=None):
