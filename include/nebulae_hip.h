@@ -74,6 +74,11 @@ typedef enum neb_plane {
  * writes it; a host with its own raster G-buffer uploads or writes it.  While the option is 0 every plane entry point refuses index 13
  * with NEB_ERR_INVALID_ARG, the answer the index had before the option existed. */
 #define NEB_PLANE_PREV_POINT 13
+/* R32G32B32A32_FLOAT 16 B/px, ONE slot: the DEMODULATED denoised colour of the last denoised frame (.w unspecified) -- the temporal pass's
+ * history while option "svgf_demodulate" is 1, see the block above neb_svgf_set_camera.  Behind the enum like the two planes above:
+ * exists only while the option is 1 (allocated zeroed, freed with the option, re-created zeroed by neb_resize).  While the option is 0
+ * every plane entry point refuses index 14 with NEB_ERR_INVALID_ARG, the answer an unknown plane index gets. */
+#define NEB_PLANE_DEMOD 14
 
 /* Slot selectors for the 2-slot (ping-pong) planes. */
 #define NEB_SLOT_CURRENT (-1) /* GetCurrentResourceIndex(), SVGFDenoiser.h:24 */
@@ -161,6 +166,9 @@ int neb_svgf_get_params(const neb_ctx* ctx, neb_svgf_params* out);
  *                       it is 1): the temporal pass follows submeshes deformed by neb_gi_update_vertices / _device through
  *                       NEB_PLANE_PREV_POINT, see neb_svgf_snapshot_vertices.  1 allocates the plane and, with a scene, the previous
  *                       vertex pools; 0 frees them.  With the option 0 nothing changes;
+ *   "svgf_demodulate":  0 (default) / 1 (opt-in): the albedo is divided out in front of the temporal pass and multiplied back at the last
+ *                       a-trous level, so that the filter leaves textures sharp; see the block above neb_svgf_set_camera.  NEB_ERR_STATE on
+ *                       a row-strip context.  1 allocates the (zeroed) NEB_PLANE_DEMOD, 0 frees it.  With 0 nothing changes;
  *   "svgf_motion":      0 (default) / 1 (opt-in, needs "svgf_reproject" = 1, else NEB_ERR_STATE): the reprojecting temporal pass follows
  *                       submeshes moved by neb_gi_update_transforms, see neb_svgf_snapshot_transforms.  1 allocates the (zeroed) submesh-id
  *                       plane and, with a scene set, two per-slot transform tables and the delta table; 0 frees them.  With 0 every
@@ -214,7 +222,35 @@ int neb_svgf_denoise(neb_ctx* ctx, neb_stream stream);
  * last chain submitted and returns the kernels' durations in microseconds (entry 0 = level 0, fused with the temporal pass when
  * the chain ran fused), *n_out = how many.  With "svgf_profile" = 2 only three events are recorded and two durations returned:
  * the first kernel, and all the others together (an event between two launches costs about 2 us of its own). */
+/* With option "svgf_demodulate" = 1 one more entry follows the durations: the number of temporal calls that ran the seed kernel (below)
+ * since "svgf_profile" was last set -- a count, not a time. */
 int neb_svgf_level_times(neb_ctx* ctx, float* out_us, uint32_t capacity, uint32_t* n_out);
+/* ---- Albedo demodulation (option "svgf_demodulate" = 1; no reference counterpart: the reference filters direct + indirect light with the
+ * textures in it, SURVEY.md section 8a, and the a-trous levels cannot tell texture from noise).  Independent of "svgf_reproject",
+ * "svgf_motion" and "svgf_vertex_motion", and composes with each.  With d_c = max(albedo_c, 1/32) per channel, albedo = the pixel's
+ * R11G11B10_FLOAT word of NEB_PLANE_ALBEDO decoded (csrc/svgf_demod.h holds the floor and the order of operations):
+ *   temporal pass:  the pixel's own radiance[cur].rgb is divided by d (the correctly rounded division) on load; the history -- same pixel
+ *                   or the four reprojected taps -- is read from NEB_PLANE_DEMOD instead of radiance[hist]; moments and variance are
+ *                   those of the demodulated luminance; the accumulated demodulated colour goes to radiance[cur] in place.
+ *   a-trous levels: all but the last are the kernels they are without the option; they filter demodulated colour, so phiColor acts on
+ *                   lighting, not on texture.  The level whose destination is the chain's result (neb_svgf_atrous_level_planes) writes
+ *                   the filtered colour as it is into NEB_PLANE_DEMOD and the colour times the output pixel's d (one product) into its
+ *                   destination: radiance[cur] ends up modulated, as a caller expects it.  Alpha is carried as without the option.
+ * Which calls behave differently: as with "svgf_reproject", neb_svgf_temporal enqueues the pass at once even with "svgf_fuse" = 1 and
+ * neb_svgf_atrous / neb_svgf_denoise run the separate kernels (bit for bit the same result with "svgf_fuse" 0 and 1).  NEB_ERR_INVALID_ARG
+ * for a value other than 0 / 1, NEB_ERR_STATE on a row-strip context and on a context created with atrous_levels = 0 (there is no last
+ * level to multiply the albedo back).  With the option 0 nothing changes, and a context switched on and off again computes what one that
+ * never had it on computes.
+ * VALIDITY of NEB_PLANE_DEMOD.  radiance[hist] holds the modulated image, and a reprojected tap comes from another pixel with another
+ * albedo, so the history is KEPT demodulated, not re-derived.  The plane is taken as the history only if (1) the last level of the denoise
+ * of the frame that is now hist wrote it -- in the previous neb_begin_frame bracket, all rows -- (2) with the option on, and (3) nothing has
+ * written that radiance slot through the ABI since: neb_upload_rows, neb_svgf_reset_history, neb_resize.  Otherwise the temporal call first
+ * runs a seed kernel over the resident plane, demod.rgb = radiance[hist].rgb / d(albedo) with the CURRENT albedo plane: the best stand-in
+ * there is, exact for a static camera.  That covers the first frame, the option switched on mid-sequence, a frame the host did not denoise
+ * and neb_svgf_reset_history.
+ * TWO CAVEATS.  A write into radiance[hist] through a raw neb_get_plane pointer cannot be seen: such a host calls neb_svgf_reset_history,
+ * or uploads a matching NEB_PLANE_DEMOD itself.  And the albedo plane must not change between a frame's temporal call and its last level:
+ * the two read the same word of it to divide and to multiply back. ---- */
 /* ---- Temporal reprojection (option "svgf_reproject" = 1; no reference counterpart: the reference's temporal pass reads the history at
  * the same pixel, SURVEY.md quirk 3, so a moving camera either skips SVGF or ghosts).  In this mode every temporal pass -- neb_svgf_temporal,
  * neb_svgf_denoise, neb_svgf_temporal_rows (whole frame only) -- runs the reprojecting kernel.  Per pixel p of the dispatch region

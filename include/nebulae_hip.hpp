@@ -110,6 +110,16 @@ namespace Neb
             ThrowIfFailed(m_ctx, neb_get_plane(m_ctx, NEB_PLANE_PREV_POINT, 0, &p, pitchBytes, rows), "neb_get_plane");
             return p;
         }
+        // Option "svgf_demodulate": the albedo is divided out in front of the temporal pass and multiplied back at the last a-trous level (see
+        // the block above neb_svgf_set_camera), and the one-slot plane that holds the demodulated history while it is on (NEB_PLANE_DEMOD,
+        // behind the neb_plane enum as well)
+        void SetAlbedoDemodulation(bool on) { ThrowIfFailed(m_ctx, neb_set_option(m_ctx, "svgf_demodulate", on ? 1 : 0), "neb_set_option"); }
+        void* GetDemodPlane(size_t* pitchBytes = nullptr, uint32_t* rows = nullptr)
+        {
+            void* p = nullptr;
+            ThrowIfFailed(m_ctx, neb_get_plane(m_ctx, NEB_PLANE_DEMOD, 0, &p, pitchBytes, rows), "neb_get_plane");
+            return p;
+        }
         // Durations (us) of the kernels of the last SubmitATrousComputeWavelet chain, after SetOption("svgf_profile", 1); returns how many
         uint32_t LevelTimes(float* outMicroseconds, uint32_t capacity)
         {

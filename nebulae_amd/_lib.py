@@ -14,6 +14,7 @@ PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY = 6, 
 PLANE_HISTORY_LENGTH = 11  # only while option svgf_reproject is 1
 PLANE_SUBMESH_ID = 12  # only while option svgf_motion is 1 (NEB_PLANE_SUBMESH_ID: behind the enum, not counted by NEB_PLANE_COUNT)
 PLANE_PREV_POINT = 13  # only while option svgf_vertex_motion is 1 (NEB_PLANE_PREV_POINT: behind the enum as well, one slot)
+PLANE_DEMOD = 14  # only while option svgf_demodulate is 1 (NEB_PLANE_DEMOD: behind the enum as well, one slot)
 SLOT_CURRENT, SLOT_HISTORY = -1, -2
 
 

@@ -25,6 +25,7 @@ const PlaneInfo kPlaneInfo[kPlaneSlots] = {
     {1, 2},  // HISTORY_LENGTH R8_UINT (only while option svgf_reproject is 1: alloc_history_length)
     {4, 2},  // SUBMESH_ID   R32_UINT (NEB_PLANE_SUBMESH_ID, behind the enum; only while option svgf_motion is 1: alloc_option_plane)
     {16, 1}, // PREV_POINT   R32G32B32A32 (NEB_PLANE_PREV_POINT, behind the enum; only while option svgf_vertex_motion is 1: alloc_option_plane)
+    {16, 1}, // DEMOD        R32G32B32A32_FLOAT (NEB_PLANE_DEMOD, behind the enum; only while option svgf_demodulate is 1: alloc_option_plane)
 };
 } // namespace neb
 
@@ -121,8 +122,8 @@ static int alloc_planes(neb_ctx* ctx)
 }
 
 // The planes that exist only while their option is on: history length (svgf_reproject; zeroed: no pixel has history yet), submesh id
-// (svgf_motion; zeroed) and previous point (svgf_vertex_motion: one slot, every byte 0xFF -- .w is then the sentinel "no per-vertex motion"
-// and .xyz is never read, where a zeroed entry would be a valid point at the origin).
+// (svgf_motion; zeroed), previous point (svgf_vertex_motion: one slot, every byte 0xFF -- .w is then the sentinel "no per-vertex motion"
+// and .xyz is never read, where a zeroed entry would be a valid point at the origin) and demodulated colour (svgf_demodulate; zeroed).
 static void free_option_plane(neb_ctx* ctx, int plane)
 {
     for (int s = 0; s < 2; ++s)
@@ -142,6 +143,14 @@ static int alloc_option_plane(neb_ctx* ctx, int plane)
     }
     NEB_HIP(ctx, hipDeviceSynchronize());
     return NEB_OK;
+}
+// Option svgf_demodulate: the demod plane no longer matches any radiance slot (the next temporal call seeds it)
+static void demod_invalidate(neb_ctx* ctx) { ctx->demod_slot = -1; }
+// ... does it hold radiance[hist] demodulated?  Written by the last level in the bracket before this one, or seeded in this one, for the slot
+// that is hist now.
+static bool demod_valid(const neb_ctx* ctx)
+{
+    return ctx->demod_slot == ctx->hist && (ctx->demod_serial == ctx->frame_serial || ctx->demod_serial + 1 == ctx->frame_serial);
 }
 static void free_history_length(neb_ctx* ctx) { free_option_plane(ctx, NEB_PLANE_HISTORY_LENGTH); }
 static int alloc_history_length(neb_ctx* ctx) { return alloc_option_plane(ctx, NEB_PLANE_HISTORY_LENGTH); }
@@ -224,6 +233,10 @@ int neb_resize(neb_ctx* ctx, uint32_t width, uint32_t height)
     if (ctx->motion)
         if (int rc = alloc_option_plane(ctx, NEB_PLANE_SUBMESH_ID))
             return rc;
+    demod_invalidate(ctx);
+    if (ctx->demod)
+        if (int rc = alloc_option_plane(ctx, NEB_PLANE_DEMOD))
+            return rc;
     return ctx->vertex_motion ? alloc_option_plane(ctx, NEB_PLANE_PREV_POINT) : NEB_OK;
 }
 
@@ -270,6 +283,7 @@ int neb_begin_frame(neb_ctx* ctx, uint32_t frame_index)
         return rc;
     ctx->cur = (int)(frame_index & 1u); // SVGFDenoiser.cpp:41-42
     ctx->hist = ctx->cur ^ 1;
+    ++ctx->frame_serial;
     geometry_invalidate(ctx); // a new frame has a new G-buffer
     return NEB_OK;
 }
@@ -329,6 +343,7 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
             return fail(ctx, NEB_ERR_INVALID_ARG, "neb_set_option: svgf_profile must be 0, 1 (an event in front of every kernel) or 2 (first kernel / the rest)");
         ctx->profile = value;
         ctx->prof_recorded = 0;
+        ctx->demod_seeds = 0;
         return NEB_OK;
     }
     if (!strcmp(key, "svgf_fuse")) {
@@ -357,6 +372,29 @@ int neb_set_option(neb_ctx* ctx, const char* key, int value)
             free_history_length(ctx);
         }
         ctx->reproject = value;
+        return NEB_OK;
+    }
+    if (!strcmp(key, "svgf_demodulate")) {
+        if (value < 0 || value > 1)
+            return fail(ctx, NEB_ERR_INVALID_ARG, "neb_set_option: svgf_demodulate must be 0 or 1");
+        if (value && (ctx->row_begin != 0 || ctx->row_end != ctx->H))
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_demodulate needs a whole-frame context (row strips are not supported)");
+        if (value && ctx->levels == 0)
+            return fail(ctx, NEB_ERR_STATE, "neb_set_option: svgf_demodulate needs atrous_levels >= 1 (the last level multiplies the albedo back)");
+        if (value == ctx->demod)
+            return NEB_OK;
+        NEB_GUARD(ctx);
+        if (value) {
+            if (int rc = alloc_option_plane(ctx, NEB_PLANE_DEMOD)) {
+                free_option_plane(ctx, NEB_PLANE_DEMOD);
+                return rc;
+            }
+        } else {
+            NEB_HIP(ctx, hipDeviceSynchronize()); // (work already enqueued may still read the plane)
+            free_option_plane(ctx, NEB_PLANE_DEMOD);
+        }
+        demod_invalidate(ctx); // (a plane just allocated holds no frame: the first temporal call seeds it)
+        ctx->demod = value;
         return NEB_OK;
     }
     if (!strcmp(key, "svgf_motion")) {
@@ -463,7 +501,7 @@ static int resolve_slot(const neb_ctx* ctx, int plane, int slot)
 {
     if (plane < 0 || plane >= kPlaneSlots)
         return -1;
-    if (plane == NEB_PLANE_PREV_POINT && !ctx->vertex_motion)
+    if ((plane == NEB_PLANE_PREV_POINT && !ctx->vertex_motion) || (plane == NEB_PLANE_DEMOD && !ctx->demod))
         return -1; // (no such plane while its option is off: the index answers as it did before the option existed)
     if (kPlaneInfo[plane].slots == 1)
         return (slot == 0 || slot == NEB_SLOT_CURRENT) ? 0 : -1;
@@ -484,7 +522,8 @@ int neb_get_plane(neb_ctx* ctx, int plane, int slot, void** dptr, size_t* pitch_
                                                   ? "neb_get_plane: the previous-point plane exists only while option svgf_vertex_motion is 1"
                                                   : "neb_get_plane: bad plane/slot");
     if (!ctx->planes[plane][s])
-        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_PREV_POINT ? "neb_get_plane: the previous-point plane is missing (a failed resize?)"
+        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_DEMOD ? "neb_get_plane: the demodulated-colour plane is missing (a failed resize?)"
+                                        : plane == NEB_PLANE_PREV_POINT ? "neb_get_plane: the previous-point plane is missing (a failed resize?)"
                                         : plane == NEB_PLANE_SUBMESH_ID ? "neb_get_plane: the submesh-id plane exists only while option svgf_motion is 1"
                                                                         : "neb_get_plane: the history-length plane exists only while option svgf_reproject is 1");
     if (int rc = svgf_flush_pending(ctx))
@@ -510,7 +549,8 @@ static int copy_rows(neb_ctx* ctx, int plane, int slot, uint32_t row0, uint32_t 
                                                   ? "copy rows: the previous-point plane exists only while option svgf_vertex_motion is 1"
                                                   : "copy rows: bad plane/slot");
     if (!ctx->planes[plane][s])
-        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_PREV_POINT ? "copy rows: the previous-point plane is missing (a failed resize?)"
+        return fail(ctx, NEB_ERR_STATE, plane == NEB_PLANE_DEMOD ? "copy rows: the demodulated-colour plane is missing (a failed resize?)"
+                                        : plane == NEB_PLANE_PREV_POINT ? "copy rows: the previous-point plane is missing (a failed resize?)"
                                         : plane == NEB_PLANE_SUBMESH_ID ? "copy rows: the submesh-id plane exists only while option svgf_motion is 1"
                                                                         : "copy rows: the history-length plane exists only while option svgf_reproject is 1");
     if (row0 < ctx->row_begin || row0 + nrows > ctx->row_end)
@@ -522,6 +562,8 @@ static int copy_rows(neb_ctx* ctx, int plane, int slot, uint32_t row0, uint32_t 
     NEB_GUARD(ctx);
     if (upload && (plane == NEB_PLANE_NORMAL || plane == NEB_PLANE_DEPTH))
         geometry_invalidate(ctx);
+    if (upload && plane == NEB_PLANE_RADIANCE && s == ctx->demod_slot)
+        demod_invalidate(ctx); // the image the demod plane holds demodulated is being overwritten
     if (upload)
         NEB_HIP(ctx, hipMemcpyAsync(d, host, pitch * nrows, hipMemcpyHostToDevice, (hipStream_t)stream));
     else
@@ -563,6 +605,7 @@ int neb_svgf_reset_history(neb_ctx* ctx, neb_stream stream)
     const size_t bytes = (size_t)ctx->W * (ctx->row_end - ctx->row_begin) * 16;
     NEB_HIP(ctx, hipMemcpyAsync(ctx->planes[NEB_PLANE_RADIANCE][ctx->hist], ctx->planes[NEB_PLANE_RADIANCE][ctx->cur],
                                 bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    demod_invalidate(ctx); // radiance[hist] is the (modulated) current image now
     if (ctx->reproject) // reprojection mode: no pixel has history any more
         NEB_HIP(ctx, hipMemsetAsync(ctx->planes[NEB_PLANE_HISTORY_LENGTH][ctx->hist], 0, (size_t)ctx->W * (ctx->row_end - ctx->row_begin),
                                     (hipStream_t)stream));
@@ -665,6 +708,25 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
     // the pass also leaves normal[cur] / depth[cur] decoded in the geometry plane for the a-trous levels -- for the pixels it
     // covers: with a ragged right / bottom remainder (Dispatch(W/8, H/8) floors) the levels' taps clamp into pixels it skips
     const bool fused_geometry = (ctx->W % 8u) == 0 && (ctx->H % 8u) == 0;
+    // option svgf_demodulate: the history is the demod plane (seeded from radiance[hist] over its albedo where it does not hold the last denoised
+    // frame), the pixel's own radiance is divided by its albedo on load
+    const float4* rad_hist = (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h];
+    const uint32_t* demod_albedo = nullptr;
+    if (ctx->demod) {
+        float4* const demod = (float4*)ctx->planes[NEB_PLANE_DEMOD][0];
+        if (!demod)
+            return fail(ctx, NEB_ERR_STATE, "neb_svgf_temporal: the demodulated-colour plane is missing (a failed resize?)");
+        demod_albedo = (const uint32_t*)ctx->planes[NEB_PLANE_ALBEDO][0];
+        if (!demod_valid(ctx)) {
+            hipError_t se = launch_demod_seed(rad_hist, demod_albedo, demod, (size_t)ctx->W * (ctx->row_end - ctx->row_begin), (hipStream_t)stream);
+            if (se != hipSuccess)
+                return fail(ctx, NEB_ERR_HIP, "svgf_demod_seed launch", se);
+            ctx->demod_serial = ctx->frame_serial;
+            ctx->demod_slot = h;
+            ++ctx->demod_seeds;
+        }
+        rad_hist = demod;
+    }
     if (ctx->reproject) {
         // reprojected taps may come from any row: whole frames only (a strip context cannot turn the option on)
         if (row0 != 0 || row1 != ctx->H)
@@ -696,14 +758,14 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
                 mo.n_delta = ctx->motion_geoms;
             }
             hipError_t e = launch_temporal_reproject_motion(make_launch(ctx, row0, row1), bc, ctx->has_cam[h] ? &bh : nullptr,
-                                                            (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
+                                                            (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], rad_hist,
                                                             (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c], (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][h],
                                                             (const uint2*)ctx->planes[NEB_PLANE_NORMAL][c], (const uint2*)ctx->planes[NEB_PLANE_NORMAL][h],
                                                             (const uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][h], (uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][c],
                                                             (uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
                                                             (const uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][h],
                                                             (uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][c],
-                                                            fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, mo, (hipStream_t)stream);
+                                                            fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, mo, (hipStream_t)stream, demod_albedo);
             if (e != hipSuccess)
                 return fail(ctx, NEB_ERR_HIP, "svgf_temporal_reproject (motion) launch", e);
             if (fused_geometry)
@@ -711,14 +773,14 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
             return NEB_OK;
         }
         hipError_t e = launch_temporal_reproject(make_launch(ctx, row0, row1), bc, ctx->has_cam[h] ? &bh : nullptr,
-                                                 (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
+                                                 (float4*)ctx->planes[NEB_PLANE_RADIANCE][c], rad_hist,
                                                  (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c], (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][h],
                                                  (const uint2*)ctx->planes[NEB_PLANE_NORMAL][c], (const uint2*)ctx->planes[NEB_PLANE_NORMAL][h],
                                                  (const uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][h], (uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][c],
                                                  (uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
                                                  (const uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][h],
                                                  (uint8_t*)ctx->planes[NEB_PLANE_HISTORY_LENGTH][c],
-                                                 fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, (hipStream_t)stream);
+                                                 fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, (hipStream_t)stream, demod_albedo);
         if (e != hipSuccess)
             return fail(ctx, NEB_ERR_HIP, "svgf_temporal_reproject launch", e);
         if (fused_geometry)
@@ -726,7 +788,7 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
         return NEB_OK;
     }
     hipError_t e = launch_temporal(make_launch(ctx, row0, row1), (float4*)ctx->planes[NEB_PLANE_RADIANCE][c],
-                                   (const float4*)ctx->planes[NEB_PLANE_RADIANCE][h],
+                                   rad_hist,
                                    (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][c],
                                    (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][h],
                                    (const uint2*)ctx->planes[NEB_PLANE_NORMAL][c],
@@ -734,7 +796,7 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
                                    (const uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][h],
                                    (uint32_t*)ctx->planes[NEB_PLANE_MOMENTS][c],
                                    (uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
-                                   fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, (hipStream_t)stream);
+                                   fused_geometry ? (float4*)ctx->planes[NEB_PLANE_GEOMETRY][0] : nullptr, (hipStream_t)stream, demod_albedo);
     if (e != hipSuccess)
         return fail(ctx, NEB_ERR_HIP, "svgf_temporal launch", e);
     if (fused_geometry)
@@ -744,10 +806,11 @@ int neb_svgf_temporal_rows(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_strea
 
 // Can this context's next frame run as the fused chain (temporal pass inside level 0, intermediate planes carrying the
 // luminance)?  A whole frame whose every pixel both passes cover (Dispatch(W/8, H/8) floors), every level on the LDS kernel.
-// Not in reprojection mode: its temporal pass is a kernel of its own, followed by the separate levels.
+// Not in reprojection mode: its temporal pass is a kernel of its own, followed by the separate levels.  Not with option svgf_demodulate: the
+// two operations live in the separate kernels' arms only.
 static bool fused_chain_possible(const neb_ctx* ctx)
 {
-    if (ctx->reproject)
+    if (ctx->reproject || ctx->demod)
         return false;
     if (ctx->row_begin != 0 || ctx->row_end != ctx->H || (ctx->W % 8u) || (ctx->H % 8u) || ctx->levels == 0)
         return false;
@@ -845,10 +908,25 @@ int neb_svgf_atrous_level_rows(neb_ctx* ctx, uint32_t level, uint32_t row0, uint
     char range_name[64];
     snprintf(range_name, sizeof(range_name), "SVGF: A-Trous compute %u (step %u)", level, step); // SVGFDenoiser.cpp:155
     ScopedRange range(range_name);
-    hipError_t e = launch_atrous(make_launch(ctx, row0, row1), ctx->atrous_variant, step,
-                                 (const float4*)ctx->planes[sp][ss], (float4*)ctx->planes[dp][ds],
-                                 (const uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
-                                 (const float4*)ctx->planes[NEB_PLANE_GEOMETRY][0], (hipStream_t)stream);
+    hipError_t e;
+    if (ctx->demod && level + 1 == ctx->levels) {
+        // option svgf_demodulate, the level whose destination is the chain's result: the filtered colour unmodulated into the demod plane (the
+        // next frame's history), times the output pixel's albedo divisor into the destination
+        if (!ctx->planes[NEB_PLANE_DEMOD][0])
+            return fail(ctx, NEB_ERR_STATE, "neb_svgf_atrous_level_rows: the demodulated-colour plane is missing (a failed resize?)");
+        e = launch_atrous_remodulate(make_launch(ctx, row0, row1), ctx->atrous_variant, step, (const float4*)ctx->planes[sp][ss],
+                                     (float4*)ctx->planes[dp][ds], (const uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0],
+                                     (const float4*)ctx->planes[NEB_PLANE_GEOMETRY][0], (const uint32_t*)ctx->planes[NEB_PLANE_ALBEDO][0],
+                                     (float4*)ctx->planes[NEB_PLANE_DEMOD][0], (hipStream_t)stream);
+        // the plane holds radiance[cur] demodulated once the whole frame has been through (a caller that runs the level in row ranges and
+        // leaves some out gets the seed kernel next frame)
+        ctx->demod_serial = ctx->frame_serial;
+        ctx->demod_slot = (row0 == 0 && row1 == ctx->H) ? ctx->cur : -1;
+    } else {
+        e = launch_atrous(make_launch(ctx, row0, row1), ctx->atrous_variant, step, (const float4*)ctx->planes[sp][ss], (float4*)ctx->planes[dp][ds],
+                          (const uint16_t*)ctx->planes[NEB_PLANE_VARIANCE][0], (const float4*)ctx->planes[NEB_PLANE_GEOMETRY][0],
+                          (hipStream_t)stream);
+    }
     if (e != hipSuccess)
         return fail(ctx, NEB_ERR_HIP, "svgf_atrous launch", e);
     return NEB_OK;
@@ -982,6 +1060,9 @@ int neb_svgf_level_times(neb_ctx* ctx, float* out_us, uint32_t capacity, uint32_
         out_us[k] = ms * 1e3f;
     }
     *n_out = n < capacity ? n : capacity;
+    // option svgf_demodulate: one more entry behind the times -- how many temporal calls have run the seed kernel since "svgf_profile" was set
+    if (ctx->demod && *n_out < capacity)
+        out_us[(*n_out)++] = (float)ctx->demod_seeds;
     return NEB_OK;
 }
 

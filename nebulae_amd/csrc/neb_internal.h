@@ -14,8 +14,9 @@ struct PlaneInfo {
     uint32_t bytes_per_px;
     uint32_t slots;
 };
-// the reference-format planes of the enum, and behind them NEB_PLANE_SUBMESH_ID and NEB_PLANE_PREV_POINT (not counted by NEB_PLANE_COUNT)
-constexpr int kPlaneSlots = NEB_PLANE_COUNT + 2;
+// the reference-format planes of the enum, and behind them NEB_PLANE_SUBMESH_ID, NEB_PLANE_PREV_POINT and NEB_PLANE_DEMOD (not counted by
+// NEB_PLANE_COUNT)
+constexpr int kPlaneSlots = NEB_PLANE_COUNT + 3;
 extern const PlaneInfo kPlaneInfo[kPlaneSlots];
 
 // Every entry point that launches or copies runs on its context's device whatever device the calling thread had
@@ -66,12 +67,19 @@ struct SvgfLaunch {
 // Kernel launchers (enqueue only).  All pointers are device pointers to resident row `row_begin`.
 hipError_t launch_temporal(const SvgfLaunch& L, float4* rad_cur, const float4* rad_hist, const uint32_t* depth_cur,
                            const uint32_t* depth_hist, const uint2* normal_cur, const uint2* normal_hist,
-                           const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance, float4* geometry, hipStream_t s);
+                           const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance, float4* geometry, hipStream_t s,
+                           const uint32_t* demod_albedo = nullptr);
+// (demod_albedo, here and on the reprojecting launchers: option svgf_demodulate -- NEB_PLANE_ALBEDO; the pixel's own radiance is divided by its
+// divisor on load and rad_hist is NEB_PLANE_DEMOD.  Null: the pass as it is without the option.)
 
 // `geometry`: {decoded shading normal.xyz, depth} per pixel (NEB_PLANE_GEOMETRY), valid for every tap row.
 // variant 0 = direct-load kernel, 1 = LDS row-lattice kernel (steps <= 32; wider steps take the direct kernel)
 hipError_t launch_atrous(const SvgfLaunch& L, int variant, uint32_t step, const float4* src, float4* dst,
                          const uint16_t* variance, const float4* geometry, hipStream_t s);
+// Option svgf_demodulate, the level whose destination is the chain's result: the same filter, the filtered colour unmodulated into `demod_out`
+// (NEB_PLANE_DEMOD) and times the output pixel's divisor (svgf_demod.h; `albedo` = NEB_PLANE_ALBEDO) into dst
+hipError_t launch_atrous_remodulate(const SvgfLaunch& L, int variant, uint32_t step, const float4* src, float4* dst, const uint16_t* variance,
+                                    const float4* geometry, const uint32_t* albedo, float4* demod_out, hipStream_t s);
 // true when launch_atrous(L, variant, step, ...) runs the LDS kernel (what the whole-frame fast path below requires of every level)
 bool atrous_lds_serves(const SvgfLaunch& L, int variant, uint32_t step);
 // Whole-frame denoise, levels after the first: src holds {r, g, b, lum} (written by the level before); dst gets {r, g, b, lum},
@@ -83,6 +91,9 @@ hipError_t launch_atrous_lum(const SvgfLaunch& L, uint32_t step, bool last, cons
 hipError_t launch_atrous_fused_temporal(const SvgfLaunch& L, bool only_level, const float4* rad_cur, const float4* rad_hist, const uint32_t* depth_cur,
                                         const uint32_t* depth_hist, const uint2* normal_cur, const uint2* normal_hist, const uint32_t* mom_hist,
                                         uint32_t* mom_cur, uint16_t* variance, float4* geometry, float4* dst, hipStream_t s);
+// Option svgf_demodulate: the stand-in history where NEB_PLANE_DEMOD does not hold the last denoised frame -- over the n resident pixels,
+// demod[i].rgb = rad_hist[i].rgb / divisor(albedo[i])
+hipError_t launch_demod_seed(const float4* rad_hist, const uint32_t* albedo, float4* demod, size_t n, hipStream_t s);
 // A camera as neb_gbuffer_raycast's kernel uses it: eye, the view axes (z points from the target to the eye), tan(vfov / 2), aspect and
 // the two depth-mapping entries of XMMatrixPerspectiveFovRH.  One host function builds it for the G-buffer producer and for the
 // reprojecting temporal pass, so that both see the same float bits.
@@ -122,7 +133,8 @@ inline CameraBasis camera_basis(const neb_camera& cam, uint32_t W, uint32_t H)
 hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
                                      const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
                                      const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
-                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s);
+                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s,
+                                     const uint32_t* demod_albedo = nullptr);
 
 // Option svgf_motion: the motion arm of the same kernel (svgf_temporal_reproject_kernel<ReprojMode::Submesh>) -- id planes of the two slots, and
 // the per-geometry delta table launch_reproj_delta wrote in front of it (n_delta = 0: nothing moved between the two snapshots).
@@ -134,11 +146,14 @@ struct ReprojMotion {
     // Option svgf_vertex_motion: NEB_PLANE_PREV_POINT, {P_h.xyz, oct16(N_h) | kReprojNoPrevPoint} per pixel.  Non-null picks the third arm
     // of the kernel (ReprojMode::Vertex), which takes P and the geometric normal from it where .w is not the sentinel.
     const float4* prev_point = nullptr;
+    // Option svgf_demodulate: NEB_PLANE_ALBEDO (set by the launcher from its demod_albedo; picks the ...Demod mode of the arm)
+    const uint32_t* demod_albedo = nullptr;
 };
 hipError_t launch_temporal_reproject_motion(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
                                             const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
                                             const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
-                                            const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion& motion, hipStream_t s);
+                                            const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion& motion, hipStream_t s,
+                                            const uint32_t* demod_albedo = nullptr);
 // one lane per geometry: the two slots' 4x4 tables (n x 16 floats, row-vector convention) -> n delta entries
 hipError_t launch_reproj_delta(const float* xf_cur, const float* xf_hist, float4* delta, uint32_t n, hipStream_t s);
 
@@ -206,6 +221,14 @@ struct neb_ctx {
     uint32_t snap_epoch[2] = {0, 0};   // updates enqueued before the snapshot: equal for both slots = nothing moved between them
     float4* motion_delta = nullptr;    // reproj_delta_kernel's output, n_geoms entries
     uint32_t motion_geoms = 0;         // geometries the three tables were sized for
+    // option svgf_demodulate: albedo divided out in front of the temporal pass, multiplied back at the last level (planes[NEB_PLANE_DEMOD] exists
+    // only then: the demodulated denoised colour = the temporal pass's history).  The plane is valid for a temporal call iff it matches
+    // radiance[hist]: written by the last level in the bracket before (or seeded in this one) for the slot that is now hist.
+    int demod = 0;
+    uint64_t frame_serial = 0;         // neb_begin_frame calls so far
+    uint64_t demod_serial = 0;         // the bracket in which the last level wrote the demod plane, or the seed kernel did
+    int demod_slot = -1;               // the radiance slot whose image it then held demodulated (-1: none -- uploads, reset_history, resize)
+    uint32_t demod_seeds = 0;          // seed launches since option svgf_profile was last set (neb_svgf_level_times reports it)
     int vertex_motion = 0;             // option svgf_vertex_motion: the temporal pass follows deformed submeshes (planes[NEB_PLANE_PREV_POINT] exists only then)
     neb::GiState* gi = nullptr;
     // neb_strip_frame* (strips.hip): a side stream for the halo exchange beside level 0, and the events that order it -- created on first use

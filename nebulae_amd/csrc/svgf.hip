@@ -17,6 +17,7 @@
 
 #include "neb_device.h"
 #include "neb_internal.h"
+#include "svgf_demod.h"
 #include "svgf_reproject.h"
 
 // Tuning knobs (tools/build_variant.sh): the product is built with none of them set.
@@ -93,7 +94,11 @@ __device__ __forceinline__ uint2 temporal_moments(float4 Cc, uint32_t mh, float 
     return temporal_moments_f(Cc, half_bits_to_float(mh & 0xffffu), half_bits_to_float(mh >> 16), alpha, varianceEps);
 }
 
-__global__ __launch_bounds__(256) void svgf_temporal_kernel(TemporalArgs a)
+// DEMOD (option svgf_demodulate): the pixel's own radiance is divided by its albedo divisor on load -- the albedo word is one more
+// load of the pixel's single round trip -- and a.rad_hist is the demod plane, which needs no albedo.  Moments, variance and the accumulated
+// colour are then those of the demodulated signal.  DEMOD = false is the kernel as it was: `albedo` is not read and the code is the same.
+template <bool DEMOD>
+__device__ __forceinline__ void temporal_pixel(const TemporalArgs& a, const uint32_t* __restrict__ albedo)
 {
     const uint32_t gid = blockIdx.x * 256u + threadIdx.x;
     if (gid >= a.Wd * a.nrows)
@@ -102,11 +107,13 @@ __global__ __launch_bounds__(256) void svgf_temporal_kernel(TemporalArgs a)
     const uint32_t x = gid - ry * a.Wd;
     const size_t i = (size_t)(a.row_off + ry) * a.W + x;
 
-    const float4 Cc = a.rad_cur[i];
+    float4 Cc = a.rad_cur[i];
     const float4 Ch = a.rad_hist[i];
     const uint32_t dc = a.depth_cur[i], dh = a.depth_hist[i];
     const uint32_t nc = a.normal_cur[i].y, nh = a.normal_hist[i].y; // .zw = shading normal
     const uint32_t mh = a.mom_hist[i];
+    if constexpr (DEMOD)
+        Cc = demodulate(Cc, albedo[i]);
 
     float3 Nc;
     float zc;
@@ -119,9 +126,32 @@ __global__ __launch_bounds__(256) void svgf_temporal_kernel(TemporalArgs a)
     a.variance[i] = (uint16_t)mv.y;
 }
 
+__global__ __launch_bounds__(256) void svgf_temporal_kernel(TemporalArgs a) { temporal_pixel<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void svgf_temporal_demod_kernel(TemporalArgs a, const uint32_t* __restrict__ albedo) { temporal_pixel<true>(a, albedo); }
+
+// Option svgf_demodulate: the stand-in history of a frame whose demod plane does not hold the last denoised frame (see the validity rule in
+// nebulae_hip.h) -- radiance[hist] over its own albedo, exact for a static camera.  Every resident pixel, 36 B each.
+__global__ __launch_bounds__(256) void svgf_demod_seed_kernel(const float4* __restrict__ rad_hist, const uint32_t* __restrict__ albedo,
+                                                              float4* __restrict__ demod, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n)
+        return;
+    demod[i] = demodulate(rad_hist[i], albedo[i]);
+}
+
+hipError_t launch_demod_seed(const float4* rad_hist, const uint32_t* albedo, float4* demod, size_t n, hipStream_t s)
+{
+    if (n == 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(svgf_demod_seed_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, rad_hist, albedo, demod, n);
+    return hipGetLastError();
+}
+
 hipError_t launch_temporal(const SvgfLaunch& L, float4* rad_cur, const float4* rad_hist, const uint32_t* depth_cur,
                            const uint32_t* depth_hist, const uint2* normal_cur, const uint2* normal_hist,
-                           const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance, float4* geometry, hipStream_t s)
+                           const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance, float4* geometry, hipStream_t s,
+                           const uint32_t* demod_albedo)
 {
     const uint32_t Wd = (L.W / 8u) * 8u, Hd = (L.H / 8u) * 8u; // Dispatch(W/8,H/8): SVGFDenoiser.cpp:116
     const uint32_t row1 = L.row1 < Hd ? L.row1 : Hd;
@@ -147,7 +177,10 @@ hipError_t launch_temporal(const SvgfLaunch& L, float4* rad_cur, const float4* r
     a.varianceEps = L.p.varianceEps;
     const uint64_t n = (uint64_t)Wd * a.nrows;
     const uint32_t blocks = (uint32_t)((n + 255) / 256);
-    hipLaunchKernelGGL(svgf_temporal_kernel, dim3(blocks), dim3(256), 0, s, a);
+    if (demod_albedo)
+        hipLaunchKernelGGL(svgf_temporal_demod_kernel, dim3(blocks), dim3(256), 0, s, a, demod_albedo);
+    else
+        hipLaunchKernelGGL(svgf_temporal_kernel, dim3(blocks), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
@@ -333,11 +366,16 @@ hipError_t launch_reproj_delta(const float* xf_cur, const float* xf_hist, float4
 // MODE = Vertex (option svgf_vertex_motion) on top of Submesh: the pixel's entry of NEB_PLANE_PREV_POINT is read in the
 // same round trip as its id; where its .w is not the sentinel it IS the previous point and geometric normal and the delta entry is not
 // read, where it is the sentinel the Submesh rule applies unchanged.  Everything behind P and Ng is shared by the three arms.
-enum class ReprojMode { Off, Submesh, Vertex };
+// The three ...Demod modes (option svgf_demodulate on top of each arm): as temporal_pixel's DEMOD -- the albedo word
+// (m.demod_albedo) is loaded with the pixel's own planes (the same first round trip), Cc is demodulated before anything reads it, and
+// a.rad_hist is the demod plane for all four taps.  The first three modes are the kernels as they were: m.demod_albedo is not read.
+enum class ReprojMode { Off, Submesh, Vertex, OffDemod, SubmeshDemod, VertexDemod };
 template <ReprojMode MODE>
 __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs a, ReprojMotion m)
 {
-    constexpr bool MOTION = MODE != ReprojMode::Off, VERTEX = MODE == ReprojMode::Vertex;
+    constexpr bool DEMOD = MODE == ReprojMode::OffDemod || MODE == ReprojMode::SubmeshDemod || MODE == ReprojMode::VertexDemod;
+    constexpr bool VERTEX = MODE == ReprojMode::Vertex || MODE == ReprojMode::VertexDemod;
+    constexpr bool MOTION = VERTEX || MODE == ReprojMode::Submesh || MODE == ReprojMode::SubmeshDemod;
     const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6);
     if (tile >= a.n_tiles)
         return;
@@ -346,7 +384,7 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
     const int x = (int)(tx * 8u + (lane & 7u)), y = (int)(ty * 8u + (lane >> 3));
     const size_t i = (size_t)y * a.W + (uint32_t)x;
 
-    const float4 Cc = a.rad_cur[i];
+    float4 Cc = a.rad_cur[i];
     const uint32_t dc = a.depth_cur[i];
     const uint2 nc = a.normal_cur[i];
     uint32_t g = kReprojNoSubmesh;
@@ -355,6 +393,8 @@ __global__ __launch_bounds__(256) void svgf_temporal_reproject_kernel(ReprojArgs
     float4 pv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if constexpr (VERTEX)
         pv = m.prev_point[i];
+    if constexpr (DEMOD)
+        Cc = demodulate(Cc, m.demod_albedo[i]);
     const float zc = depth_unorm24(dc);
 
     float4 Ch = Cc; // (with no history: a = 0 and lerp(Cc, Cc, 0) = Cc exactly)
@@ -492,7 +532,8 @@ static ReprojCam reproj_cam(const CameraBasis& b)
 static hipError_t launch_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
                                    const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
                                    const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
-                                   const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion* motion, hipStream_t s)
+                                   const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion* motion, hipStream_t s,
+                                   const uint32_t* demod_albedo)
 {
     const uint32_t Wd = (L.W / 8u) * 8u, Hd = (L.H / 8u) * 8u; // the same-pixel pass's Dispatch(W/8, H/8) region
     if (Wd == 0 || Hd == 0)
@@ -524,6 +565,18 @@ static hipError_t launch_reproject(const SvgfLaunch& L, const CameraBasis& cam_c
     a.hist_ok = cam_hist != nullptr;
     a.cc = reproj_cam(cam_cur);
     a.ch = reproj_cam(cam_hist ? *cam_hist : cam_cur);
+    const dim3 grid((a.n_tiles + 3u) / 4u);
+    if (demod_albedo) {
+        ReprojMotion mo = motion ? *motion : ReprojMotion{};
+        mo.demod_albedo = demod_albedo;
+        if (motion && motion->prev_point)
+            hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::VertexDemod>, grid, dim3(256), 0, s, a, mo);
+        else if (motion)
+            hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::SubmeshDemod>, grid, dim3(256), 0, s, a, mo);
+        else
+            hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::OffDemod>, grid, dim3(256), 0, s, a, mo);
+        return hipGetLastError();
+    }
     if (motion && motion->prev_point)
         hipLaunchKernelGGL(svgf_temporal_reproject_kernel<ReprojMode::Vertex>, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, s, a, *motion);
     else if (motion)
@@ -536,19 +589,20 @@ static hipError_t launch_reproject(const SvgfLaunch& L, const CameraBasis& cam_c
 hipError_t launch_temporal_reproject(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
                                      const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
                                      const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
-                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s)
+                                     const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, hipStream_t s, const uint32_t* demod_albedo)
 {
     return launch_reproject(L, cam_cur, cam_hist, rad_cur, rad_hist, depth_cur, depth_hist, normal_cur, normal_hist, mom_hist, mom_cur, variance,
-                            hlen_hist, hlen_cur, geometry, nullptr, s);
+                            hlen_hist, hlen_cur, geometry, nullptr, s, demod_albedo);
 }
 
 hipError_t launch_temporal_reproject_motion(const SvgfLaunch& L, const CameraBasis& cam_cur, const CameraBasis* cam_hist, float4* rad_cur,
                                             const float4* rad_hist, const uint32_t* depth_cur, const uint32_t* depth_hist, const uint2* normal_cur,
                                             const uint2* normal_hist, const uint32_t* mom_hist, uint32_t* mom_cur, uint16_t* variance,
-                                            const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion& motion, hipStream_t s)
+                                            const uint8_t* hlen_hist, uint8_t* hlen_cur, float4* geometry, const ReprojMotion& motion, hipStream_t s,
+                                            const uint32_t* demod_albedo)
 {
     return launch_reproject(L, cam_cur, cam_hist, rad_cur, rad_hist, depth_cur, depth_hist, normal_cur, normal_hist, mom_hist, mom_cur, variance,
-                            hlen_hist, hlen_cur, geometry, &motion, s);
+                            hlen_hist, hlen_cur, geometry, &motion, s, demod_albedo);
 }
 
 // The same decode for rows the temporal pass did not cover (halo rows of a strip; ragged images; a level run on its own).
@@ -615,16 +669,24 @@ struct AtrousArgs {
     uint32_t nblocks;           // real block count (grid is padded to a multiple of 8)
     float cz;                   // log2e / (phiDepth * step)
     float phiColor, phiNormal;
-    // kInFused only: the temporal pass's own planes (src = radiance[cur] as rendered) and constants
+    // kInFused only: the temporal pass's own planes (src = radiance[cur] as rendered) and constants.  The remodulating arms (kInClassicDemod and
+    // the direct kernel's) never run fused and keep their two planes in members of it, so that the layout every other kernel reads stays as it is:
+    // `albedo` = NEB_PLANE_ALBEDO, `demod_out` = NEB_PLANE_DEMOD.
     const float4* rad_hist;
-    const uint32_t* depth_cur;
+    union {
+        const uint32_t* depth_cur;
+        const uint32_t* albedo;
+    };
     const uint32_t* depth_hist;
     const uint2* normal_cur;
     const uint2* normal_hist;
     const uint32_t* mom_hist;
     uint32_t* mom_cur;
     uint16_t* variance_out;
-    float4* geometry_out;
+    union {
+        float4* geometry_out;
+        float4* demod_out;
+    };
     float t_neg_inv_two_sigma2_log2e, t_alpha, t_varianceEps;
 };
 
@@ -798,6 +860,46 @@ __global__ __launch_bounds__(256) void svgf_atrous_direct_kernel(AtrousArgs a)
     a.dst[i] = make_float4(sr * inv, sg * inv, sb * inv, c0.w);
 }
 
+// The same as the chain's last level under option svgf_demodulate: the filtered colour goes unmodulated to a.demod_out and times the output
+// pixel's divisor to a.dst; the albedo word is loaded with the centre texel.  A kernel of its own, the taps written out a second time: the
+// kernel above called through a shared body comes out of the compiler with operands commuted, and it is pinned to stay as it was.
+__global__ __launch_bounds__(256) void svgf_atrous_direct_demod_kernel(AtrousArgs a)
+{
+    const int x = blockIdx.x * 64 + (threadIdx.x & 63);
+    const int y = a.row0 + blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= a.Wd || y >= a.row1)
+        return;
+    const size_t i = (size_t)(y - a.row_begin) * a.W + x;
+    const float4 c0 = a.src[i];
+    const uint32_t alb = a.albedo[i];
+    const float lum0 = luminance(c0.x, c0.y, c0.z);
+    const float cl = lum_scale(half_bits_to_float(a.variance[i]), a.phiColor);
+    const float4 g0 = a.geometry[i];
+    float sr = 0.f, sg = 0.f, sb = 0.f, sw = 0.f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; ++dy) {
+        const int qy = min(max(y + dy * a.step, 0), a.H - 1);
+        const size_t rowoff = (size_t)(qy - a.row_begin) * a.W;
+#pragma unroll
+        for (int dx = -2; dx <= 2; ++dx) {
+            const int qx = min(max(x + dx * a.step, 0), a.W - 1);
+            const float4 c = a.src[rowoff + qx];
+            const float4 g = a.geometry[rowoff + qx];
+            const float w = tap_weight(0.5f * g0.x, 0.5f * g0.y, 0.5f * g0.z, g0.w, lum0, cl, make_float4(c.x, c.y, c.z, luminance(c.x, c.y, c.z)), g,
+                                       a.phiNormal, a.cz, tap_constant(a.phiNormal, dx, dy));
+            sr = fmaf(w, c.x, sr);
+            sg = fmaf(w, c.y, sg);
+            sb = fmaf(w, c.z, sb);
+            sw += w;
+        }
+    }
+    const float inv = fast_rcp(fmaxf(sw, 1e-4f));
+    const float3 d = demod_divisor(alb);
+    const float r = sr * inv, g = sg * inv, b = sb * inv;
+    a.demod_out[i] = make_float4(r, g, b, c0.w);
+    a.dst[i] = make_float4(r * d.x, g * d.y, b * d.z, c0.w);
+}
+
 // LDS kernel: row-lattice tiles, persistent workgroups.
 //   Workgroup = 256 lanes = 4 waves.  Output tile = BW (64) columns x BH (= 4R)
 //   rows of the lattice {r + S*j}.  Taps of a lattice row are lattice rows j-2..j+2, so the
@@ -825,7 +927,10 @@ __global__ __launch_bounds__(256) void svgf_atrous_direct_kernel(AtrousArgs a)
 //   OUT_ALPHA: the output's .w is the centre pixel's alpha (the ABI's radiance planes) -- false: lum(output), for a
 //   following kInLum level.  The alpha comes from src (kInClassic), from alpha_src = the destination itself (kInLum: the
 //   last level writes radiance[cur], which still holds the frame's input) or from the fused staging (kInFused).
-enum : int { kInClassic = 0, kInLum = 1, kInFused = 2 };
+//   kInClassicDemod  kInClassic as the chain's last level under option svgf_demodulate (OUT_ALPHA = true): the output pixel's albedo word is
+//               fetched one tile ahead with its variance; the filtered colour goes unmodulated to demod_out and times the pixel's divisor
+//               (svgf_demod.h) to dst.  Staging, taps and schedule are kInClassic's.
+enum : int { kInClassic = 0, kInLum = 1, kInFused = 2, kInClassicDemod = 3 };
 
 // The columns of a tile.  Up to S = 8 a tile's 64 output columns are consecutive and it stages 64 + 4 S of them.  Beyond, that halo
 // doubles and triples the tile (128 staged columns per 64 outputs at S = 16), so the columns form a lattice too, in GROUPS of
@@ -865,6 +970,8 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
     constexpr int R = T::R, BW = T::BW, BH = T::BH, COLS = T::COLS, ROWS = T::ROWS, TOTAL = T::TOTAL, NLOAD = T::NLOAD, THREADS = T::THREADS;
     constexpr int XS = T::XS, XM = T::XM, SPAN = T::SPAN;
     static_assert(IN != kInFused || S == 1, "the fused temporal staging is level 0");
+    static_assert(IN != kInClassicDemod || OUT_ALPHA, "the remodulating level writes the chain's result");
+    constexpr bool kClassic = IN == kInClassic || IN == kInClassicDemod, kDemod = IN == kInClassicDemod;
     extern __shared__ float4 lds[];
     float4* __restrict__ A = lds;               // {r, g, b, lum}
     float4* __restrict__ B = lds + ROWS * COLS; // {nx, ny, nz, z}
@@ -894,7 +1001,7 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
     // plane's first element; the next interior tile puts the regular ones back.
     uint32_t toff[NLOAD];
     bool toff_regular = false;
-    float4 pc[IN == kInClassic ? NLOAD : 1];
+    float4 pc[kClassic ? NLOAD : 1];
 
     struct Tile {
         int r, jbase, x0;
@@ -964,7 +1071,7 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
     };
     // kInClassic: the next tile's radiance, into registers
     auto issue_load = [&](int k, const Tile& o) {
-        if constexpr (IN == kInClassic) {
+        if constexpr (kClassic) {
             if (threadIdx.x + THREADS * k < TOTAL)
                 pc[k] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(src + o.first) + toff[k]);
         }
@@ -985,7 +1092,7 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
     // The centre pixel's variance and alpha (the per-pixel inputs that are not staged) are fetched one tile ahead as
     // well: loaded at the start of the filter phase they were a dependent global round trip in front of every tile's
     // arithmetic (2.5 us per level).  (kInFused has both in LDS.)
-    uint32_t nvar[R];
+    uint32_t nvar[R], nalb[kDemod ? R : 1];
     float nalpha[R];
     auto issue_centre_loads = [&](const Tile& o) {
         if constexpr (IN != kInFused) {
@@ -999,7 +1106,9 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
                     const size_t i = (size_t)(yo - a.row_begin) * a.W + xo;
                     nvar[k] = a.variance[i];
                     if constexpr (OUT_ALPHA)
-                        nalpha[k] = reinterpret_cast<const float*>(IN == kInClassic ? src : a.alpha_src)[4 * i + 3];
+                        nalpha[k] = reinterpret_cast<const float*>(kClassic ? src : a.alpha_src)[4 * i + 3];
+                    if constexpr (kDemod)
+                        nalb[k] = a.albedo[i];
                 }
             }
         }
@@ -1076,7 +1185,7 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
         }
         const int cr = nt.r, cjbase = nt.jbase, cx0 = nt.x0;
         // ---- stage the tile ----
-        if constexpr (IN == kInClassic) {
+        if constexpr (kClassic) {
             issue_dma(geometry, B, nt); // first: its flight overlaps the wait for the prefetched radiance and the luminance arithmetic
             float lum[NLOAD];
 #pragma unroll
@@ -1145,11 +1254,14 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
         __syncthreads(); // (also waits for this wave's DMA: an LDS-DMA is a pending LDS write on the VM counter)
 
         // ---- next tile: issue its loads now, consume them after this tile is filtered ----
-        uint32_t cvar[R];
+        uint32_t cvar[R], calb[kDemod ? R : 1];
         float calpha[R];
 #pragma unroll
-        for (int k = 0; k < R; ++k)
+        for (int k = 0; k < R; ++k) {
             cvar[k] = nvar[k], calpha[k] = nalpha[k];
+            if constexpr (kDemod)
+                calb[k] = nalb[k];
+        }
         bool have_next = false;
         t += wgs_per_xcd;
         while (t < t_end && !(have_next = tile_origin(t, nt)))
@@ -1320,6 +1432,13 @@ __global__ __launch_bounds__(256, (AtrousTile<S, IN>::WAVES_PER_SIMD)) void svgf
             const int yo = cr + S * (cjbase + rg * R + k);
             const float inv = fast_rcp(fmaxf(sw[k], 1e-4f)); // :84
             const float r = sr[k] * inv, g = sg[k] * inv, b = sb[k] * inv;
+            if constexpr (kDemod) {
+                const float3 d = demod_divisor(calb[k]);
+                const size_t o = (size_t)(yo - a.row_begin) * a.W + xo;
+                store_output(a.demod_out + o, make_float4(r, g, b, alpha0[k]));
+                store_output(a.dst + o, make_float4(r * d.x, g * d.y, b * d.z, alpha0[k]));
+                continue;
+            }
             store_output(a.dst + ((size_t)(yo - a.row_begin) * a.W + xo), make_float4(r, g, b, OUT_ALPHA ? alpha0[k] : luminance(r, g, b)));
         }
         have = have_next;
@@ -1420,6 +1539,21 @@ hipError_t launch_atrous(const SvgfLaunch& L, int variant, uint32_t step, const 
         return launch_lds_step<kInClassic, true>(a, step, L.device, L.num_cus > 0 ? L.num_cus : 256, s);
     dim3 grid((a.Wd + 63) / 64, (a.row1 - a.row0 + 3) / 4);
     hipLaunchKernelGGL(svgf_atrous_direct_kernel, grid, dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_atrous_remodulate(const SvgfLaunch& L, int variant, uint32_t step, const float4* src, float4* dst, const uint16_t* variance,
+                                    const float4* geometry, const uint32_t* albedo, float4* demod_out, hipStream_t s)
+{
+    AtrousArgs a;
+    if (!atrous_args(L, step, src, dst, variance, geometry, a))
+        return hipSuccess;
+    a.albedo = albedo;
+    a.demod_out = demod_out;
+    if (atrous_lds_serves(L, variant, step))
+        return launch_lds_step<kInClassicDemod, true>(a, step, L.device, L.num_cus > 0 ? L.num_cus : 256, s);
+    dim3 grid((a.Wd + 63) / 64, (a.row1 - a.row0 + 3) / 4);
+    hipLaunchKernelGGL(svgf_atrous_direct_demod_kernel, grid, dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -70,6 +70,10 @@ class DeferredRenderer:
         # also writes PLANE_PREV_POINT, where each pixel's surface point was one frame ago, from the previous vertices it keeps.  A caller
         # that uploads its own G-buffer uploads that plane too and calls svgf.snapshot_vertices() once per frame.
         self.vertex_motion = False
+        # Beyond the reference, independent of the three above: divide the primary surface's albedo out in front of the temporal pass and
+        # multiply it back at the last a-trous level, so that the filter smooths lighting and leaves textures sharp (option svgf_demodulate,
+        # set at init).  The albedo plane of the frame must be in place before submit_commands_svgf_denoising and stay until it returns.
+        self.albedo_demodulation = False
         self.info = None
 
     # ---- DeferredRenderer::Init (src/DeferredRenderer.cpp:26-57) ----
@@ -87,6 +91,8 @@ class DeferredRenderer:
             self.svgf.set_option("svgf_motion", 1)
         if self.vertex_motion:
             self.svgf.set_option("svgf_vertex_motion", 1)
+        if self.albedo_demodulation:
+            self.svgf.set_option("svgf_demodulate", 1)
         self.width, self.height = width, height
         return True
 

@@ -15,7 +15,7 @@ import numpy as np
 from . import _lib
 from ._lib import (PLANE_DEPTH, PLANE_MOMENTS, PLANE_NORMAL, PLANE_RADIANCE, PLANE_SCRATCH, PLANE_VARIANCE,  # noqa: F401
                    PLANE_ALBEDO, PLANE_ROUGH_METAL, PLANE_WORLDPOS, PLANE_LDR, PLANE_GEOMETRY, PLANE_HISTORY_LENGTH, PLANE_SUBMESH_ID,
-                   PLANE_PREV_POINT, SLOT_CURRENT, SLOT_HISTORY, NebError)
+                   PLANE_PREV_POINT, PLANE_DEMOD, SLOT_CURRENT, SLOT_HISTORY, NebError)
 
 # plane -> (numpy dtype, channels)
 PLANE_LAYOUT = {
@@ -24,6 +24,7 @@ PLANE_LAYOUT = {
     PLANE_ALBEDO: (np.uint32, 1), PLANE_ROUGH_METAL: (np.float16, 2), PLANE_WORLDPOS: (np.float16, 4),
     PLANE_LDR: (np.uint32, 1), PLANE_GEOMETRY: (np.float32, 4), PLANE_HISTORY_LENGTH: (np.uint8, 1),
     PLANE_SUBMESH_ID: (np.uint32, 1),
+    PLANE_DEMOD: (np.float32, 4),  # the demodulated denoised colour (option svgf_demodulate); .w unspecified
     PLANE_PREV_POINT: (np.float32, 4),  # .w holds uint32 bits: the oct16 pair of the previous normal, 0xFFFFFFFF = no per-vertex motion
 }
 
@@ -209,7 +210,8 @@ class SVGFDenoiser:
     def level_times(self):
         """Durations (us) of the kernels of the last submit_atrous_compute_wavelet chain (option svgf_profile = 1): entry 0 is
         level 0 -- fused with the temporal pass when the two calls ran as one chain.  Option svgf_profile = 2: [the first kernel,
-        all the others as one interval]."""
+        all the others as one interval].  With option svgf_demodulate one more entry follows: how many temporal calls have run the
+        seed kernel since svgf_profile was set (a count)."""
         out = (C.c_float * 32)()
         n = C.c_uint32()
         self._check(self._lib.neb_svgf_level_times(self._ctx, out, 32, C.byref(n)), "neb_svgf_level_times")
