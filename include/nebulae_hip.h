@@ -498,6 +498,30 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream);
  * transform takes a corner of the submesh's object-space box (or a vertex) to a position that is not finite.  n == 0: NEB_OK. */
 int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, const float* surfaceToWorld /* n x 16, as neb_geometry_desc */,
                              uint32_t n, neb_stream stream);
+/* Hiding and showing submeshes, the tree kept: the reference's InstanceMask -- RTCommon.h:90 sets 0xFF for every instance,
+ * and InstanceMask = 0 in the PERFORM_UPDATE build it already runs (RTAccelerationStructureBuilder.cpp:100-130) is DXR's way to make an
+ * instance absent.  geometry_indices[k] names a geometry of neb_gi_set_scene, visible[k] != 0 shows it, 0 hides it.  A hidden submesh
+ * exists for no ray of any kind (camera, bounce, shadow): frames are those of a scene whose geometry k has an empty index list, up to
+ * exact ties between coincident hits.  It stays a geometry: its slot, its pools, its matrix and its boxes remain, every update call
+ * still applies to it (and keeps it hidden), neb_gi_download_vertices still reads it, and showing it bakes its CURRENT pose under its
+ * CURRENT matrix.  What is rewritten, on the device and in place: one word per named geometry, the triangle slots of the geometries
+ * whose flag changed (a hidden one gets triangles no ray can hit, the id words kept), the boxes of the 128-byte nodes above them (a
+ * leaf bounds its visible triangles only; a leaf or node with none is an inverted box no ray enters) and the 64-byte nodes.  Topology,
+ * node numbering, leaf order and depth do not change, so showing restores the tree bit for bit.  Entries that name a geometry already in
+ * the state asked for are dropped; a call with nothing left enqueues nothing and keeps the sun table.
+ * State: neb_gi_set_scene makes everything visible; neb_gi_build_bvh keeps the flags (it builds over ALL triangles, then empties the
+ * hidden ones on the same stream before it returns, inside neb_gi_build_ms).  neb_gi_scene_box is the box of the visible geometries,
+ * {0,0,0}-{0,0,0} when nothing is visible.
+ * Streams: exactly as neb_gi_update_transforms -- enqueue only, no device synchronisation, no allocation, the arguments travel through
+ * the same ring of 4 pinned slots, ordered behind every dispatch enqueued before the call on whichever stream and ahead of every later one.
+ * Sun table: dropped whenever a flag changes, as after a scene change; "gi_sun_hold" decides when a table is built again, against the box
+ * of the visible geometries; none is built while nothing is visible.  Row-strip contexts accept the call; every context of a group makes it.
+ * Refusals, each leaving everything unchanged: NEB_ERR_STATE before a successful neb_gi_build_bvh; NEB_ERR_INVALID_ARG for a null
+ * pointer with n > 0 or an index named twice; NEB_ERR_OUT_OF_RANGE for an index >= n_geoms.  n == 0: NEB_OK. */
+int neb_gi_set_visibility(neb_ctx* ctx, const uint32_t* geometry_indices, const uint8_t* visible /* n, 0 = hidden */, uint32_t n, neb_stream stream);
+/* The flags as the host holds them (1 = visible), one byte per geometry: out[0 .. min(capacity, n_geoms)); *n_out = n_geoms (either may
+ * be asked for alone: capacity == 0 or n_out == NULL).  NEB_ERR_STATE without a scene.  Never waits. */
+int neb_gi_get_visibility(const neb_ctx* ctx, uint8_t* out, uint32_t capacity, uint32_t* n_out);
 /* Deforming submeshes: new object-space vertices for ranges of n submeshes, the tree kept.  NO reference counterpart:
  * the reference builds its BLASes without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79), so a swaying curtain, a skinned figure or
  * a morph target would mean new BLASes there; here it is the refit of neb_gi_update_transforms with another way in.

@@ -163,6 +163,16 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_update_transforms(m_svgf.Context(), geometryIndices, surfaceToWorld, n, commandList), "neb_gi_update_transforms");
         }
+        // InstanceMask = 0 / 0xFF in that same update (RTCommon.h:90): submeshes hidden from every ray or shown again, the tree kept
+        void SetVisibility(const uint32_t* geometryIndices, const uint8_t* visible, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_set_visibility(m_svgf.Context(), geometryIndices, visible, n, commandList), "neb_gi_set_visibility");
+        }
+        // one byte per geometry, 1 = visible; *nOut = the geometry count
+        void GetVisibility(uint8_t* out, uint32_t capacity, uint32_t* nOut) const
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_get_visibility(m_svgf.Context(), out, capacity, nOut), "neb_gi_get_visibility");
+        }
         // No reference counterpart (its BLASes are built without ALLOW_UPDATE, RTAccelerationStructureBuilder.cpp:79): new object-space
         // vertices for ranges of submeshes -- a swaying drape, a skinned figure --, the tree refitted in place
         void UpdateVertices(const neb_vertex_update* updates, uint32_t n, neb_stream commandList)

@@ -134,6 +134,8 @@ def _gi_sigs():
                                        C.POINTER(S.TextureDesc), C.c_uint32]),
         "neb_gi_build_bvh": (C.c_int, [C.c_void_p, C.c_void_p]),
         "neb_gi_update_transforms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
+        "neb_gi_set_visibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_uint32, C.c_void_p]),
+        "neb_gi_get_visibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
         "neb_gi_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_update_vertices_device": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_set_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinDesc), C.c_uint32, C.c_void_p]),

@@ -1096,7 +1096,7 @@ __global__ void collapse_emit_kernel(CollapseArgs a)
     nd.hiy = make_float4(hi[1][0], hi[1][1], hi[1][2], hi[1][3]);
     nd.hiz = make_float4(hi[2][0], hi[2][1], hi[2][2], hi[2][3]);
     nd.child = make_int4(ch[0], ch[1], ch[2], ch[3]);
-    nd.pad = make_int4(0, 0, 0, 0);
+    nd.pad = make_int4((c[0] >= 0 ? 1 : 0) | (c[1] >= 0 ? 2 : 0) | (c[2] >= 0 ? 4 : 0) | (c[3] >= 0 ? 8 : 0), 0, 0, 0); // the used slots, for the refit
     a.wide[e] = nd;
     if (k == a.level_count - 1)
         a.level_state[0] = a.inner_scan[k] + a.inner_count[k];
@@ -1132,8 +1132,9 @@ __global__ void quantise_nodes_kernel(const Bvh4Node* __restrict__ nodes, uint32
                 mn = fminf(mn, lo[ax][q]);
                 mx = fmaxf(mx, hi[ax][q]);
             }
-        if (!(mn <= mx))
-            mn = mx = 0.0f; // (a node without children does not occur; keep the record finite)
+        const bool childless = !(mn <= mx); // (never from the build; after a refit, a node all of whose geometries are hidden: neb_gi_set_visibility)
+        if (childless)
+            mn = mx = 0.0f; // keep the record finite
         {
             const float pad = fmaxf(fmaxf(fabsf(mn), fabsf(mx)), mx - mn) * 0x1p-20f;
             mn -= pad;
@@ -1145,6 +1146,12 @@ __global__ void quantise_nodes_kernel(const Bvh4Node* __restrict__ nodes, uint32
         float sc = fmaxf((mx - mn) / 255.0f * (1.0f + 0x1p-21f), 1e-30f);
         for (int guard = 0; guard < 8 && fmaf(255.0f, sc, mn) < mx; ++guard)
             sc *= 1.0f + 0x1p-20f;
+        // Every slot of a childless node is the inverted box 255 / 0, and the node may be the root, which every ray visits: its planes have to
+        // stay apart in the walk's folded arithmetic, fmaf(q, scale inv, origin inv - o inv).  At the scale of 1e-30 the step 255 scale inv is
+        // rounded away beside o inv, entry and exit plane coincide on every axis, and a ray through the origin enters all four slots.  At
+        // 2^100 the entry plane lies 3e32 / |d| beyond the exit plane (finite: 255 * 2^100 < FLT_MAX; an infinite product is still beyond).
+        if (childless)
+            sc = 0x1p100f;
         org[ax] = mn;
         scl[ax] = sc;
         qlo[ax] = qhi[ax] = 0u;
@@ -1224,6 +1231,7 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
     GiState* g = new GiState();
     g->h_geoms.resize(n_geoms);
     g->h_seen.assign(n_geoms, 0u);
+    g->h_visible.assign(n_geoms, 1); // (a new scene: everything visible)
     g->n_geoms = n_geoms;
     std::vector<DevGeom> dgeoms(n_geoms);
     std::vector<DevMat> dmats(n_mats);
@@ -1486,13 +1494,17 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
         const float* d_xf = nullptr;
         void* stamps = nullptr;
         void* stage = nullptr;
-        if ((e = upload(g, xf, &d_xf)) != hipSuccess || (e = hipMalloc(&stamps, (size_t)n_geoms * 4)) != hipSuccess) {
+        const std::vector<uint32_t> shown(n_geoms, 1u);
+        const uint32_t* d_shown = nullptr;
+        if ((e = upload(g, xf, &d_xf)) != hipSuccess || (e = upload(g, shown, &d_shown)) != hipSuccess ||
+            (e = hipMalloc(&stamps, (size_t)n_geoms * 4)) != hipSuccess) {
             gi_destroy(g);
             return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_scene: transform tables", e);
         }
         g->allocs.push_back(stamps);
         g->d_xf = const_cast<float*>(d_xf);
         g->d_geom_epoch = (uint32_t*)stamps;
+        g->d_visible = const_cast<uint32_t*>(d_shown);
         if ((e = hipMemset(stamps, 0, (size_t)n_geoms * 4)) != hipSuccess ||
             (e = hipHostMalloc(&stage, (size_t)GiState::kStageSlots * n_geoms * sizeof(GiState::StageEntry), hipHostMallocDefault)) != hipSuccess) {
             gi_destroy(g);
@@ -1836,10 +1848,15 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     BUILD_HIP(hipMemcpyAsync(d_tris12, have_pieces ? h_refs.data() : g->h_tris.data(), (size_t)n * 48, hipMemcpyHostToDevice, stream));
     if (have_pieces)
         BUILD_HIP(hipMemcpyAsync(d_boxes, h_boxes.data(), (size_t)n * 32, hipMemcpyHostToDevice, stream));
-    const float3 smin = make_float3(g->scene_min[0], g->scene_min[1], g->scene_min[2]);
+    // (with hidden geometries g->scene_min / max is the box of the visible ones: the build sorts by the box of ALL, topology does not depend on the flags)
+    float full_min[3], full_max[3];
+    memcpy(full_min, g->scene_min, 12), memcpy(full_max, g->scene_max, 12);
+    if (g->n_hidden)
+        gi_fold_scene_box(g, false, full_min, full_max);
+    const float3 smin = make_float3(full_min[0], full_min[1], full_min[2]);
     // (per-axis normalisation: cubic cells -- all axes scaled by the longest extent -- traversed 12 % slower on the bench scene)
-    const float3 sinv = make_float3(1.0f / fmaxf(g->scene_max[0] - g->scene_min[0], 1e-20f), 1.0f / fmaxf(g->scene_max[1] - g->scene_min[1], 1e-20f),
-                                    1.0f / fmaxf(g->scene_max[2] - g->scene_min[2], 1e-20f));
+    const float3 sinv = make_float3(1.0f / fmaxf(full_max[0] - full_min[0], 1e-20f), 1.0f / fmaxf(full_max[1] - full_min[1], 1e-20f),
+                                    1.0f / fmaxf(full_max[2] - full_min[2], 1e-20f));
     const uint32_t nb = (n + 255) / 256;
     uint32_t index_bits = 1;
     while (index_bits < 32 && (1ull << index_bits) < (unsigned long long)n)
@@ -1862,8 +1879,8 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
         float minus_one;
         const int m1 = -1;
         memcpy(&minus_one, &m1, 4);
-        const float4 root_lo = make_float4(g->scene_min[0], g->scene_min[1], g->scene_min[2], minus_one);
-        const float4 root_hi = make_float4(g->scene_max[0], g->scene_max[1], g->scene_max[2], minus_one);
+        const float4 root_lo = make_float4(full_min[0], full_min[1], full_min[2], minus_one);
+        const float4 root_hi = make_float4(full_max[0], full_max[1], full_max[2], minus_one);
         const uint32_t h_state[2] = {1u, n + 1u};
         BUILD_HIP(hipMemcpyAsync(d_segs[0], &root_seg, sizeof(root_seg), hipMemcpyHostToDevice, stream));
         BUILD_HIP(hipMemcpyAsync(N.lo + root_node, &root_lo, 16, hipMemcpyHostToDevice, stream));
@@ -2032,6 +2049,13 @@ int neb_gi_build_bvh(neb_ctx* ctx, neb_stream stream_)
     g->view.root = root_code;
     g->n_nodes = n_wide;
     g->bvh_depth = (uint32_t)max_depth;
+    if (g->n_hidden) { // the hidden geometries leave the fresh tree before the build is reported done -- inside build_ms
+        hipError_t ev = gi_visibility_after_build(g, stream);
+        if (ev == hipSuccess)
+            ev = hipStreamSynchronize(stream);
+        if (ev != hipSuccess)
+            return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_build_bvh: hidden geometries", ev);
+    }
     g->build_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t_build0).count();
     g->sun_table_state = 0; // fresh shading records carry no sun-visibility flags yet
     g->sun_table_stale = false;

@@ -75,7 +75,7 @@ struct Bvh4Node {
     float4 lox, loy, loz; //  0, 16, 32
     int4 child;           // 48
     float4 hix, hiy, hiz; // 64, 80, 96
-    int4 pad;
+    int4 pad;             // .x: the slots the build used, bit q = slot q (refit_level_kernel tells an emptied slot from an unused one by it); no ray reads it
 };
 static_assert(sizeof(Bvh4Node) == 128 && offsetof(Bvh4Node, hix) == offsetof(Bvh4Node, lox) + 64, "node layout");
 // The same tree in 64 bytes per node, for the rays that only ask "is anything in the way" (any-hit: sun visibility).
@@ -375,12 +375,24 @@ struct GiState {
     int n_reader_streams = 0;
     bool reader_overflow = false;
     uint32_t n_geoms = 0;
+    // ---- hidden submeshes: neb_gi_set_visibility (gi_refit.hip) ----
+    // One word per geometry on the device (1 = visible) that rebake_kernel and refit_level_kernel read, and its host copy.  A hidden
+    // geometry keeps its pools, its matrix and its boxes up to date; its triangle slots hold triangles no ray can hit, its leaves
+    // inverted boxes.  neb_gi_set_scene makes everything visible, neb_gi_build_bvh keeps the flags.
+    std::vector<uint8_t> h_visible;
+    uint32_t* d_visible = nullptr;
+    uint32_t n_hidden = 0;        // geometries with h_visible == 0
+    bool nothing_visible = false; // no visible geometry has a triangle: the scene box is the zero box, no sun table is built
 };
 hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_t stream);
 hipError_t gi_sun_table_order(GiState* g, hipStream_t stream);
 hipError_t mark_rewrite(GiState* g, hipStream_t stream);
 hipError_t gi_quantise_nodes(const Bvh4Node* nodes, uint32_t n, Bvh4NodeQ* out, hipStream_t stream);
 void gi_rebake_host(GiState* g);
+// The end of neb_gi_build_bvh with hidden geometries: their slots emptied and the tree refitted on `stream` (enqueue only).
+hipError_t gi_visibility_after_build(GiState* g, hipStream_t stream);
+// the scene box over the visible geometries (over all of them: the box the build sorts by)
+void gi_fold_scene_box(const GiState* g, bool visible_only, float lo[3], float hi[3]);
 // Applies the result records of finished updates in call order: boxes of the listed geometries, then the scene box.  block = false
 // stops at the first record whose event has not passed; block = true waits for every record of a call <= upto.
 hipError_t gi_harvest_results(GiState* g, bool block, uint32_t upto = 0xffffffffu);

@@ -23,6 +23,11 @@
 // and the rest pose of a geometry stay on the device, a call hands over one weight per target -- compacted on the host to the targets
 // that act -- and, for a skinned geometry, optionally its palette: morph_check_kernel and morph_scatter_kernel blend the rest pose and,
 // with a palette, put the blend through the skin's own arithmetic in the place of its bind pose (glTF's order: morph, then skin).
+//
+// neb_gi_set_visibility is the reference's InstanceMask = 0 in the TLAS update it already runs (RTCommon.h:90 sets 0xFF,
+// RTAccelerationStructureBuilder.cpp:100-130 is the PERFORM_UPDATE build): a word per geometry says whether its triangles exist for the rays.
+// visibility_apply_kernel stands where refit_apply_kernel stands; rebake_kernel gives the slots of a hidden geometry triangles no ray can hit,
+// refit_level_kernel leaves them out of the boxes, and every other update call goes through the same two kernels: hidden stays hidden.
 #include <algorithm>
 
 #include "gi_device.h"
@@ -55,6 +60,27 @@ __global__ void refit_apply_kernel(const GiState::StageEntry* __restrict__ stage
     geom_epoch[gi] = epoch;
 }
 
+// lane k: entry k of neb_gi_set_visibility (StageEntry::pad[0] = the new flag) -> the geometry's visibility word, and its stamp
+__global__ void visibility_apply_kernel(const GiState::StageEntry* __restrict__ stage, uint32_t n, uint32_t n_geoms, uint32_t epoch,
+                                        uint32_t* __restrict__ visible, uint32_t* __restrict__ geom_epoch)
+{
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n)
+        return;
+    const uint32_t gi = stage[k].geom;
+    if (gi >= n_geoms)
+        return;
+    visible[gi] = stage[k].pad[0] ? 1u : 0u;
+    geom_epoch[gi] = epoch;
+}
+// lane gi: a hidden geometry is stamped (the end of a build: the fresh tree holds every triangle, the hidden ones leave it again)
+__global__ void visibility_stamp_kernel(uint32_t n_geoms, uint32_t epoch, const uint32_t* __restrict__ visible, uint32_t* __restrict__ geom_epoch)
+{
+    const uint32_t gi = blockIdx.x * blockDim.x + threadIdx.x;
+    if (gi < n_geoms && !visible[gi])
+        geom_epoch[gi] = epoch;
+}
+
 // world = (p, 1) * M: gi_bake_point (gi_internal.h) with every rounding spelled out, same bits as the host.  HIP's __fmul_rn /
 // __fadd_rn are plain operators, and with the compiler's default contraction mode the back end fuses a product into the sum that
 // takes it whatever a pragma says: each product passes through an empty asm statement, which the optimiser cannot see through
@@ -75,10 +101,12 @@ __device__ __forceinline__ float3 bake_point(const float* __restrict__ m, const 
     return w;
 }
 
-// one lane per leaf-order triangle slot: a slot of a moved geometry gets its triangle baked again, {geom, prim} stay
+// one lane per leaf-order triangle slot: a slot of a moved geometry gets its triangle baked again, {geom, prim} stay.
+// A stamped geometry that is hidden (neb_gi_set_visibility) gets the triangle no ray can hit instead: v0 = e1 = e2 = +0, det == 0 in
+// intersect_tri_regs whatever the ray, every word finite; the id words keep their bits, so that showing it finds {geom, prim} again.
 __global__ void rebake_kernel(float4* __restrict__ tris, uint32_t n_slots, uint32_t n_geoms, uint32_t epoch, const uint32_t* __restrict__ geom_epoch,
                               const DevGeom* __restrict__ geoms, const uint32_t* __restrict__ indices, const float* __restrict__ pos,
-                              const float* __restrict__ xf)
+                              const float* __restrict__ xf, const uint32_t* __restrict__ visible)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_slots)
@@ -87,6 +115,12 @@ __global__ void rebake_kernel(float4* __restrict__ tris, uint32_t n_slots, uint3
     const uint32_t gi = __float_as_uint(ids.y), prim = __float_as_uint(ids.z);
     if (gi >= n_geoms || geom_epoch[gi] != epoch)
         return;
+    if (!visible[gi]) {
+        tris[3 * (size_t)i] = make_float4(0.f, 0.f, 0.f, 0.f);
+        tris[3 * (size_t)i + 1] = make_float4(0.f, 0.f, 0.f, 0.f);
+        tris[3 * (size_t)i + 2] = make_float4(0.f, ids.y, ids.z, ids.w);
+        return;
+    }
     const uint32_t first = geoms[gi].firstIndex + 3u * prim, vb = geoms[gi].vertexBase;
     const float* m = xf + 16 * (size_t)gi;
     const float3 w0 = bake_point(m, pos + 3 * (size_t)(vb + indices[first]));
@@ -601,17 +635,21 @@ __global__ __launch_bounds__(256) void geom_box_kernel(const uint32_t* __restric
 // its triangles -- the whole triangle also where the slot holds a clipped reference of the splitting pass: conservative.  An inner
 // child below which something changed takes the exact min / max of that node's four boxes (its level was refitted by the launch
 // before: unused slots are inverted boxes and drop out of min / max by themselves).  Everything else keeps its bits.
+// Hidden geometries (neb_gi_set_visibility): a leaf takes the bounds of its VISIBLE triangles, and the inverted box when it has none; an
+// inner child all of whose slots are inverted becomes inverted itself (min / max of four inverted boxes).  Such a slot has to come
+// back when its geometry is shown, so the slots nothing ever lived in are told by the mask the build wrote (Bvh4Node::pad.x), not by
+// their box -- and not by the child word: ~0 is the unused slot and also the leaf {slot 0, one triangle}.
 __global__ void refit_level_kernel(Bvh4Node* __restrict__ nodes, uint32_t first, uint32_t count, uint32_t n_nodes, const float4* __restrict__ tris,
                                    uint32_t n_slots, uint32_t n_geoms, uint32_t epoch, const uint32_t* __restrict__ geom_epoch,
-                                   uint32_t* __restrict__ node_epoch)
+                                   uint32_t* __restrict__ node_epoch, const uint32_t* __restrict__ visible)
 {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 4u * count)
         return;
     const uint32_t i = first + (t >> 2), q = t & 3u;
     float* nf = reinterpret_cast<float*>(nodes + i);
-    if (!(nf[q] <= nf[16 + q]))
-        return; // unused slot (inverted box)
+    if (!(((uint32_t)nodes[i].pad.x >> q) & 1u))
+        return; // a slot the build left unused
     const int c = reinterpret_cast<const int*>(nodes + i)[12 + q];
     float lo[3], hi[3];
     if (c < 0) {
@@ -629,6 +667,9 @@ __global__ void refit_level_kernel(Bvh4Node* __restrict__ nodes, uint32_t first,
             lo[ax] = INFINITY, hi[ax] = -INFINITY;
         for (uint32_t k = 0; k < cnt; ++k) {
             const float4 a = tris[3 * (size_t)(slot + k)], b = tris[3 * (size_t)(slot + k) + 1], d = tris[3 * (size_t)(slot + k) + 2];
+            const uint32_t gi = __float_as_uint(d.y);
+            if (gi < n_geoms && !visible[gi])
+                continue; // (a hidden triangle bounds nothing)
             // (the vertices as the builder's reference_box and the triangle test form them: v0, v0 + e1, v0 + e2)
             const float v[3][3] = {{a.x, a.y, a.z}, {__fadd_rn(a.x, a.w), __fadd_rn(a.y, b.x), __fadd_rn(a.z, b.y)},
                                    {__fadd_rn(a.x, b.z), __fadd_rn(a.y, b.w), __fadd_rn(a.z, d.x)}};
@@ -651,17 +692,45 @@ __global__ void refit_level_kernel(Bvh4Node* __restrict__ nodes, uint32_t first,
 
 // ---- what the two kinds of update share on the host ----
 // the scene box: the union of the geometries' exact boxes, as neb_gi_set_scene folds it
-static void refit_scene_box(GiState* g)
+// -- of the VISIBLE ones (neb_gi_set_visibility): the box of a scene built without the hidden ones.  Nothing visible: the zero box of
+// an empty scene, and no sun table is built (GiState::nothing_visible).
+void gi_fold_scene_box(const GiState* g, bool visible_only, float lo[3], float hi[3])
 {
     float smin[3] = {3.4e38f, 3.4e38f, 3.4e38f}, smax[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-    for (const GiState::HostGeom& hg : g->h_geoms)
-        if (hg.n_tris)
-            for (int q = 0; q < 3; ++q) {
-                smin[q] = fminf(smin[q], hg.world_lo[q]);
-                smax[q] = fmaxf(smax[q], hg.world_hi[q]);
-            }
-    memcpy(g->scene_min, smin, sizeof(smin));
-    memcpy(g->scene_max, smax, sizeof(smax));
+    bool any = false;
+    for (size_t gi = 0; gi < g->h_geoms.size(); ++gi) {
+        const GiState::HostGeom& hg = g->h_geoms[gi];
+        if (!hg.n_tris || (visible_only && !g->h_visible[gi]))
+            continue;
+        any = true;
+        for (int q = 0; q < 3; ++q) {
+            smin[q] = fminf(smin[q], hg.world_lo[q]);
+            smax[q] = fmaxf(smax[q], hg.world_hi[q]);
+        }
+    }
+    for (int q = 0; q < 3; ++q)
+        lo[q] = any ? smin[q] : 0.f, hi[q] = any ? smax[q] : 0.f;
+}
+static void refit_scene_box(GiState* g)
+{
+    if (g->n_hidden == 0) { // (the fold of every release before hidden geometries existed, its bits kept)
+        float smin[3] = {3.4e38f, 3.4e38f, 3.4e38f}, smax[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+        for (const GiState::HostGeom& hg : g->h_geoms)
+            if (hg.n_tris)
+                for (int q = 0; q < 3; ++q) {
+                    smin[q] = fminf(smin[q], hg.world_lo[q]);
+                    smax[q] = fmaxf(smax[q], hg.world_hi[q]);
+                }
+        memcpy(g->scene_min, smin, sizeof(smin));
+        memcpy(g->scene_max, smax, sizeof(smax));
+        g->nothing_visible = false;
+        return;
+    }
+    gi_fold_scene_box(g, true, g->scene_min, g->scene_max);
+    bool any = false;
+    for (size_t gi = 0; gi < g->h_geoms.size(); ++gi)
+        any = any || (g->h_geoms[gi].n_tris && g->h_visible[gi]);
+    g->nothing_visible = !any;
 }
 // The sun table as after a scene change: the flags in the records are those of the old positions and are ignored from here on (state 2); the hold
 // policy of gi_sun_table_update decides when the next table is built -- and looks at the new scene box when it does.
@@ -683,7 +752,8 @@ static hipError_t refit_enqueue_levels(GiState* g, uint32_t call, hipStream_t st
         const uint32_t first = g->level_first[lv - 1], count = g->level_first[lv] - first;
         if (count)
             hipLaunchKernelGGL(refit_level_kernel, dim3((4u * count + 255) / 256), dim3(256), 0, stream, const_cast<Bvh4Node*>(g->view.nodes), first, count,
-                               g->n_nodes, g->view.tris, n_slots, g->n_geoms, call, (const uint32_t*)g->d_geom_epoch, g->d_node_epoch);
+                               g->n_nodes, g->view.tris, n_slots, g->n_geoms, call, (const uint32_t*)g->d_geom_epoch, g->d_node_epoch,
+                               (const uint32_t*)g->d_visible);
     }
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
@@ -728,7 +798,8 @@ static hipError_t refit_enqueue_rewrite(GiState* g, int slot, uint32_t call, boo
 {
     const uint32_t n_slots = g->view.n_tris;
     hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
-                       (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf);
+                       (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf,
+                       (const uint32_t*)g->d_visible);
     if (repack)
         hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
                            reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
@@ -1014,11 +1085,113 @@ int gi_roll_vertices(neb_ctx* ctx, hipStream_t stream)
     return NEB_OK;
 }
 
+// The fresh tree of neb_gi_build_bvh holds every triangle at its real position -- its topology does not depend on the flags, so showing
+// never needs a rebuild --; the hidden geometries leave it here: stamped, their slots emptied, the levels refitted, the 64-byte nodes
+// quantised again.  One more update in the count of epochs; no argument slot (the flags are on the device already).
+hipError_t gi_visibility_after_build(GiState* g, hipStream_t stream)
+{
+    if (!g->n_hidden || !g->n_geoms || !g->view.n_tris)
+        return hipSuccess;
+    const uint32_t call = ++g->epoch;
+    hipLaunchKernelGGL(visibility_stamp_kernel, dim3((g->n_geoms + 63) / 64), dim3(64), 0, stream, g->n_geoms, call, (const uint32_t*)g->d_visible,
+                       g->d_geom_epoch);
+    const uint32_t n_slots = g->view.n_tris;
+    hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
+                       (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf,
+                       (const uint32_t*)g->d_visible);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    return refit_enqueue_levels(g, call, stream);
+}
+
 } // namespace neb
 
 using namespace neb;
 
 extern "C" {
+
+int neb_gi_set_visibility(neb_ctx* ctx, const uint32_t* geometry_indices, const uint8_t* visible, uint32_t n, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_set_visibility: no built scene (neb_gi_set_scene + neb_gi_build_bvh first)");
+    if (n == 0)
+        return NEB_OK;
+    if (!geometry_indices || !visible)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_visibility: null pointer");
+    GI_HIP(ctx, gi_harvest_results(g, false));
+    // ---- everything that can refuse the call comes before anything changes ----
+    const uint32_t call = g->epoch + 1u;
+    const uint32_t stamp = ++g->seen_stamp; // (one per call, accepted or not: h_seen needs no clearing)
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t gi = geometry_indices[k];
+        if (gi >= g->n_geoms)
+            return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_set_visibility: geometry index out of range");
+        if (g->h_seen[gi] == stamp)
+            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_visibility: a geometry is named twice");
+        g->h_seen[gi] = stamp;
+    }
+    uint32_t n_changed = 0; // (n <= n_geoms from here on: every index is in range and none is named twice)
+    for (uint32_t k = 0; k < n; ++k)
+        n_changed += (g->h_visible[geometry_indices[k]] != 0) != (visible[k] != 0) ? 1u : 0u;
+    if (n_changed == 0)
+        return NEB_OK; // every geometry is in the state asked for: nothing is enqueued, the sun table stays
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    // ---- the argument slot: pinned host memory the first kernel reads ----
+    int slot = 0;
+    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
+    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+        return rc;
+    // ---- commit the host side ----
+    g->epoch = call;
+    GiState::StageEntry* st = g->h_stage + (size_t)slot * g->n_geoms;
+    uint32_t ns = 0;
+    bool any_tris = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t gi = geometry_indices[k];
+        const uint8_t v = visible[k] ? 1 : 0;
+        if (g->h_visible[gi] == v)
+            continue;
+        g->h_visible[gi] = v;
+        g->n_hidden += v ? (uint32_t)-1 : 1u;
+        memset(&st[ns], 0, sizeof(st[ns]));
+        st[ns].geom = gi;
+        st[ns].pad[0] = v;
+        ++ns;
+        any_tris = any_tris || g->h_geoms[gi].n_tris != 0;
+    }
+    refit_scene_box(g);
+    refit_drop_sun_table(g);
+    // ---- enqueue ----
+    hipLaunchKernelGGL(visibility_apply_kernel, dim3((ns + 63) / 64), dim3(64), 0, stream, (const GiState::StageEntry*)st, ns, g->n_geoms, call, g->d_visible,
+                       g->d_geom_epoch);
+    GI_HIP(ctx, hipGetLastError());
+    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
+    g->stage_used[slot] = true;
+    if (any_tris && g->view.n_tris)
+        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, false, 0u, stream));
+    GI_HIP(ctx, mark_rewrite(g, stream));
+    return NEB_OK;
+}
+
+int neb_gi_get_visibility(const neb_ctx* ctx, uint8_t* out, uint32_t capacity, uint32_t* n_out)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    const GiState* g = ctx->gi;
+    if (!g)
+        return NEB_ERR_STATE;
+    if (n_out)
+        *n_out = g->n_geoms;
+    if (capacity && !out)
+        return NEB_ERR_INVALID_ARG;
+    for (uint32_t gi = 0; gi < g->n_geoms && gi < capacity; ++gi)
+        out[gi] = g->h_visible[gi];
+    return NEB_OK;
+}
 
 int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, const float* surfaceToWorld, uint32_t n, neb_stream stream_)
 {

@@ -517,6 +517,8 @@ hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_
 {
     if (!g->built || g->view.n_tris == 0 || !g->view.shade)
         return hipSuccess;
+    if (g->nothing_visible) // (neb_gi_set_visibility: every triangle is hidden -- no ray meets a record, a dropped table stays dropped)
+        return hipSuccess;
     const float key[4] = {c.sunLightDirection[0], c.sunLightDirection[1], c.sunLightDirection[2], c.sunTanHalfAngle};
     const bool want = g->sun_table;
     // The flags live in the shading records every dispatch reads.  With two dispatches in flight ("gi_defer_resolve" = 2) the other one may still

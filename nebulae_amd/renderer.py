@@ -137,6 +137,35 @@ class DeferredRenderer:
         for k, gi in enumerate(idx):
             self._scene.geometries[int(gi)]["M"] = mats[k].copy()
 
+    # ---- InstanceMask = 0 / 0xFF in that same update (RTCommon.h:90) ----
+    def set_visible(self, indices, visible, stream=None):
+        """Hide or show submeshes in place: geometry indices[k] is shown where visible[k] is true and hidden -- absent for every ray --
+        where it is false; `visible` is one bool for all or a sequence (neb_gi_set_visibility).  The tree is kept, so showing costs what
+        hiding costs.  The renderer's scene object is not changed: a hidden submesh keeps its vertices, matrix and index list."""
+        if self._scene is None:
+            raise NebError("set_visible: no scene (init_pathtracer_scene first)")
+        idx = np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))
+        if idx.size and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise NebError("set_visible: geometry index out of range")
+        idx = idx.astype(np.uint32)
+        vis = np.asarray(visible)
+        vis = np.full(idx.size, bool(vis), np.uint8) if vis.ndim == 0 else np.ascontiguousarray(vis.reshape(-1).astype(bool).astype(np.uint8))
+        if vis.size != idx.size:
+            raise NebError(f"set_visible: {idx.size} indices but {vis.size} flags")
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        rc = self._lib.neb_gi_set_visibility(self._ctx, idx.ctypes.data_as(C.POINTER(C.c_uint32)), vis.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                             idx.size, st)
+        self._check(rc, "neb_gi_set_visibility")
+
+    def visibility(self):
+        """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
+        n = C.c_uint32(0)
+        self._check(self._lib.neb_gi_get_visibility(self._ctx, None, 0, C.byref(n)), "neb_gi_get_visibility")
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            self._check(self._lib.neb_gi_get_visibility(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, None), "neb_gi_get_visibility")
+        return out.astype(bool)
+
     # ---- no reference counterpart: its BLASes are built without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79) ----
     def update_vertices(self, index, positions, normals=None, tangents=None, first_vertex=0, stream=None):
         """Deform a submesh: vertices [first_vertex, first_vertex + len(positions)) of geometry `index` get new object-space positions
