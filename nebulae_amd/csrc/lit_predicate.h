@@ -277,6 +277,47 @@ NEB_LIT_HD bool may_occlude(const Frame& F, const RV& R, const Tri& O)
     return false;
 }
 
+// ---- which lit bits a scene update leaves sound (checked on the CPU: tools/lit_keep_proto.cpp, tests/test_sun_keep_cpu.py; no kernel
+// uses it yet -- every update call still drops the table) ----
+// Everything an update can have put in a receiver's way lies inside the new world boxes of the updated submeshes.  A box in sun
+// coordinates: the intervals of a, b and h over its eight corners.
+struct SunBox {
+    double a[2], b[2], h[2];
+};
+// lo / hi: a world-space box (floats: the triangles the traverser tests are (v0, v0 + e1, v0 + e2) with rounded edges, `pad` -- an ulp of
+// the scene's largest coordinate -- covers what that can add to the box of the baked vertices)
+NEB_LIT_HD void make_sun_box(const Frame& F, const float lo[3], const float hi[3], double pad, SunBox& B)
+{
+    B.a[0] = B.b[0] = B.h[0] = 1e300;
+    B.a[1] = B.b[1] = B.h[1] = -1e300;
+    for (int corner = 0; corner < 8; ++corner) {
+        const double p[3] = {(corner & 1) ? (double)hi[0] + pad : (double)lo[0] - pad, (corner & 2) ? (double)hi[1] + pad : (double)lo[1] - pad,
+                             (corner & 4) ? (double)hi[2] + pad : (double)lo[2] - pad};
+        double a, b, h;
+        to_sun(F, p, a, b, h);
+        B.a[0] = a < B.a[0] ? a : B.a[0], B.a[1] = a > B.a[1] ? a : B.a[1];
+        B.b[0] = b < B.b[0] ? b : B.b[0], B.b[1] = b > B.b[1] ? b : B.b[1];
+        B.h[0] = h < B.h[0] ? h : B.h[0], B.h[1] = h > B.h[1] ? h : B.h[1];
+    }
+}
+// Can a shadow ray from receiver R meet anything inside B?  false = certainly not: may_occlude's own first two rejections (nothing of the
+// box is above the lowest origin; the box lies outside the origins' lateral box pushed out by the drift a ray can have when it has climbed
+// to the box's top) hold for the box and therefore for every triangle in it.  An invalid receiver has no lit bit to keep: "may".
+NEB_LIT_HD bool box_may_shadow(const Frame& F, const Receiver& R, const SunBox& B)
+{
+    if (!R.valid)
+        return true;
+    const double s = B.h[1] - R.h_min + F.margin; // the most a ray can have climbed inside the box
+    if (s <= 0.0)
+        return false;
+    const double rho = s * F.tau + F.margin;
+    if (B.a[1] < R.bb_a[0] - rho || B.a[0] > R.bb_a[1] + rho)
+        return false;
+    if (B.b[1] < R.bb_b[0] - rho || B.b[0] > R.bb_b[1] + rho)
+        return false;
+    return true;
+}
+
 // Which of kCoverSamples fixed sample origins of R (a triangular grid of barycentrics, offset to the middle of the origin box)
 // a ray towards the centre of the sun disk would leave through O: bit k of the mask.  Only RANKS occluder hints
 // (gi_sun_table.hip): a hint is tried with the traverser's own triangle test, so a poor estimate costs speed, never correctness.
