@@ -522,6 +522,45 @@ int neb_gi_set_visibility(neb_ctx* ctx, const uint32_t* geometry_indices, const 
 /* The flags as the host holds them (1 = visible), one byte per geometry: out[0 .. min(capacity, n_geoms)); *n_out = n_geoms (either may
  * be asked for alone: capacity == 0 or n_out == NULL).  NEB_ERR_STATE without a scene.  Never waits. */
 int neb_gi_get_visibility(const neb_ctx* ctx, uint8_t* out, uint32_t capacity, uint32_t* n_out);
+/* What a submesh looks like, updated in place: the counterpart of the reference uploading its material table and its
+ * textures again without touching the TLAS.  None of the four calls below touches triangles, nodes or shading records: the tree and the
+ * SUN TABLE are kept.  They need a scene only (before or after neb_gi_build_bvh; a later build keeps what they set, neb_gi_set_scene
+ * starts over), results are those of a fresh scene set from the edited tables, bit for bit.
+ * Streams: exactly as neb_gi_update_transforms -- enqueue only, no device synchronisation, ordered behind every dispatch enqueued before
+ * the call on whichever stream and ahead of every later one; no allocation after the first call of a kind (the host-sourced texel call
+ * grows its staging to the largest call seen).  Row-strip contexts accept the calls; every context of a group makes them.
+ * Refusals, each leaving everything unchanged: NEB_ERR_STATE without a scene; NEB_ERR_INVALID_ARG for a null pointer with n > 0, an
+ * index named twice (materials and geometries; not textures), textureIndices that differ, a bad pitch, a source the device cannot
+ * read; NEB_ERR_OUT_OF_RANGE for an index past its table, a factor that is not finite, a rectangle that is empty or leaves its texture.
+ * n == 0: NEB_OK.
+ *
+ * neb_gi_update_materials: new albedo[0..2] and roughnessMetalness[0..1] for the named materials (albedo[3] is ignored, as in
+ * neb_gi_set_scene).  textureIndices must equal what the material was set with (indices outside the texture table count as -1, as there):
+ * which maps a material binds decides the layout of the tables, which is not rebuilt here.  A material given the factors it already has
+ * is dropped; a call with nothing left enqueues nothing. */
+int neb_gi_update_materials(neb_ctx* ctx, const uint32_t* material_indices, const neb_material_desc* mats, uint32_t n, neb_stream stream);
+/* The named geometries name another material; a negative index means none (the shade pass sees the fields of no material exactly as
+ * neb_gi_set_scene writes them).  Entries that change nothing are dropped. */
+int neb_gi_set_geometry_materials(neb_ctx* ctx, const uint32_t* geometry_indices, const int32_t* material_indices, uint32_t n, neb_stream stream);
+/* New texels: the rectangle [x, x + width) x [y, y + height) of texture `texture` is replaced by rows of RGBA8 at pitchBytes
+ * (a multiple of 4, >= 4 * width).  The rectangle lies inside the texture and does not wrap; the texture's size does not change.
+ * Several entries of one call may name the same texture: they apply in order.  The standalone footprint table of the texture and every
+ * material bundle it sits in are patched (each texel lives in four entries of each).
+ * neb_gi_update_textures: rgba8 is HOST memory, copied before the call returns; the rectangles of one call may total 64 MB at most
+ * (NEB_ERR_OUT_OF_RANGE beyond: the staging is pinned memory, four slots of the largest call seen).
+ * neb_gi_update_textures_device: rgba8 is memory this context's device reads at that address (as the sources of
+ * neb_gi_update_vertices_device), 4-byte aligned, read in stream order: `stream` has to be ordered behind whatever writes it, and it
+ * must stay untouched until the stream has passed the update.  No size limit. */
+typedef struct neb_texture_update {
+    uint32_t texture, x, y, width, height, pitchBytes;
+    const void* rgba8;
+} neb_texture_update;
+int neb_gi_update_textures(neb_ctx* ctx, const neb_texture_update* updates, uint32_t n, neb_stream stream);
+int neb_gi_update_textures_device(neb_ctx* ctx, const neb_texture_update* updates, uint32_t n, neb_stream stream);
+/* Diagnostics: the texture tables as the device holds them -- the standalone footprint tables (16 bytes per texel position, in texture
+ * order), then the material bundles (32 bytes per position, in material order) -- copied to host[0 .. *bytes) behind the work of `stream`;
+ * waits for the copy.  host == NULL or capacity == 0: the size alone.  NEB_ERR_INVALID_ARG when capacity is below it. */
+int neb_gi_debug_texture_tables(neb_ctx* ctx, void* host, size_t capacity, size_t* bytes, neb_stream stream);
 /* Deforming submeshes: new object-space vertices for ranges of n submeshes, the tree kept.  NO reference counterpart:
  * the reference builds its BLASes without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79), so a swaying curtain, a skinned figure or
  * a morph target would mean new BLASes there; here it is the refit of neb_gi_update_transforms with another way in.

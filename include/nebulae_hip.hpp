@@ -173,6 +173,31 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_get_visibility(m_svgf.Context(), out, capacity, nOut), "neb_gi_get_visibility");
         }
+        // The material table and the textures uploaded again, the TLAS untouched (GIProcessedScene.cpp:16-137): new factors for materials, ...
+        void UpdateMaterials(const uint32_t* materialIndices, const neb_material_desc* mats, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_update_materials(m_svgf.Context(), materialIndices, mats, n, commandList), "neb_gi_update_materials");
+        }
+        // ... another material for geometries (negative: none), ...
+        void SetGeometryMaterials(const uint32_t* geometryIndices, const int32_t* materialIndices, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_set_geometry_materials(m_svgf.Context(), geometryIndices, materialIndices, n, commandList),
+                          "neb_gi_set_geometry_materials");
+        }
+        // ... new texels for rectangles of textures, from host memory or (Device) from memory the device reads in stream order; the tree and the sun table are kept
+        void UpdateTextures(const neb_texture_update* updates, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_update_textures(m_svgf.Context(), updates, n, commandList), "neb_gi_update_textures");
+        }
+        void UpdateTexturesDevice(const neb_texture_update* updates, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_update_textures_device(m_svgf.Context(), updates, n, commandList), "neb_gi_update_textures_device");
+        }
+        // diagnostics: the standalone footprint tables, then the material bundles, as the device holds them (host == nullptr: the size alone)
+        void TextureTables(void* host, size_t capacity, size_t* bytes, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_debug_texture_tables(m_svgf.Context(), host, capacity, bytes, commandList), "neb_gi_debug_texture_tables");
+        }
         // No reference counterpart (its BLASes are built without ALLOW_UPDATE, RTAccelerationStructureBuilder.cpp:79): new object-space
         // vertices for ranges of submeshes -- a swaying drape, a skinned figure --, the tree refitted in place
         void UpdateVertices(const neb_vertex_update* updates, uint32_t n, neb_stream commandList)

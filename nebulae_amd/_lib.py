@@ -123,6 +123,12 @@ class MorphUpdate(C.Structure):
     _fields_ = [("geometry", C.c_uint32), ("weights", C.POINTER(C.c_float)), ("jointMatrices", C.POINTER(C.c_float))]
 
 
+class TextureUpdate(C.Structure):
+    """neb_texture_update"""
+    _fields_ = [("texture", C.c_uint32), ("x", C.c_uint32), ("y", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32),
+                ("pitchBytes", C.c_uint32), ("rgba8", C.c_void_p)]
+
+
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -136,6 +142,11 @@ def _gi_sigs():
         "neb_gi_update_transforms": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.c_uint32, C.c_void_p]),
         "neb_gi_set_visibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint8), C.c_uint32, C.c_void_p]),
         "neb_gi_get_visibility": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.POINTER(C.c_uint32)]),
+        "neb_gi_update_materials": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(S.MaterialDesc), C.c_uint32, C.c_void_p]),
+        "neb_gi_set_geometry_materials": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_int32), C.c_uint32, C.c_void_p]),
+        "neb_gi_update_textures": (C.c_int, [C.c_void_p, C.POINTER(TextureUpdate), C.c_uint32, C.c_void_p]),
+        "neb_gi_update_textures_device": (C.c_int, [C.c_void_p, C.POINTER(TextureUpdate), C.c_uint32, C.c_void_p]),
+        "neb_gi_debug_texture_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
         "neb_gi_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_update_vertices_device": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_set_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinDesc), C.c_uint32, C.c_void_p]),

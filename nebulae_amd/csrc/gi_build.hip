@@ -84,6 +84,8 @@ void gi_destroy(GiState* g)
             (void)hipFree(mo.d_block);
     if (g->d_skin_args)
         (void)hipFree(g->d_skin_args);
+    if (g->d_tstage)
+        (void)hipFree(g->d_tstage);
     delete g;
 }
 
@@ -1413,6 +1415,33 @@ int neb_gi_set_scene(neb_ctx* ctx, const neb_geometry_desc* geoms, uint32_t n_ge
             table_entries += (size_t)dtexs[i].w * dtexs[i].h;
         }
     g->texture_table_bytes = table_entries * 16 + bundle_entries * 32;
+    {   // what the layout just decided, for the update calls of gi_material.hip (read-only bookkeeping: nothing here reaches the device)
+        g->table_bytes = table_entries * 16, g->bundle_bytes = bundle_entries * 32;
+        g->h_mats = dmats;
+        g->h_texs = dtexs;
+        g->h_mat_seen.assign(n_mats, 0u);
+        g->h_geom_mat.resize(n_geoms);
+        for (uint32_t gi = 0; gi < n_geoms; ++gi)
+            g->h_geom_mat[gi] = dgeoms[gi].material;
+        std::vector<std::vector<GiState::TexUse>> uses(n_texs);
+        for (uint32_t i = 0; i < n_mats; ++i) {
+            const DevMat& d = dmats[i];
+            if (!d.bundle_w)
+                continue;
+            for (int k = 0; k < 3; ++k) { // (a texture that fills several roles of one material is ONE use with several role bits)
+                uint32_t roles = 0;
+                for (int q = 0; q < 3; ++q)
+                    roles |= d.tex[q] == d.tex[k] ? 1u << q : 0u;
+                if (!(roles & ((1u << k) - 1u)))
+                    uses[d.tex[k]].push_back({i, d.bundle, roles});
+            }
+        }
+        g->tex_use_first.assign(n_texs + 1u, 0u);
+        for (uint32_t t = 0; t < n_texs; ++t) {
+            g->tex_uses.insert(g->tex_uses.end(), uses[t].begin(), uses[t].end());
+            g->tex_use_first[t + 1] = (uint32_t)g->tex_uses.size();
+        }
+    }
     {
         uint32_t* d_raw = nullptr;
         uint4* d_tables = nullptr;

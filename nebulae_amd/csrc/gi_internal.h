@@ -383,7 +383,32 @@ struct GiState {
     uint32_t* d_visible = nullptr;
     uint32_t n_hidden = 0;        // geometries with h_visible == 0
     bool nothing_visible = false; // no visible geometry has a triangle: the scene box is the zero box, no sun table is built
+    // ---- materials and texels in place: neb_gi_update_materials / _set_geometry_materials / _update_textures (gi_material.hip) ----
+    // What neb_gi_set_scene decided about the tables, kept for the update calls (the raw images are gone): host copies of the DevMat rows,
+    // of DevGeom::material and of the DevTex rows (offset 0xffffffff: no standalone table), and per texture the bundles it sits in -- the
+    // uses of texture t are tex_uses[tex_use_first[t] .. tex_use_first[t + 1]).
+    struct TexUse { uint32_t material, bundle /* first entry, 32-byte units */, roles /* texpatch::kRole* */; };
+    std::vector<DevMat> h_mats;
+    std::vector<int32_t> h_geom_mat;
+    std::vector<DevTex> h_texs;
+    std::vector<TexUse> tex_uses;
+    std::vector<uint32_t> tex_use_first;
+    std::vector<uint32_t> h_mat_seen; // per material, as h_seen per geometry
+    size_t table_bytes = 0, bundle_bytes = 0; // the two parts of texture_table_bytes
+    // One staged entry of a factor update (index = material) or of a reassignment (index = geometry, material = the new one).
+    struct MatStage { uint32_t index; int32_t material; float albedo[3]; float rough, metal; uint32_t pad; };
+    // [n_mats] then [n_geoms] stamps: == epoch where the update in progress wrote the row.  Allocated by the first such call.
+    uint32_t* d_mat_epoch = nullptr;
+    // Host-sourced texel updates: the pinned slot is copied here in one hipMemcpyAsync and the patch kernels read device memory (every
+    // texel is read by four lanes, and by every use of its texture).  Allocated by the first call, grown to the largest seen.
+    void* d_tstage = nullptr;
+    size_t d_tstage_cap = 0;
 };
+// ---- what every update call does with the ring and with its streams (gi_refit.hip) ----
+hipError_t vstage_reserve(GiState* g, size_t bytes, size_t want);
+hipError_t stage_slot_acquire(GiState* g, uint32_t call, int* slot);
+bool device_readable(const neb_ctx* ctx, const void* p, size_t bytes);
+int refit_order_behind_readers(neb_ctx* ctx, GiState* g, hipStream_t stream);
 hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_t stream);
 hipError_t gi_sun_table_order(GiState* g, hipStream_t stream);
 hipError_t mark_rewrite(GiState* g, hipStream_t stream);

@@ -763,7 +763,7 @@ static hipError_t refit_enqueue_levels(GiState* g, uint32_t call, hipStream_t st
 // ---- what every update call does with the ring and with the end of its chain ----
 // The pinned vertex staging holds at least `bytes` per slot; when it has to grow it grows to `want` (>= bytes), rounded up to pages.
 // Growing frees the ring: every update that may still read it has to be done first.
-static hipError_t vstage_reserve(GiState* g, size_t bytes, size_t want)
+hipError_t vstage_reserve(GiState* g, size_t bytes, size_t want)
 {
     if (bytes <= g->vstage_cap)
         return hipSuccess;
@@ -782,7 +782,7 @@ static hipError_t vstage_reserve(GiState* g, size_t bytes, size_t want)
     return hipSuccess;
 }
 // the slot of update `call`: its event exists, and the update kStageSlots calls ago has read it (long done unless the host runs that far ahead)
-static hipError_t stage_slot_acquire(GiState* g, uint32_t call, int* slot)
+hipError_t stage_slot_acquire(GiState* g, uint32_t call, int* slot)
 {
     const int s = (int)(call % (uint32_t)GiState::kStageSlots);
     *slot = s;
@@ -944,7 +944,7 @@ static hipError_t results_enqueue_readback(GiState* g, int slot, uint32_t call, 
 
 // A source of neb_gi_update_vertices_device: `bytes` from p must be memory this context's device reads at the very address p --
 // device memory of this device (and then inside its allocation), managed memory, or pinned host memory mapped at its own address.
-static bool device_readable(const neb_ctx* ctx, const void* p, size_t bytes)
+bool device_readable(const neb_ctx* ctx, const void* p, size_t bytes)
 {
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -968,7 +968,7 @@ static bool device_readable(const neb_ctx* ctx, const void* p, size_t bytes)
 }
 
 // order: behind the last rewrite, and behind every stream that may still be reading what is about to be rewritten
-static int refit_order_behind_readers(neb_ctx* ctx, GiState* g, hipStream_t stream)
+int refit_order_behind_readers(neb_ctx* ctx, GiState* g, hipStream_t stream)
 {
     GI_HIP(ctx, gi_sun_table_order(g, stream));
     if (g->reader_overflow) {

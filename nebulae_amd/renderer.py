@@ -166,6 +166,114 @@ class DeferredRenderer:
             self._check(self._lib.neb_gi_get_visibility(self._ctx, out.ctypes.data_as(C.POINTER(C.c_uint8)), n.value, None), "neb_gi_get_visibility")
         return out.astype(bool)
 
+    # ---- the material table and the textures uploaded again, the TLAS untouched (GIProcessedScene.cpp:16-137) ----
+    def _stream_arg(self, stream):
+        return C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+
+    def update_materials(self, indices, albedo=None, rough_metal=None, stream=None):
+        """New factors for materials indices[k]: albedo[k] (rgb; a fourth component is ignored) and / or rough_metal[k] (roughness,
+        metalness); None keeps what the material has.  The maps a material binds do not change (neb_gi_update_materials).  The tree and
+        the sun table are kept.  The renderer's scene object takes the same factors."""
+        if self._scene is None:
+            raise NebError("update_materials: no scene (init_pathtracer_scene first)")
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self._scene.materials)):
+            raise NebError("update_materials: material index out of range")
+        alb = None if albedo is None else np.asarray(albedo, np.float32).reshape(idx.size, -1)
+        rm = None if rough_metal is None else np.asarray(rough_metal, np.float32).reshape(idx.size, -1)
+        if (alb is not None and alb.shape[1] not in (3, 4)) or (rm is not None and rm.shape[1] != 2):
+            raise NebError("update_materials: albedo is n x 3 (or 4), rough_metal n x 2")
+        descs = (S.MaterialDesc * max(1, idx.size))()
+        new = []
+        for k, mi in enumerate(idx):
+            m = self._scene.materials[int(mi)]
+            a = tuple(float(v) for v in alb[k][:3]) + (m["albedo"][3],) if alb is not None else m["albedo"]
+            r = tuple(float(v) for v in rm[k]) if rm is not None else m["rm"]
+            descs[k].textureIndices[:] = m["textures"]
+            descs[k].albedo[:] = a
+            descs[k].roughnessMetalness[:] = r
+            new.append((a, r))
+        ids = np.ascontiguousarray(idx.astype(np.uint32))
+        self._check(self._lib.neb_gi_update_materials(self._ctx, ids.ctypes.data_as(C.POINTER(C.c_uint32)), descs, idx.size, self._stream_arg(stream)),
+                    "neb_gi_update_materials")
+        self._scene.materials = list(self._scene.materials)  # (a fresh list and fresh dicts: a Scene that shares its materials with a clone does not change the clone)
+        for mi, (a, r) in zip(idx, new):
+            self._scene.materials[int(mi)] = dict(self._scene.materials[int(mi)], albedo=a, rm=r)
+
+    def set_geometry_materials(self, indices, materials, stream=None):
+        """Geometry indices[k] names material materials[k] from here on; -1 = none (neb_gi_set_geometry_materials).  The tree and the sun
+        table are kept.  The renderer's scene object follows."""
+        if self._scene is None:
+            raise NebError("set_geometry_materials: no scene (init_pathtracer_scene first)")
+        idx = np.asarray(indices, np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= len(self._scene.geometries)):
+            raise NebError("set_geometry_materials: geometry index out of range")
+        mats = np.asarray(materials, np.int64).reshape(-1)
+        mats = np.full(idx.size, int(mats[0]), np.int64) if mats.size == 1 and idx.size != 1 else mats
+        if mats.size != idx.size:
+            raise NebError(f"set_geometry_materials: {idx.size} indices but {mats.size} materials")
+        if mats.size and mats.max() >= len(self._scene.materials):
+            raise NebError("set_geometry_materials: material index out of range")
+        ids, ms = np.ascontiguousarray(idx.astype(np.uint32)), np.ascontiguousarray(np.maximum(mats, -1).astype(np.int32))
+        self._check(self._lib.neb_gi_set_geometry_materials(self._ctx, ids.ctypes.data_as(C.POINTER(C.c_uint32)), ms.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                            idx.size, self._stream_arg(stream)), "neb_gi_set_geometry_materials")
+        for gi, mi in zip(idx, ms):
+            self._scene.geometries[int(gi)]["material"] = int(mi)
+
+    def update_texture(self, index, rgba8, x=0, y=0, stream=None, mirror=True):
+        """New texels for texture `index`: the rectangle at (x, y) of the size of rgba8 (rows x columns x 4 uint8).  A numpy array goes
+        through the host call (neb_gi_update_textures: copied before the call returns); a torch tensor on this renderer's device through
+        the device call (neb_gi_update_textures_device): rows may be strided and are read where they lie, in stream order -- `stream` has
+        to be ordered behind whatever wrote them and they must stay untouched until the stream has passed the update.  The tree and the sun
+        table are kept.  mirror=True: the renderer's scene object takes the texels (a device tensor is copied back for it: .cpu() waits)."""
+        if self._scene is None:
+            raise NebError("update_texture: no scene (init_pathtracer_scene first)")
+        index, x, y = int(index), int(x), int(y)
+        if not 0 <= index < len(self._scene.textures) or x < 0 or y < 0:
+            raise NebError("update_texture: texture index or origin out of range")
+        u = _lib.TextureUpdate(texture=index, x=x, y=y)
+        host = isinstance(rgba8, np.ndarray) or not hasattr(rgba8, "data_ptr")
+        if host:
+            px = np.asarray(rgba8)
+            if px.dtype != np.uint8 or px.ndim != 3 or px.shape[2] != 4:
+                raise NebError("update_texture: rgba8 must be uint8 of shape (rows, columns, 4)")
+            if px.size and (px.strides[2] != 1 or px.strides[1] != 4 or px.strides[0] < 4 * px.shape[1] or px.strides[0] % 4):
+                px = np.ascontiguousarray(px)
+            u.height, u.width = px.shape[0], px.shape[1]
+            u.pitchBytes = px.strides[0] if px.shape[0] > 1 else 4 * px.shape[1]
+            u.rgba8 = px.ctypes.data
+            fn, name = self._lib.neb_gi_update_textures, "neb_gi_update_textures"
+        else:
+            import torch
+            px = rgba8
+            if not isinstance(px, torch.Tensor) or not px.is_cuda or px.dtype != torch.uint8 or px.dim() != 3 or px.shape[2] != 4:
+                raise NebError("update_texture: rgba8 must be a uint8 device tensor of shape (rows, columns, 4)")
+            if px.numel() and (px.stride(2) != 1 or px.stride(1) != 4 or (px.shape[0] > 1 and (px.stride(0) < 4 * px.shape[1] or px.stride(0) % 4))):
+                raise NebError("update_texture: the texels of a row must be contiguous, rows a multiple of 4 bytes apart and not overlapping")
+            if px.device.index != self.svgf.device:
+                raise NebError("update_texture: rgba8 is on another device than the renderer")
+            u.height, u.width = px.shape[0], px.shape[1]
+            u.pitchBytes = px.stride(0) if px.shape[0] > 1 else 4 * px.shape[1]
+            u.rgba8 = px.data_ptr() if px.numel() else None
+            fn, name = self._lib.neb_gi_update_textures_device, "neb_gi_update_textures_device"
+        self._check(fn(self._ctx, C.byref(u), 1, self._stream_arg(stream)), name)
+        if mirror:  # (a fresh array and a fresh list: a Scene that shares its textures with a clone does not change the clone)
+            full = np.array(self._scene.textures[index], np.uint8, copy=True)
+            full[y:y + u.height, x:x + u.width] = px if host else px.cpu().numpy()
+            self._scene.textures = list(self._scene.textures)
+            self._scene.textures[index] = full
+
+    def texture_tables(self, stream=None):
+        """the texture tables as the device holds them, as bytes: the standalone footprint tables, then the material bundles
+        (neb_gi_debug_texture_tables; waits for the copy)"""
+        n = C.c_size_t(0)
+        self._check(self._lib.neb_gi_debug_texture_tables(self._ctx, None, 0, C.byref(n), None), "neb_gi_debug_texture_tables")
+        out = np.zeros(n.value, np.uint8)
+        if n.value:
+            self._check(self._lib.neb_gi_debug_texture_tables(self._ctx, out.ctypes.data, n.value, None, self._stream_arg(stream)),
+                        "neb_gi_debug_texture_tables")
+        return out
+
     # ---- no reference counterpart: its BLASes are built without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79) ----
     def update_vertices(self, index, positions, normals=None, tangents=None, first_vertex=0, stream=None):
         """Deform a submesh: vertices [first_vertex, first_vertex + len(positions)) of geometry `index` get new object-space positions
