@@ -405,8 +405,13 @@ struct GiState {
     size_t d_tstage_cap = 0;
 };
 // ---- what every update call does with the ring and with its streams (gi_refit.hip) ----
+// An update takes slot call % kStageSlots of the pinned rings once that slot's last user has read it (stage_slot_acquire), orders its
+// stream behind every reader of what it rewrites (refit_order_behind_readers), commits g->epoch = call, lets the slot go behind the last
+// command that reads it (stage_slot_release) and ends with mark_rewrite.  The geometry updates of gi_refit.hip go through this as
+// update_begin ... update_finish there, which add the result record and the rewrite of the tree; gi_material.hip calls the parts.
 hipError_t vstage_reserve(GiState* g, size_t bytes, size_t want);
 hipError_t stage_slot_acquire(GiState* g, uint32_t call, int* slot);
+hipError_t stage_slot_release(GiState* g, int slot, hipStream_t stream);
 bool device_readable(const neb_ctx* ctx, const void* p, size_t bytes);
 int refit_order_behind_readers(neb_ctx* ctx, GiState* g, hipStream_t stream);
 hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_t stream);

@@ -149,8 +149,7 @@ static int material_enqueue(neb_ctx* ctx, GiState* g, int slot, uint32_t call, c
                        const_cast<DevMat*>(g->view.mats), reassign ? const_cast<DevGeom*>(g->view.geoms) : (DevGeom*)nullptr,
                        reassign ? geom_epoch : mat_epoch);
     GI_HIP(ctx, hipGetLastError());
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
+    GI_HIP(ctx, stage_slot_release(g, slot, stream));
     if (g->n_geoms) {
         hipLaunchKernelGGL(shade_header_refresh_kernel, dim3((g->n_geoms + 63) / 64), dim3(64), 0, stream, g->n_geoms, n_mats, call, g->view.geoms, g->view.mats,
                            (const uint32_t*)mat_epoch, (const uint32_t*)geom_epoch, const_cast<ShadeHeader*>(g->shade_heads));
@@ -351,8 +350,7 @@ int neb_gi_update_textures(neb_ctx* ctx, const neb_texture_update* updates, uint
     }
     // ---- enqueue ----
     GI_HIP(ctx, hipMemcpyAsync(g->d_tstage, base, total, hipMemcpyHostToDevice, stream));
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
+    GI_HIP(ctx, stage_slot_release(g, slot, stream));
     off = 0;
     for (uint32_t k = 0; k < n; ++k) {
         const neb_texture_update& u = updates[k];

@@ -28,6 +28,12 @@
 // RTAccelerationStructureBuilder.cpp:100-130 is the PERFORM_UPDATE build): a word per geometry says whether its triangles exist for the rays.
 // visibility_apply_kernel stands where refit_apply_kernel stands; rebake_kernel gives the slots of a hidden geometry triangles no ray can hit,
 // refit_level_kernel leaves them out of the boxes, and every other update call goes through the same two kernels: hidden stays hidden.
+//
+// What the six update calls share is written once.  On the device: lane_range (a lane's range by bisection) and source_lane,
+// refuse_unless_finite (the refusal of the three check kernels), stamp_geometry and store_vertex (the end of the three scatter kernels),
+// skin_vertex (the skin kernels, and the skinned arm of the morph kernels).  On the host: geometry_named_once, collect_vertex_spans and
+// palette_finite for the refusals; UpdateCall with update_begin, update_touch, update_record_init, stage_slot_release and update_finish
+// for the chain -- each entry point keeps its own order of enqueues between them --; setup_fresh_blocks for the two set-up calls.
 #include <algorithm>
 
 #include "gi_device.h"
@@ -131,14 +137,68 @@ __global__ void rebake_kernel(float4* __restrict__ tris, uint32_t n_slots, uint3
     tris[3 * (size_t)i + 2] = make_float4(__fsub_rn(w2.z, w0.z), ids.y, ids.z, ids.w);
 }
 
+// ---- what the per-vertex kernels share ----
+// THE lane lookup: the index of the last range with first_lane <= k, by bisection (n ranges, ascending by first_lane, none empty).
+// Range: GiState::DeformRange or GiState::RollSpan.
+template <typename Range>
+__device__ __forceinline__ uint32_t lane_range(const Range* __restrict__ ranges, uint32_t n, uint32_t k)
+{
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (ranges[mid].first_lane <= k)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+// The lane's range, the source beside it (GiState::SkinSource / MorphSource) and its vertex inside the geometry; false: the lane has nothing to do.
+template <typename Source>
+__device__ __forceinline__ bool source_lane(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const Source* __restrict__ sources, uint32_t k,
+                                            uint32_t n_geoms, GiState::DeformRange& r, Source& s, uint32_t& j)
+{
+    const uint32_t i = lane_range(ranges, n_ranges, k);
+    r = ranges[i];
+    s = sources[i];
+    j = k - r.first_lane;
+    return j < r.count && j < s.n_verts && r.geom < n_geoms;
+}
+// THE refusal: the object-space position a, and its world point under the geometry's matrix m, must be finite within gi_bake_point's
+// bound -- what neb_gi_update_vertices checks on the host.  A failing lane sets the call's refusal word.
+__device__ __forceinline__ void refuse_unless_finite(const float a[3], const float* __restrict__ m, uint32_t* __restrict__ refused)
+{
+    const float3 w = bake_point(m, a);
+    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
+                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
+    if (!ok)
+        atomicOr(refused, 1u);
+}
+// THE stamp (lane 0 of a range): the geometry belongs to update `epoch`, and -- option svgf_vertex_motion, deform_dirty null with the
+// option off -- its dirty word is set, which gbuffer_kernel reads and deform_roll_kernel clears.
+__device__ __forceinline__ void stamp_geometry(uint32_t geom, uint32_t epoch, uint32_t* __restrict__ geom_epoch, uint32_t* __restrict__ deform_dirty)
+{
+    geom_epoch[geom] = epoch;
+    if (deform_dirty)
+        deform_dirty[geom] = 1u;
+}
+// vertex v of the pools: the position, and the normal (3 floats) and the tangent (4 floats) where the pointer is not null
+__device__ __forceinline__ void store_vertex(float* __restrict__ pos, float* __restrict__ normals, float* __restrict__ tangents, size_t v, const float* p,
+                                             const float* n, const float* t)
+{
+    pos[3 * v] = p[0], pos[3 * v + 1] = p[1], pos[3 * v + 2] = p[2];
+    if (n)
+        normals[3 * v] = n[0], normals[3 * v + 1] = n[1], normals[3 * v + 2] = n[2];
+    if (t)
+        tangents[4 * v] = t[0], tangents[4 * v + 1] = t[1], tangents[4 * v + 2] = t[2], tangents[4 * v + 3] = t[3];
+}
+
 // One lane per staged vertex: the compact streams of the update -> the object-space position pool and the normal / tangent pools.
-// The lane finds its range by bisection over first_lane (n ranges, ascending, none empty); lane 0 of a range stamps its geometry.
+// The lane finds its range by lane_range; lane 0 of a range stamps its geometry.
 // `stage` is the pinned slot itself or its device copy ("gi_deform_stage").
 // DEVICE_SRC: the vertices are not in the slot but where sources[range] points (strided device memory), and the whole launch leaves
 // at once when deform_check_kernel has set the call's refusal word -- nothing is written, no geometry is stamped, and every kernel
 // behind this one acts on stamped geometries only: a refused update is a no-op on the device.
-// deform_dirty (option svgf_vertex_motion, null with the option off): where the lane stamps its geometry it also sets the geometry's
-// dirty word, which gbuffer_kernel reads and deform_roll_kernel clears.
 template <bool DEVICE_SRC>
 __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const float* __restrict__ data, uint32_t n_lanes,
                                       uint32_t n_pool, uint32_t n_geoms, uint32_t epoch, float* __restrict__ pos, float* __restrict__ normals,
@@ -152,22 +212,14 @@ __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ r
     if constexpr (DEVICE_SRC)
         if (*refused)
             return;
-    uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ranges[mid].first_lane <= k)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const GiState::DeformRange r = ranges[lo];
+    const uint32_t i = lane_range(ranges, n_ranges, k);
+    const GiState::DeformRange r = ranges[i];
     const uint32_t j = k - r.first_lane;
     if (j >= r.count || r.dst + j >= n_pool)
         return;
-    const size_t v = (size_t)r.dst + j;
     const float *sp, *sn = nullptr, *st = nullptr;
     if constexpr (DEVICE_SRC) {
-        const GiState::DeformSource s = sources[lo];
+        const GiState::DeformSource s = sources[i];
         sp = reinterpret_cast<const float*>(s.pos + (size_t)j * s.pos_stride);
         if (r.nrm_off != GiState::kNoStream)
             sn = reinterpret_cast<const float*>(s.nrm + (size_t)j * s.nrm_stride);
@@ -180,21 +232,14 @@ __global__ void deform_scatter_kernel(const GiState::DeformRange* __restrict__ r
         if (r.tan_off != GiState::kNoStream)
             st = data + r.tan_off + 4 * (size_t)j;
     }
-    pos[3 * v] = sp[0], pos[3 * v + 1] = sp[1], pos[3 * v + 2] = sp[2];
-    if (sn)
-        normals[3 * v] = sn[0], normals[3 * v + 1] = sn[1], normals[3 * v + 2] = sn[2];
-    if (st)
-        tangents[4 * v] = st[0], tangents[4 * v + 1] = st[1], tangents[4 * v + 2] = st[2], tangents[4 * v + 3] = st[3];
-    if (j == 0 && r.geom < n_geoms) {
-        geom_epoch[r.geom] = epoch;
-        if (deform_dirty)
-            deform_dirty[r.geom] = 1u;
-    }
+    store_vertex(pos, normals, tangents, (size_t)r.dst + j, sp, sn, st);
+    if (j == 0 && r.geom < n_geoms)
+        stamp_geometry(r.geom, epoch, geom_epoch, deform_dirty);
 }
 
-// Option svgf_vertex_motion: one lane per vertex of the spans updated since the last roll, found by the scatter's bisection over the
-// spans' first lanes (n spans, ascending, none empty).  The lane copies its vertex's position and normal from the live pools to the
-// previous pools; lane 0 of a span clears its geometry's dirty word.  Enqueued behind gbuffer_kernel, which has read both.
+// Option svgf_vertex_motion: one lane per vertex of the spans updated since the last roll, found by lane_range over the spans' first
+// lanes.  The lane copies its vertex's position and normal from the live pools to the previous pools; lane 0 of a span clears its
+// geometry's dirty word.  Enqueued behind gbuffer_kernel, which has read both.
 __global__ void deform_roll_kernel(const GiState::RollSpan* __restrict__ spans, uint32_t n_spans, uint32_t n_lanes, uint32_t n_pool, uint32_t n_geoms,
                                    const float* __restrict__ pos, const float* __restrict__ normals, float* __restrict__ pos_prev,
                                    float* __restrict__ nrm_prev, uint32_t* __restrict__ deform_dirty)
@@ -202,15 +247,7 @@ __global__ void deform_roll_kernel(const GiState::RollSpan* __restrict__ spans, 
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_lanes)
         return;
-    uint32_t lo = 0, hi = n_spans; // the last span with first_lane <= k
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (spans[mid].first_lane <= k)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const GiState::RollSpan r = spans[lo];
+    const GiState::RollSpan r = spans[lane_range(spans, n_spans, k)];
     const uint32_t j = k - r.first_lane;
     if (j >= r.count || r.dst + j >= n_pool)
         return;
@@ -256,55 +293,26 @@ __device__ __forceinline__ float refit_max(float a, float b) { return refit_orde
 __device__ __forceinline__ float refit_min4(const float4 v) { return refit_min(refit_min(v.x, v.y), refit_min(v.z, v.w)); }
 __device__ __forceinline__ float refit_max4(const float4 v) { return refit_max(refit_max(v.x, v.y), refit_max(v.z, v.w)); }
 
-// One lane per source vertex of a device-sourced update, the bisection of deform_scatter_kernel: what neb_gi_update_vertices checks
-// on the host -- the position is finite, and finite under the geometry's current matrix (bake_point's products, gi_bake_point's bound).
-// A failing lane sets the call's refusal word.
+// One lane per source vertex of a device-sourced update, the ranges of deform_scatter_kernel: the source position goes through
+// refuse_unless_finite under the geometry's current matrix.
 __global__ void deform_check_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::DeformSource* __restrict__ sources,
                                     uint32_t n_lanes, uint32_t n_geoms, const float* __restrict__ xf, uint32_t* __restrict__ refused)
 {
     const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n_lanes)
         return;
-    uint32_t lo = 0, hi = n_ranges;
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ranges[mid].first_lane <= k)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    const GiState::DeformRange r = ranges[lo];
+    const uint32_t i = lane_range(ranges, n_ranges, k);
+    const GiState::DeformRange r = ranges[i];
     const uint32_t j = k - r.first_lane;
     if (j >= r.count || r.geom >= n_geoms)
         return;
-    const GiState::DeformSource s = sources[lo];
+    const GiState::DeformSource s = sources[i];
     const float* sp = reinterpret_cast<const float*>(s.pos + (size_t)j * s.pos_stride);
     const float a[3] = {sp[0], sp[1], sp[2]};
-    const float3 w = bake_point(xf + 16 * (size_t)r.geom, a);
-    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
-                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
-    if (!ok)
-        atomicOr(refused, 1u);
+    refuse_unless_finite(a, xf + 16 * (size_t)r.geom, refused);
 }
 
 // ---- skinning ----
-// The lane's range by the scatter's bisection, its source and its vertex inside the geometry; false: the lane has nothing to do.
-__device__ __forceinline__ bool skin_lane(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::SkinSource* __restrict__ sources,
-                                          uint32_t k, uint32_t n_geoms, GiState::DeformRange& r, GiState::SkinSource& s, uint32_t& j)
-{
-    uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ranges[mid].first_lane <= k)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    r = ranges[lo];
-    s = sources[lo];
-    j = k - r.first_lane;
-    return j < r.count && j < s.n_verts && r.geom < n_geoms && s.n_joints != 0u;
-}
 // The blended matrix of vertex j, THE written order: S[q] = ((w0 J0[q] + w1 J1[q]) + w2 J2[q]) + w3 J3[q] for rows 0-3, columns 0-2, every
 // product and every sum rounded by itself (rounded_product, __fadd_rn).  Column 3 of the joint matrices is never read.  A joint index is
 // clamped to the palette (neb_gi_set_skin refused the skin that has one beyond it: the clamp only keeps the read inside the buffer).
@@ -340,9 +348,23 @@ __device__ __forceinline__ float3 skin_direction(const float* S, float x, float 
     d.z = __fadd_rn(__fadd_rn(rounded_product(x, S[2]), rounded_product(y, S[6])), rounded_product(z, S[10]));
     return d;
 }
+// THE skinned vertex under the blended matrix S: the position by bake_point, then -- where the caller has them -- the normal and the
+// tangent's xyz by skin_direction, in this order; the tangent's w keeps its bits.  The skin kernels hand the bind pose, the morph kernels
+// the blended rest pose (glTF's order: morph, then skin).
+__device__ __forceinline__ float3 skin_vertex(const float* S, float3 p, bool attrs = false, float3* n = nullptr, float4* t = nullptr)
+{
+    const float a[3] = {p.x, p.y, p.z};
+    p = bake_point(S, a);
+    if (attrs) {
+        *n = skin_direction(S, n->x, n->y, n->z);
+        const float3 td = skin_direction(S, t->x, t->y, t->z);
+        t->x = td.x, t->y = td.y, t->z = td.z;
+    }
+    return p;
+}
 
-// One lane per vertex of the skinned geometries a call names: the skinned position, and the world point under the geometry's current
-// matrix, must be finite within gi_bake_point's bound; a failing lane sets the call's refusal word (deform_check_kernel's contract).
+// One lane per vertex of the skinned geometries a call names: the skinned position goes through refuse_unless_finite under the
+// geometry's current matrix (deform_check_kernel's contract).
 __global__ void skin_check_kernel(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::SkinSource* __restrict__ sources,
                                   const float* __restrict__ palette, uint32_t n_lanes, uint32_t n_geoms, const float* __restrict__ xf,
                                   uint32_t* __restrict__ refused)
@@ -353,19 +375,14 @@ __global__ void skin_check_kernel(const GiState::DeformRange* __restrict__ range
     GiState::DeformRange r;
     GiState::SkinSource s;
     uint32_t j;
-    if (!skin_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j))
+    if (!source_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || !s.n_joints)
         return;
     float S[16];
     skin_blend(s, palette, j, S);
     const float* bp = skin_bind_pos(s, j);
-    const float p[3] = {bp[0], bp[1], bp[2]};
-    const float3 a3 = bake_point(S, p);
+    const float3 a3 = skin_vertex(S, make_float3(bp[0], bp[1], bp[2]));
     const float a[3] = {a3.x, a3.y, a3.z};
-    const float3 w = bake_point(xf + 16 * (size_t)r.geom, a);
-    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
-                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
-    if (!ok)
-        atomicOr(refused, 1u);
+    refuse_unless_finite(a, xf + 16 * (size_t)r.geom, refused);
 }
 
 // One lane per vertex: position, normal and tangent from the BIND pose (never the live pools: a chain of calls does not drift) under the
@@ -385,48 +402,28 @@ __global__ void skin_scatter_kernel(const GiState::DeformRange* __restrict__ ran
     GiState::DeformRange r;
     GiState::SkinSource s;
     uint32_t j;
-    if (!skin_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || r.dst + j >= n_pool)
+    if (!source_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || !s.n_joints || r.dst + j >= n_pool)
         return;
-    const size_t v = (size_t)r.dst + j;
     float S[16];
     skin_blend(s, palette, j, S);
     const float* bp = skin_bind_pos(s, j);
-    const float p[3] = {bp[0], bp[1], bp[2]};
-    const float3 a = bake_point(S, p);
-    pos[3 * v] = a.x, pos[3 * v + 1] = a.y, pos[3 * v + 2] = a.z;
+    float3 p = make_float3(bp[0], bp[1], bp[2]), n = make_float3(0.f, 0.f, 0.f);
+    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
     if (s.attrs) {
         const float* bn = reinterpret_cast<const float*>(s.block + 52 * (size_t)s.n_verts) + 3 * (size_t)j;
-        const float4 bt = reinterpret_cast<const float4*>(s.block + 16 * (size_t)s.n_verts)[j];
-        const float3 n = skin_direction(S, bn[0], bn[1], bn[2]);
-        const float3 t = skin_direction(S, bt.x, bt.y, bt.z);
-        normals[3 * v] = n.x, normals[3 * v + 1] = n.y, normals[3 * v + 2] = n.z;
-        tangents[4 * v] = t.x, tangents[4 * v + 1] = t.y, tangents[4 * v + 2] = t.z, tangents[4 * v + 3] = bt.w;
+        n = make_float3(bn[0], bn[1], bn[2]);
+        t = reinterpret_cast<const float4*>(s.block + 16 * (size_t)s.n_verts)[j];
     }
-    if (j == 0) {
-        geom_epoch[r.geom] = epoch;
-        if (deform_dirty)
-            deform_dirty[r.geom] = 1u;
-    }
+    p = skin_vertex(S, p, s.attrs != 0u, &n, &t);
+    if (s.attrs)
+        store_vertex(pos, normals, tangents, (size_t)r.dst + j, &p.x, &n.x, &t.x);
+    else
+        store_vertex(pos, normals, tangents, (size_t)r.dst + j, &p.x, nullptr, nullptr);
+    if (j == 0)
+        stamp_geometry(r.geom, epoch, geom_epoch, deform_dirty);
 }
 
 // ---- morph targets ----
-// The lane's range by the scatter's bisection, its source and its vertex inside the geometry; false: the lane has nothing to do.
-__device__ __forceinline__ bool morph_lane(const GiState::DeformRange* __restrict__ ranges, uint32_t n_ranges, const GiState::MorphSource* __restrict__ sources,
-                                           uint32_t k, uint32_t n_geoms, GiState::DeformRange& r, GiState::MorphSource& s, uint32_t& j)
-{
-    uint32_t lo = 0, hi = n_ranges; // the last range with first_lane <= k
-    while (hi - lo > 1u) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (ranges[mid].first_lane <= k)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    r = ranges[lo];
-    s = sources[lo];
-    j = k - r.first_lane;
-    return j < r.count && j < s.n_verts && r.geom < n_geoms && s.n_targets != 0u;
-}
 // THE written order of one float3 stream: v[c] = v[c] + w * d_k[c] for each pair {k, w} of the lane's active list, in the list's order,
 // every product and every sum rounded by itself.  The order of the sums is fixed, the loads are not: four targets' deltas are fetched
 // before the first of their dependent adds, so that four round trips are in flight, not one.  `deltas` is the target-major stream
@@ -493,21 +490,16 @@ __global__ void morph_check_kernel(const GiState::DeformRange* __restrict__ rang
     GiState::DeformRange r;
     GiState::MorphSource s;
     uint32_t j;
-    if (!morph_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j))
+    if (!source_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || !s.n_targets)
         return;
-    const float3 m = morph_position(s, act, j);
-    float a[3] = {m.x, m.y, m.z};
+    float3 m = morph_position(s, act, j);
     if (s.n_joints) {
         float S[16];
         skin_blend(morph_skin(s), palette, j, S);
-        const float3 a3 = bake_point(S, a);
-        a[0] = a3.x, a[1] = a3.y, a[2] = a3.z;
+        m = skin_vertex(S, m);
     }
-    const float3 w = bake_point(xf + 16 * (size_t)r.geom, a);
-    const bool ok = fabsf(a[0]) <= 3.0e38f && fabsf(a[1]) <= 3.0e38f && fabsf(a[2]) <= 3.0e38f && fabsf(w.x) <= 3.0e38f && fabsf(w.y) <= 3.0e38f &&
-                    fabsf(w.z) <= 3.0e38f; // (a NaN fails every comparison)
-    if (!ok)
-        atomicOr(refused, 1u);
+    const float a[3] = {m.x, m.y, m.z};
+    refuse_unless_finite(a, xf + 16 * (size_t)r.geom, refused);
 }
 
 // One lane per vertex: m, n, t = the REST pose (never the live pools: a chain of calls does not drift) plus the active targets in the
@@ -528,9 +520,8 @@ __global__ void morph_scatter_kernel(const GiState::DeformRange* __restrict__ ra
     GiState::DeformRange r;
     GiState::MorphSource s;
     uint32_t j;
-    if (!morph_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || r.dst + j >= n_pool)
+    if (!source_lane(ranges, n_ranges, sources, k, n_geoms, r, s, j) || !s.n_targets || r.dst + j >= n_pool)
         return;
-    const size_t v = (size_t)r.dst + j;
     float3 m = morph_position(s, act, j);
     const bool attrs = (s.flags & GiState::kMorphAttrs) != 0u;
     float3 n = make_float3(0.f, 0.f, 0.f);
@@ -548,24 +539,14 @@ __global__ void morph_scatter_kernel(const GiState::DeformRange* __restrict__ ra
     if (s.n_joints) {
         float S[16];
         skin_blend(morph_skin(s), palette, j, S);
-        const float p[3] = {m.x, m.y, m.z};
-        m = bake_point(S, p);
-        if (attrs) {
-            n = skin_direction(S, n.x, n.y, n.z);
-            const float3 td = skin_direction(S, t.x, t.y, t.z);
-            t.x = td.x, t.y = td.y, t.z = td.z;
-        }
+        m = skin_vertex(S, m, attrs, &n, &t);
     }
-    pos[3 * v] = m.x, pos[3 * v + 1] = m.y, pos[3 * v + 2] = m.z;
-    if (attrs) {
-        normals[3 * v] = n.x, normals[3 * v + 1] = n.y, normals[3 * v + 2] = n.z;
-        tangents[4 * v] = t.x, tangents[4 * v + 1] = t.y, tangents[4 * v + 2] = t.z, tangents[4 * v + 3] = t.w;
-    }
-    if (j == 0) {
-        geom_epoch[r.geom] = epoch;
-        if (deform_dirty)
-            deform_dirty[r.geom] = 1u;
-    }
+    if (attrs)
+        store_vertex(pos, normals, tangents, (size_t)r.dst + j, &m.x, &n.x, &t.x);
+    else
+        store_vertex(pos, normals, tangents, (size_t)r.dst + j, &m.x, nullptr, nullptr);
+    if (j == 0)
+        stamp_geometry(r.geom, epoch, geom_epoch, deform_dirty);
 }
 
 // the result record of a call before its chain: {call, refusal word = 0, entries, 0}, every box word at the neutral element of atomicMin
@@ -791,15 +772,29 @@ hipError_t stage_slot_acquire(GiState* g, uint32_t call, int* slot)
             return e;
     return g->stage_used[s] ? hipEventSynchronize(g->stage_ev[s]) : hipSuccess;
 }
+// the slot is let go behind what has been enqueued on `stream` so far: the last command that reads the pinned memory
+hipError_t stage_slot_release(GiState* g, int slot, hipStream_t stream)
+{
+    if (hipError_t e = hipEventRecord(g->stage_ev[slot], stream); e != hipSuccess)
+        return e;
+    g->stage_used[slot] = true;
+    return hipSuccess;
+}
 static hipError_t results_enqueue_boxes(GiState* g, int slot, uint32_t n_entries, hipStream_t stream);
-// what follows the kernel that stamped the geometries: their triangles baked again, the normal and tangent words of their records where
-// these changed, the boxes of the slot's entry list, the levels of the tree, the 64-byte nodes
-static hipError_t refit_enqueue_rewrite(GiState* g, int slot, uint32_t call, bool repack, uint32_t n_boxed, hipStream_t stream)
+// the triangles of the geometries stamped `call` baked again (hidden ones: emptied), one lane per leaf-order slot
+static void refit_enqueue_rebake(GiState* g, uint32_t call, hipStream_t stream)
 {
     const uint32_t n_slots = g->view.n_tris;
     hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
                        (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf,
                        (const uint32_t*)g->d_visible);
+}
+// what follows the kernel that stamped the geometries: their triangles baked again, the normal and tangent words of their records where
+// these changed, the boxes of the slot's entry list, the levels of the tree, the 64-byte nodes
+static hipError_t refit_enqueue_rewrite(GiState* g, int slot, uint32_t call, bool repack, uint32_t n_boxed, hipStream_t stream)
+{
+    const uint32_t n_slots = g->view.n_tris;
+    refit_enqueue_rebake(g, call, stream);
     if (repack)
         hipLaunchKernelGGL(repack_records_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream,
                            reinterpret_cast<float*>(const_cast<float4*>(g->view.shade)), g->view.tris, n_slots, g->n_geoms, call,
@@ -820,6 +815,7 @@ static float refit_unordered(uint32_t k) // the float whose refit_ordered key is
     return f;
 }
 static size_t result_stride(const GiState* g) { return GiState::kResultHead + (size_t)GiState::kResultEntry * g->n_geoms; }
+static uint32_t* result_refusal_word(GiState* g, int slot) { return g->d_result + (size_t)slot * result_stride(g) + 1; }
 
 hipError_t gi_harvest_results(GiState* g, bool block, uint32_t upto)
 {
@@ -1080,8 +1076,7 @@ int gi_roll_vertices(neb_ctx* ctx, hipStream_t stream)
     hipLaunchKernelGGL(deform_roll_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::RollSpan*)spans, n_spans, lane, n_pool,
                        g->n_geoms, (const float*)g->d_pos, g->view.normals, g->d_pos_prev, g->d_nrm_prev, g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
+    GI_HIP(ctx, stage_slot_release(g, slot, stream));
     return NEB_OK;
 }
 
@@ -1095,13 +1090,201 @@ hipError_t gi_visibility_after_build(GiState* g, hipStream_t stream)
     const uint32_t call = ++g->epoch;
     hipLaunchKernelGGL(visibility_stamp_kernel, dim3((g->n_geoms + 63) / 64), dim3(64), 0, stream, g->n_geoms, call, (const uint32_t*)g->d_visible,
                        g->d_geom_epoch);
-    const uint32_t n_slots = g->view.n_tris;
-    hipLaunchKernelGGL(rebake_kernel, dim3((n_slots + 255) / 256), dim3(256), 0, stream, const_cast<float4*>(g->view.tris), n_slots, g->n_geoms, call,
-                       (const uint32_t*)g->d_geom_epoch, g->view.geoms, g->view.indices, (const float*)g->d_pos, (const float*)g->d_xf,
-                       (const uint32_t*)g->d_visible);
+    refit_enqueue_rebake(g, call, stream);
     if (hipError_t e = hipGetLastError(); e != hipSuccess)
         return e;
     return refit_enqueue_levels(g, call, stream);
+}
+
+// ---- what the update calls share on the host: refusals ----
+static int fail_who(neb_ctx* ctx, int code, const char* who, const char* what, hipError_t e = hipSuccess)
+{
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return gi_fail(ctx, code, msg, e);
+}
+// One entry of a call's geometry list: the index is in range (range_code where it is not) and the call has not named it before.
+// stamp = ++g->seen_stamp, one per call, accepted or not: h_seen needs no clearing.
+static int geometry_named_once(neb_ctx* ctx, GiState* g, uint32_t stamp, uint32_t gi, const char* who, int range_code)
+{
+    if (gi >= g->n_geoms)
+        return fail_who(ctx, range_code, who, "geometry index out of range");
+    if (g->h_seen[gi] == stamp)
+        return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "a geometry is named twice");
+    g->h_seen[gi] = stamp;
+    return NEB_OK;
+}
+// columns 0-2 of every joint matrix of a palette are finite (column 3 is never read: skin_blend)
+static bool palette_finite(const float* m, uint32_t n_joints)
+{
+    for (uint32_t q = 0; q < 16u * n_joints; ++q)
+        if ((q & 3u) != 3u && !std::isfinite(m[q]))
+            return false;
+    return true;
+}
+// What neb_gi_update_vertices and neb_gi_update_vertices_device (device_sources: pointers and strides are multiples of 4, the lanes
+// load floats) check of their entries before anything changes.  The ranges that are not empty come back sorted by {geometry, first
+// vertex}, with the numbers of vertices in all of them, and in those that carry normals and tangents.
+struct VertexSpan { uint32_t geom, first, count, k; };
+static int collect_vertex_spans(neb_ctx* ctx, const GiState* g, const neb_vertex_update* updates, uint32_t n, const char* who, bool device_sources,
+                                std::vector<VertexSpan>& spans, size_t& n_lanes, size_t& n_nrm, size_t& n_tan)
+{
+    spans.reserve(n);
+    n_lanes = n_nrm = n_tan = 0;
+    for (uint32_t k = 0; k < n; ++k) {
+        const neb_vertex_update& u = updates[k];
+        if (!u.positions)
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "null positions");
+        if (u.geometry >= g->n_geoms)
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "geometry index out of range");
+        const GiState::HostGeom& hg = g->h_geoms[u.geometry];
+        if ((uint64_t)u.firstVertex + u.numVertices > hg.n_verts)
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "vertex range beyond the geometry's numVertices");
+        if ((u.normals || u.tangents) && !hg.valid)
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "normals or tangents for a geometry that was set without its attribute streams");
+        if (u.positionStride < 12u || (u.normals && u.normalStride < 12u) || (u.tangents && u.tangentStride < 16u))
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "a stride is smaller than its element");
+        if (device_sources && ((((uintptr_t)u.positions | u.positionStride) & 3u) || (u.normals && (((uintptr_t)u.normals | u.normalStride) & 3u)) ||
+                               (u.tangents && (((uintptr_t)u.tangents | u.tangentStride) & 3u))))
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "a pointer or a stride is not a multiple of 4");
+        if (u.numVertices == 0)
+            continue;
+        spans.push_back({u.geometry, u.firstVertex, u.numVertices, k});
+        n_lanes += u.numVertices;
+        n_nrm += u.normals ? u.numVertices : 0u;
+        n_tan += u.tangents ? u.numVertices : 0u;
+    }
+    std::sort(spans.begin(), spans.end(), [](const VertexSpan& a, const VertexSpan& b) { return a.geom != b.geom ? a.geom < b.geom : a.first < b.first; });
+    for (size_t i = 1; i < spans.size(); ++i)
+        if (spans[i].geom == spans[i - 1].geom && (uint64_t)spans[i - 1].first + spans[i - 1].count > spans[i].first)
+            return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "two ranges of one geometry overlap");
+    if (n_lanes > 0xffffffffull / 10u) // (lanes are 32-bit, and so are the offsets into the slot, in floats: at most 10 floats per vertex)
+        return fail_who(ctx, NEB_ERR_INVALID_ARG, who, "too many vertices in one call");
+    return NEB_OK;
+}
+
+// ---- what the update calls share on the host: the chain ----
+// One accepted call from its ring slot to the end of its chain.  device_sourced: the new vertices never pass the host (neb_gi_update_
+// vertices_device, neb_gi_skin_vertices, neb_gi_morph_vertices) -- h_pos of every touched geometry goes stale, and the call always has
+// a result record, which counts in neb_gi_update_status.  Every other call has one where it touches a geometry whose h_pos is stale.
+struct UpdateCall {
+    neb_ctx* ctx;
+    GiState* g;
+    hipStream_t stream;
+    bool device_sourced;
+    uint32_t call = 0;      // the epoch of this update
+    int slot = 0;           // its slot in the rings (arguments, entry lists, result records)
+    bool may_record = false; // update_begin made the slot's result record ready
+    bool any_tris = false;  // a touched geometry has triangles: the chain rewrites them
+    GiState::ResultRecord& rec() const { return g->result_rec[slot]; }
+    uint32_t n_boxed() const { return may_record ? (uint32_t)rec().geoms.size() : 0u; }
+    bool has_record() const { return device_sourced || n_boxed() != 0u; }
+};
+// The slot of the call, its result record where the call may need one (the record of kStageSlots calls ago is applied first), the
+// stream ordered behind every reader -- and then, nothing being able to fail any more, the epoch: the call counts.
+static int update_begin(UpdateCall& uc, bool may_record)
+{
+    GiState* g = uc.g;
+    uc.call = g->epoch + 1u;
+    uc.may_record = may_record;
+    GI_HIP(uc.ctx, stage_slot_acquire(g, uc.call, &uc.slot));
+    if (may_record) {
+        GI_HIP(uc.ctx, results_acquire(g, uc.slot));
+        uc.rec().geoms.clear();
+    }
+    if (int rc = refit_order_behind_readers(uc.ctx, g, uc.stream); rc != NEB_OK)
+        return rc;
+    g->epoch = uc.call;
+    return NEB_OK;
+}
+// The call changes geometry gi: h_tris holds an earlier bake of its triangles from here on, and where h_pos does not hold its vertices the
+// geometry joins the slot's entry list (geom_box_kernel) and the result record that brings its boxes back -- once: a caller that
+// names a geometry several times names it in a row.
+static void update_touch(UpdateCall& uc, uint32_t gi)
+{
+    GiState* g = uc.g;
+    GiState::HostGeom& hg = g->h_geoms[gi];
+    if (uc.device_sourced)
+        hg.host_stale = true;
+    if (!hg.n_tris)
+        return;
+    hg.dirty = true;
+    uc.any_tris = true;
+    std::vector<uint32_t>& listed = uc.rec().geoms;
+    if (!hg.host_stale || (!listed.empty() && listed.back() == gi))
+        return;
+    g->h_box_list[(size_t)uc.slot * g->n_geoms + listed.size()] = gi;
+    listed.push_back(gi);
+}
+// first in the chain wherever there is a record: its head and the neutral boxes of its entries
+static hipError_t update_record_init(const UpdateCall& uc)
+{
+    return uc.has_record() ? results_enqueue_init(uc.g, uc.slot, uc.call, uc.n_boxed(), uc.stream) : hipSuccess;
+}
+// The end of every chain, behind the kernel that stamped the geometries: the rewrite where a touched geometry has triangles, the
+// record on its way back where there is one, the rewrite marked for the readers on other streams.
+static int update_finish(UpdateCall& uc, bool repack)
+{
+    GiState* g = uc.g;
+    if (uc.any_tris && g->view.n_tris)
+        GI_HIP(uc.ctx, refit_enqueue_rewrite(g, uc.slot, uc.call, repack, uc.n_boxed(), uc.stream));
+    if (uc.has_record())
+        GI_HIP(uc.ctx, results_enqueue_readback(g, uc.slot, uc.call, uc.device_sourced, uc.stream));
+    GI_HIP(uc.ctx, mark_rewrite(g, uc.stream));
+    return NEB_OK;
+}
+
+// The second half of neb_gi_set_skin and neb_gi_set_morph_targets, behind their checks.  What the call needs is allocated before anything
+// is let go of: a fresh block of block_bytes[k] for entry k (0: the entry removes), and a fresh argument buffer where the capacity changes.
+// Everything that can still fail fills the FRESH blocks -- fill(k, block) -- behind a rewrite enqueued on another stream (gi_scene_reader;
+// a later rewrite waits for the copies).  A failure frees them and nothing of the context has changed; success commits the argument
+// buffer and hands the blocks over in `fresh` for the caller to bind (rebind_block): from there on nothing can fail.
+template <typename Fill>
+static int setup_fresh_blocks(neb_ctx* ctx, GiState* g, hipStream_t stream, const char* who, const std::vector<size_t>& block_bytes, size_t args_cap,
+                              std::vector<void*>& fresh, Fill fill)
+{
+    const size_t n = block_bytes.size();
+    fresh.assign(n, nullptr);
+    void* fresh_args = nullptr;
+    hipError_t e = hipSuccess;
+    for (size_t k = 0; k < n && e == hipSuccess; ++k)
+        if (block_bytes[k])
+            e = hipMalloc(&fresh[k], block_bytes[k]);
+    if (e == hipSuccess && args_cap && args_cap != g->skin_args_cap)
+        e = hipMalloc(&fresh_args, args_cap);
+    if (e == hipSuccess)
+        e = hipDeviceSynchronize(); // (a set-up call: a call still in flight reads the blocks and the argument buffer about to be replaced)
+    if (e == hipSuccess)
+        e = gi_scene_reader(g, stream);
+    for (size_t k = 0; k < n && e == hipSuccess; ++k)
+        if (fresh[k])
+            e = fill((uint32_t)k, (uint8_t*)fresh[k]);
+    if (e != hipSuccess) {
+        for (void* p : fresh)
+            if (p)
+                (void)hipFree(p); // (waits for the device: a copy into the block that was enqueued is done)
+        if (fresh_args)
+            (void)hipFree(fresh_args);
+        return fail_who(ctx, NEB_ERR_HIP, who, "device memory", e);
+    }
+    if (args_cap != g->skin_args_cap) {
+        if (g->d_skin_args)
+            (void)hipFree(g->d_skin_args);
+        g->d_skin_args = fresh_args;
+        g->skin_args_cap = args_cap;
+    }
+    return NEB_OK;
+}
+// the geometry's old block is freed and its entry (GiState::Skin / Morph) starts again with the fresh one (null: unbound)
+template <typename Bound>
+static Bound& rebind_block(std::vector<Bound>& bound, uint32_t gi, void* fresh)
+{
+    Bound& b = bound[gi];
+    if (b.d_block)
+        (void)hipFree(b.d_block);
+    b = Bound();
+    b.d_block = fresh;
+    return b;
 }
 
 } // namespace neb
@@ -1123,33 +1306,22 @@ int neb_gi_set_visibility(neb_ctx* ctx, const uint32_t* geometry_indices, const 
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_visibility: null pointer");
     GI_HIP(ctx, gi_harvest_results(g, false));
     // ---- everything that can refuse the call comes before anything changes ----
-    const uint32_t call = g->epoch + 1u;
-    const uint32_t stamp = ++g->seen_stamp; // (one per call, accepted or not: h_seen needs no clearing)
-    for (uint32_t k = 0; k < n; ++k) {
-        const uint32_t gi = geometry_indices[k];
-        if (gi >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_set_visibility: geometry index out of range");
-        if (g->h_seen[gi] == stamp)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_visibility: a geometry is named twice");
-        g->h_seen[gi] = stamp;
-    }
+    const uint32_t stamp = ++g->seen_stamp;
+    for (uint32_t k = 0; k < n; ++k)
+        if (int rc = geometry_named_once(ctx, g, stamp, geometry_indices[k], "neb_gi_set_visibility", NEB_ERR_OUT_OF_RANGE); rc != NEB_OK)
+            return rc;
     uint32_t n_changed = 0; // (n <= n_geoms from here on: every index is in range and none is named twice)
     for (uint32_t k = 0; k < n; ++k)
         n_changed += (g->h_visible[geometry_indices[k]] != 0) != (visible[k] != 0) ? 1u : 0u;
     if (n_changed == 0)
         return NEB_OK; // every geometry is in the state asked for: nothing is enqueued, the sun table stays
-    hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
-    // ---- the argument slot: pinned host memory the first kernel reads ----
-    int slot = 0;
-    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
-    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+    UpdateCall uc{ctx, g, (hipStream_t)stream_, false};
+    if (int rc = update_begin(uc, false); rc != NEB_OK)
         return rc;
-    // ---- commit the host side ----
-    g->epoch = call;
-    GiState::StageEntry* st = g->h_stage + (size_t)slot * g->n_geoms;
+    // ---- commit the host side; the argument slot is pinned host memory the first kernel reads ----
+    GiState::StageEntry* st = g->h_stage + (size_t)uc.slot * g->n_geoms;
     uint32_t ns = 0;
-    bool any_tris = false;
     for (uint32_t k = 0; k < n; ++k) {
         const uint32_t gi = geometry_indices[k];
         const uint8_t v = visible[k] ? 1 : 0;
@@ -1161,20 +1333,16 @@ int neb_gi_set_visibility(neb_ctx* ctx, const uint32_t* geometry_indices, const 
         st[ns].geom = gi;
         st[ns].pad[0] = v;
         ++ns;
-        any_tris = any_tris || g->h_geoms[gi].n_tris != 0;
+        uc.any_tris = uc.any_tris || g->h_geoms[gi].n_tris != 0; // (no update_touch: the vertices and h_tris stay what they are)
     }
     refit_scene_box(g);
     refit_drop_sun_table(g);
     // ---- enqueue ----
-    hipLaunchKernelGGL(visibility_apply_kernel, dim3((ns + 63) / 64), dim3(64), 0, stream, (const GiState::StageEntry*)st, ns, g->n_geoms, call, g->d_visible,
-                       g->d_geom_epoch);
+    hipLaunchKernelGGL(visibility_apply_kernel, dim3((ns + 63) / 64), dim3(64), 0, uc.stream, (const GiState::StageEntry*)st, ns, g->n_geoms, uc.call,
+                       g->d_visible, g->d_geom_epoch);
     GI_HIP(ctx, hipGetLastError());
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
-    if (any_tris && g->view.n_tris)
-        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, false, 0u, stream));
-    GI_HIP(ctx, mark_rewrite(g, stream));
-    return NEB_OK;
+    GI_HIP(ctx, stage_slot_release(g, uc.slot, uc.stream));
+    return update_finish(uc, false);
 }
 
 int neb_gi_get_visibility(const neb_ctx* ctx, uint8_t* out, uint32_t capacity, uint32_t* n_out)
@@ -1208,16 +1376,10 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_transforms: more entries than geometries (an index is out of range or named twice)");
     GI_HIP(ctx, gi_harvest_results(g, false));
     // ---- everything that can refuse the call comes before anything changes ----
-    const uint32_t call = g->epoch + 1u;
-    const uint32_t stamp = ++g->seen_stamp; // (one per call, accepted or not: h_seen needs no clearing)
-    for (uint32_t k = 0; k < n; ++k) {
-        const uint32_t gi = geometry_indices[k];
-        if (gi >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_transforms: geometry index out of range");
-        if (g->h_seen[gi] == stamp)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_transforms: a geometry is named twice");
-        g->h_seen[gi] = stamp;
-    }
+    const uint32_t stamp = ++g->seen_stamp;
+    for (uint32_t k = 0; k < n; ++k)
+        if (int rc = geometry_named_once(ctx, g, stamp, geometry_indices[k], "neb_gi_update_transforms", NEB_ERR_INVALID_ARG); rc != NEB_OK)
+            return rc;
     // A geometry whose h_pos is stale (neb_gi_update_vertices_device) is checked by the corners of its object-space box alone -- current
     // once every record has been harvested -- and takes its world box from geom_box_kernel and a result record, not from a host walk.
     bool any_stale = false;
@@ -1272,21 +1434,13 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
             }
         }
     }
-    hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
-    // ---- the argument slot: pinned host memory the first kernel reads ----
-    int slot = 0;
-    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
-    if (any_stale)
-        GI_HIP(ctx, results_acquire(g, slot));
-    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+    UpdateCall uc{ctx, g, (hipStream_t)stream_, false};
+    if (int rc = update_begin(uc, any_stale); rc != NEB_OK)
         return rc;
-    // ---- commit the host side ----
-    g->epoch = call;
-    GiState::StageEntry* st = g->h_stage + (size_t)slot * g->n_geoms;
+    // ---- commit the host side; the argument slot is pinned host memory the first kernel reads ----
+    GiState::StageEntry* st = g->h_stage + (size_t)uc.slot * g->n_geoms;
     uint32_t ns = 0;
-    bool any_tris = false;
-    std::vector<uint32_t> boxed; // the stale geometries among the moved ones: entries of this call's result record
     for (uint32_t k = 0; k < n; ++k) {
         if (!changed[k])
             continue;
@@ -1297,45 +1451,28 @@ int neb_gi_update_transforms(neb_ctx* ctx, const uint32_t* geometry_indices, con
         st[ns].pad[0] = st[ns].pad[1] = st[ns].pad[2] = 0;
         memcpy(st[ns].m, hg.m, 64);
         ++ns;
-        if (hg.n_tris) {
-            hg.dirty = true;
-            any_tris = true;
-            if (hg.host_stale) {
-                boxed.push_back(gi);
-            } else {
-                memcpy(hg.world_lo, boxes[k].lo, 12);
-                memcpy(hg.world_hi, boxes[k].hi, 12);
-            }
+        update_touch(uc, gi); // (the stale geometries among the moved ones become entries of this call's result record)
+        if (hg.n_tris && !hg.host_stale) {
+            memcpy(hg.world_lo, boxes[k].lo, 12);
+            memcpy(hg.world_hi, boxes[k].hi, 12);
         }
     }
-    if (!boxed.empty())
-        memcpy(g->h_box_list + (size_t)slot * g->n_geoms, boxed.data(), boxed.size() * sizeof(uint32_t));
-    if (any_tris) {
+    if (uc.any_tris) {
         refit_scene_box(g);
         refit_drop_sun_table(g);
     }
     // ---- enqueue ----
-    const uint32_t n_slots = g->view.n_tris;
-    if (!boxed.empty())
-        GI_HIP(ctx, results_enqueue_init(g, slot, call, (uint32_t)boxed.size(), stream));
-    hipLaunchKernelGGL(refit_apply_kernel, dim3((ns + 63) / 64), dim3(64), 0, stream, (const GiState::StageEntry*)st, ns, g->n_geoms, call, g->d_xf,
+    GI_HIP(ctx, update_record_init(uc));
+    hipLaunchKernelGGL(refit_apply_kernel, dim3((ns + 63) / 64), dim3(64), 0, uc.stream, (const GiState::StageEntry*)st, ns, g->n_geoms, uc.call, g->d_xf,
                        const_cast<DevGeom*>(g->view.geoms), const_cast<ShadeHeader*>(g->shade_heads), g->d_geom_epoch);
     GI_HIP(ctx, hipGetLastError());
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
-    if (any_tris && n_slots) {
-        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, false, (uint32_t)boxed.size(), stream));
-    }
-    if (!boxed.empty()) {
-        g->result_rec[slot].geoms = std::move(boxed);
-        GI_HIP(ctx, results_enqueue_readback(g, slot, call, false, stream));
-    }
-    GI_HIP(ctx, mark_rewrite(g, stream));
-    return NEB_OK;
+    GI_HIP(ctx, stage_slot_release(g, uc.slot, uc.stream));
+    return update_finish(uc, false);
 }
 
 int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream_)
 {
+    static const char who[] = "neb_gi_update_vertices";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -1347,37 +1484,11 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: null pointer");
     GI_HIP(ctx, gi_harvest_results(g, false));
     // ---- everything that can refuse the call comes before anything changes ----
-    struct Span { uint32_t geom, first, count, k; };
-    std::vector<Span> spans;
-    spans.reserve(n);
-    size_t n_lanes = 0, n_nrm = 0, n_tan = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        const neb_vertex_update& u = updates[k];
-        if (!u.positions)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: null positions");
-        if (u.geometry >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: geometry index out of range");
-        const GiState::HostGeom& hg = g->h_geoms[u.geometry];
-        if ((uint64_t)u.firstVertex + u.numVertices > hg.n_verts)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: vertex range beyond the geometry's numVertices");
-        if ((u.normals || u.tangents) && !hg.valid)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: normals or tangents for a geometry that was set without its attribute streams");
-        if (u.positionStride < 12u || (u.normals && u.normalStride < 12u) || (u.tangents && u.tangentStride < 16u))
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: a stride is smaller than its element");
-        if (u.numVertices == 0)
-            continue;
-        spans.push_back({u.geometry, u.firstVertex, u.numVertices, k});
-        n_lanes += u.numVertices;
-        n_nrm += u.normals ? u.numVertices : 0u;
-        n_tan += u.tangents ? u.numVertices : 0u;
-    }
-    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom != b.geom ? a.geom < b.geom : a.first < b.first; });
-    for (size_t i = 1; i < spans.size(); ++i)
-        if (spans[i].geom == spans[i - 1].geom && (uint64_t)spans[i - 1].first + spans[i - 1].count > spans[i].first)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: two ranges of one geometry overlap");
-    if (n_lanes > 0xffffffffull / 10u) // (offsets into the slot are 32-bit float counts: at most 10 floats per vertex)
-        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices: too many vertices in one call");
-    for (const Span& sp : spans) {
+    std::vector<VertexSpan> spans;
+    size_t n_lanes, n_nrm, n_tan;
+    if (int rc = collect_vertex_spans(ctx, g, updates, n, who, false, spans, n_lanes, n_nrm, n_tan); rc != NEB_OK)
+        return rc;
+    for (const VertexSpan& sp : spans) {
         const neb_vertex_update& u = updates[sp.k];
         const float* m = g->h_geoms[sp.geom].m;
         for (uint32_t j = 0; j < sp.count; ++j) {
@@ -1391,14 +1502,12 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
     }
     if (spans.empty())
         return NEB_OK; // every range is empty: nothing moves, nothing is enqueued, the sun table stays
-    hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
-    // the touched geometries whose h_pos is stale (neb_gi_update_vertices_device): their boxes come from geom_box_kernel and a result record
-    std::vector<uint32_t> boxed;
-    for (size_t i = 0; i < spans.size(); ++i)
-        if ((!i || spans[i].geom != spans[i - 1].geom) && g->h_geoms[spans[i].geom].host_stale && g->h_geoms[spans[i].geom].n_tris)
-            boxed.push_back(spans[i].geom);
-    if (!boxed.empty())
+    // a touched geometry whose h_pos is stale (neb_gi_update_vertices_device): its boxes come from geom_box_kernel and a result record
+    bool any_boxed = false;
+    for (const VertexSpan& sp : spans)
+        any_boxed = any_boxed || (g->h_geoms[sp.geom].host_stale && g->h_geoms[sp.geom].n_tris);
+    if (any_boxed)
         GI_HIP(ctx, results_prepare(g));
     // ---- the staging slot: pinned host memory, {ranges | positions | normals | tangents}, grown to the largest update seen ----
     const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
@@ -1412,22 +1521,17 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         g->d_vstage = fresh;
         g->d_vstage_cap = g->vstage_cap;
     }
-    const uint32_t call = g->epoch + 1u;
-    int slot = 0;
-    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
-    if (!boxed.empty())
-        GI_HIP(ctx, results_acquire(g, slot));
-    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+    UpdateCall uc{ctx, g, (hipStream_t)stream_, false};
+    if (int rc = update_begin(uc, any_boxed); rc != NEB_OK)
         return rc;
     // ---- commit the host side: the slot, h_pos, the boxes ----
-    g->epoch = call;
-    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)uc.slot * g->vstage_cap;
     GiState::DeformRange* ranges = (GiState::DeformRange*)base;
     float* data = (float*)(base + head);
     uint32_t lane = 0, off_p = 0, off_n = (uint32_t)(3u * n_lanes), off_t = (uint32_t)(3u * n_lanes + 3u * n_nrm);
-    bool any_tris = false, any_attr = false;
+    bool any_attr = false;
     for (size_t i = 0; i < spans.size(); ++i) {
-        const Span& sp = spans[i];
+        const VertexSpan& sp = spans[i];
         const neb_vertex_update& u = updates[sp.k];
         GiState::HostGeom& hg = g->h_geoms[sp.geom];
         GiState::DeformRange& r = ranges[i];
@@ -1451,10 +1555,7 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
         off_n += u.normals ? 3u * sp.count : 0u;
         off_t += u.tangents ? 4u * sp.count : 0u;
         any_attr = any_attr || u.normals || u.tangents;
-        if (hg.n_tris) {
-            hg.dirty = true;
-            any_tris = true;
-        }
+        update_touch(uc, sp.geom);
     }
     // the boxes of every touched geometry over its referenced vertices: object space, and world space in the bake's own arithmetic
     for (size_t i = 0; i < spans.size(); ++i) {
@@ -1479,41 +1580,30 @@ int neb_gi_update_vertices(neb_ctx* ctx, const neb_vertex_update* updates, uint3
             }
         }
     }
-    if (any_tris)
+    if (uc.any_tris) {
         refit_scene_box(g);
-    if (any_tris)
         refit_drop_sun_table(g);
-    // ---- enqueue ----
-    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
-    const uint8_t* src = base;
-    if (!boxed.empty()) {
-        memcpy(g->h_box_list + (size_t)slot * g->n_geoms, boxed.data(), boxed.size() * sizeof(uint32_t));
-        GI_HIP(ctx, results_enqueue_init(g, slot, call, (uint32_t)boxed.size(), stream));
     }
+    // ---- enqueue ----
+    const uint32_t n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
+    const uint8_t* src = base;
+    GI_HIP(ctx, update_record_init(uc));
     if (g->deform_stage == 1) {
-        GI_HIP(ctx, hipMemcpyAsync(g->d_vstage, base, bytes, hipMemcpyHostToDevice, stream));
+        GI_HIP(ctx, hipMemcpyAsync(g->d_vstage, base, bytes, hipMemcpyHostToDevice, uc.stream));
         src = (const uint8_t*)g->d_vstage;
     }
-    hipLaunchKernelGGL(deform_scatter_kernel<false>, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)src, n_ranges,
-                       (const float*)(src + head), lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
+    hipLaunchKernelGGL(deform_scatter_kernel<false>, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)src, n_ranges,
+                       (const float*)(src + head), lane, n_pool, g->n_geoms, uc.call, g->d_pos, const_cast<float*>(g->view.normals),
                        const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)nullptr, (const uint32_t*)nullptr,
                        g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
-    if (any_tris && n_slots) {
-        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, any_attr, (uint32_t)boxed.size(), stream));
-    }
-    if (!boxed.empty()) {
-        g->result_rec[slot].geoms = std::move(boxed);
-        GI_HIP(ctx, results_enqueue_readback(g, slot, call, false, stream));
-    }
-    GI_HIP(ctx, mark_rewrite(g, stream));
-    return NEB_OK;
+    GI_HIP(ctx, stage_slot_release(g, uc.slot, uc.stream));
+    return update_finish(uc, any_attr);
 }
 
 int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates, uint32_t n, neb_stream stream_)
 {
+    static const char who[] = "neb_gi_update_vertices_device";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -1525,42 +1615,14 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: null pointer");
     GI_HIP(ctx, gi_harvest_results(g, false));
     // ---- everything the HOST can refuse the call for comes before anything changes (the vertices themselves: deform_check_kernel) ----
-    struct Span { uint32_t geom, first, count, k; };
-    std::vector<Span> spans;
-    spans.reserve(n);
-    size_t n_lanes = 0;
-    for (uint32_t k = 0; k < n; ++k) {
-        const neb_vertex_update& u = updates[k];
-        if (!u.positions)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: null positions");
-        if (u.geometry >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: geometry index out of range");
-        const GiState::HostGeom& hg = g->h_geoms[u.geometry];
-        if ((uint64_t)u.firstVertex + u.numVertices > hg.n_verts)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: vertex range beyond the geometry's numVertices");
-        if ((u.normals || u.tangents) && !hg.valid)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: normals or tangents for a geometry that was set without its attribute streams");
-        if (u.positionStride < 12u || (u.normals && u.normalStride < 12u) || (u.tangents && u.tangentStride < 16u))
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: a stride is smaller than its element");
-        if ((((uintptr_t)u.positions | u.positionStride) & 3u) || (u.normals && (((uintptr_t)u.normals | u.normalStride) & 3u)) ||
-            (u.tangents && (((uintptr_t)u.tangents | u.tangentStride) & 3u)))
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: a pointer or a stride is not a multiple of 4");
-        if (u.numVertices == 0)
-            continue;
-        spans.push_back({u.geometry, u.firstVertex, u.numVertices, k});
-        n_lanes += u.numVertices;
-    }
-    std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom != b.geom ? a.geom < b.geom : a.first < b.first; });
-    for (size_t i = 1; i < spans.size(); ++i)
-        if (spans[i].geom == spans[i - 1].geom && (uint64_t)spans[i - 1].first + spans[i - 1].count > spans[i].first)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: two ranges of one geometry overlap");
-    if (n_lanes > 0xffffffffull / 10u) // (the bound of neb_gi_update_vertices: lanes are 32-bit)
-        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_update_vertices_device: too many vertices in one call");
+    std::vector<VertexSpan> spans;
+    size_t n_lanes, n_nrm, n_tan;
+    if (int rc = collect_vertex_spans(ctx, g, updates, n, who, true, spans, n_lanes, n_nrm, n_tan); rc != NEB_OK)
+        return rc;
     if (spans.empty())
         return NEB_OK; // every range is empty: nothing moves, nothing is enqueued, the sun table stays
-    hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
-    for (const Span& sp : spans) { // a host pointer handed in by mistake would fault the device: every source is looked up first
+    for (const VertexSpan& sp : spans) { // a host pointer handed in by mistake would fault the device: every source is looked up first
         const neb_vertex_update& u = updates[sp.k];
         const size_t last = (size_t)sp.count - 1u;
         if (!device_readable(ctx, u.positions, last * u.positionStride + 12u) || (u.normals && !device_readable(ctx, u.normals, last * u.normalStride + 12u)) ||
@@ -1572,28 +1634,20 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
     const size_t head = (spans.size() * sizeof(GiState::DeformRange) + 15u) & ~(size_t)15u;
     const size_t bytes = head + spans.size() * sizeof(GiState::DeformSource);
     GI_HIP(ctx, vstage_reserve(g, bytes, bytes));
-    const uint32_t call = g->epoch + 1u;
-    int slot = 0;
-    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
-    GI_HIP(ctx, results_acquire(g, slot));
-    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+    UpdateCall uc{ctx, g, (hipStream_t)stream_, true};
+    if (int rc = update_begin(uc, true); rc != NEB_OK)
         return rc;
     // ---- commit the host side: the slot; h_pos is left behind (host_stale), the boxes follow with the result record ----
-    g->epoch = call;
-    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)uc.slot * g->vstage_cap;
     GiState::DeformRange* ranges = (GiState::DeformRange*)base;
     GiState::DeformSource* sources = (GiState::DeformSource*)(base + head);
-    uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
-    GiState::ResultRecord& rec = g->result_rec[slot];
-    rec.geoms.clear();
     uint32_t lane = 0;
-    bool any_tris = false, any_attr = false;
+    bool any_attr = false;
     for (size_t i = 0; i < spans.size(); ++i) {
-        const Span& sp = spans[i];
+        const VertexSpan& sp = spans[i];
         const neb_vertex_update& u = updates[sp.k];
-        GiState::HostGeom& hg = g->h_geoms[sp.geom];
         GiState::DeformRange& r = ranges[i];
-        r.first_lane = lane, r.count = sp.count, r.dst = hg.vertexBase + sp.first, r.geom = sp.geom, r.pad = 0;
+        r.first_lane = lane, r.count = sp.count, r.dst = g->h_geoms[sp.geom].vertexBase + sp.first, r.geom = sp.geom, r.pad = 0;
         roll_mark(g, sp.geom, sp.first, sp.count); // (the host cannot know of a refusal on the device: the roll then copies equal values)
         r.pos_off = 0;
         r.nrm_off = u.normals ? 0u : GiState::kNoStream; // (device sources: only "has the stream" is read)
@@ -1601,42 +1655,29 @@ int neb_gi_update_vertices_device(neb_ctx* ctx, const neb_vertex_update* updates
         sources[i] = {(const uint8_t*)u.positions, (const uint8_t*)u.normals, (const uint8_t*)u.tangents, u.positionStride, u.normalStride, u.tangentStride, 0u};
         lane += sp.count;
         any_attr = any_attr || u.normals || u.tangents;
-        hg.host_stale = true;
-        if (hg.n_tris) {
-            hg.dirty = true;
-            any_tris = true;
-            if (rec.geoms.empty() || rec.geoms.back() != sp.geom) {
-                list[rec.geoms.size()] = sp.geom;
-                rec.geoms.push_back(sp.geom);
-            }
-        }
+        update_touch(uc, sp.geom);
     }
-    if (any_tris)
+    if (uc.any_tris)
         refit_drop_sun_table(g);
     // ---- enqueue: check, scatter, bake, records, boxes, levels, quantise, the record back ----
-    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3), n_boxed = (uint32_t)rec.geoms.size();
-    uint32_t* d_res = g->d_result + (size_t)slot * result_stride(g);
-    GI_HIP(ctx, results_enqueue_init(g, slot, call, n_boxed, stream));
-    hipLaunchKernelGGL(deform_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)ranges, n_ranges,
-                       (const GiState::DeformSource*)sources, lane, g->n_geoms, (const float*)g->d_xf, d_res + 1);
-    hipLaunchKernelGGL(deform_scatter_kernel<true>, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)ranges, n_ranges,
-                       (const float*)nullptr, lane, n_pool, g->n_geoms, call, g->d_pos, const_cast<float*>(g->view.normals),
-                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)sources, (const uint32_t*)(d_res + 1),
+    const uint32_t n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
+    uint32_t* refused = result_refusal_word(g, uc.slot);
+    GI_HIP(ctx, update_record_init(uc));
+    hipLaunchKernelGGL(deform_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)ranges, n_ranges,
+                       (const GiState::DeformSource*)sources, lane, g->n_geoms, (const float*)g->d_xf, refused);
+    hipLaunchKernelGGL(deform_scatter_kernel<true>, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)ranges, n_ranges,
+                       (const float*)nullptr, lane, n_pool, g->n_geoms, uc.call, g->d_pos, const_cast<float*>(g->view.normals),
+                       const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const GiState::DeformSource*)sources, (const uint32_t*)refused,
                        g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
-    if (any_tris && n_slots) {
-        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, any_attr, n_boxed, stream));
-    }
-    GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
-    GI_HIP(ctx, mark_rewrite(g, stream));
-    return NEB_OK;
+    GI_HIP(ctx, stage_slot_release(g, uc.slot, uc.stream));
+    return update_finish(uc, any_attr);
 }
 
 // ---- skinned submeshes ----
 int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_stream stream_)
 {
+    static const char who[] = "neb_gi_set_skin";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -1651,13 +1692,11 @@ int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_st
     // ---- everything that can refuse the call comes before anything changes ----
     const uint32_t stamp = ++g->seen_stamp;
     uint32_t n_skins = g->n_skins, n_joints = g->skin_joints;
+    std::vector<size_t> block_bytes(n, 0); // (64 bytes per vertex: GiState::Skin)
     for (uint32_t k = 0; k < n; ++k) {
         const neb_skin_desc& d = skins[k];
-        if (d.geometry >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: geometry index out of range");
-        if (g->h_seen[d.geometry] == stamp)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: a geometry is named twice");
-        g->h_seen[d.geometry] = stamp;
+        if (int rc = geometry_named_once(ctx, g, stamp, d.geometry, who, NEB_ERR_INVALID_ARG); rc != NEB_OK)
+            return rc;
         if (!g->skins.empty() && g->skins[d.geometry].n_joints)
             n_skins -= 1u, n_joints -= g->skins[d.geometry].n_joints;
         if (!d.joints)
@@ -1670,6 +1709,7 @@ int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_st
             return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_skin: a stride is smaller than its element");
         n_skins += 1u, n_joints += d.numJoints;
         const uint32_t nv = g->h_geoms[d.geometry].n_verts;
+        block_bytes[k] = std::max<size_t>(64, (size_t)64 * nv);
         for (uint32_t v = 0; v < nv; ++v) {
             uint16_t j4[4];
             float w4[4];
@@ -1685,37 +1725,22 @@ int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_st
     }
     hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
-    // ---- what the call needs is allocated before anything is let go of ----
-    std::vector<void*> fresh(n, nullptr);
-    void* fresh_args = nullptr;
-    const size_t args_cap = GiState::args_capacity(n_skins, n_joints, g->n_morphs, g->morph_targets); // (the buffer is shared with the morph calls)
-    hipError_t e = hipSuccess;
-    for (uint32_t k = 0; k < n && e == hipSuccess; ++k)
-        if (skins[k].joints)
-            e = hipMalloc(&fresh[k], std::max<size_t>(64, (size_t)64 * g->h_geoms[skins[k].geometry].n_verts));
-    if (e == hipSuccess && args_cap && args_cap != g->skin_args_cap)
-        e = hipMalloc(&fresh_args, args_cap);
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize(); // (a set-up call: a skin call still in flight reads the blocks and the palette buffer about to be replaced)
-    // Everything that can still fail fills the FRESH blocks: joints and weights repacked tight, and the bind pose -- read behind a rewrite
-    // enqueued on another stream (gi_scene_reader; a later rewrite waits for the copies).  Nothing of the context has changed yet.
-    if (e == hipSuccess)
-        e = gi_scene_reader(g, stream);
+    // the fresh blocks: joints and weights repacked tight, and the bind pose from the pools (the buffer of arguments is shared with the morph calls)
+    std::vector<void*> fresh;
     std::vector<uint16_t> hj;
     std::vector<float> hw;
-    for (uint32_t k = 0; k < n && e == hipSuccess; ++k) {
+    const auto fill = [&](uint32_t k, uint8_t* b) {
         const neb_skin_desc& d = skins[k];
         const GiState::HostGeom& hg = g->h_geoms[d.geometry];
         const size_t nv = hg.n_verts;
-        if (!d.joints || !nv)
-            continue;
+        if (!nv)
+            return hipSuccess;
         hj.resize(4 * nv), hw.resize(4 * nv);
         for (size_t v = 0; v < nv; ++v) {
             memcpy(&hj[4 * v], (const uint8_t*)d.joints + v * d.jointStride, 8);
             memcpy(&hw[4 * v], (const uint8_t*)d.weights + v * d.weightStride, 16);
         }
-        uint8_t* b = (uint8_t*)fresh[k];
-        e = hipMemcpy(b, hw.data(), 16 * nv, hipMemcpyHostToDevice);
+        hipError_t e = hipMemcpy(b, hw.data(), 16 * nv, hipMemcpyHostToDevice);
         if (e == hipSuccess)
             e = hipMemcpy(b + 32 * nv, hj.data(), 8 * nv, hipMemcpyHostToDevice);
         if (e == hipSuccess)
@@ -1724,40 +1749,26 @@ int neb_gi_set_skin(neb_ctx* ctx, const neb_skin_desc* skins, uint32_t n, neb_st
             e = hipMemcpyAsync(b + 52 * nv, g->view.normals + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess)
             e = hipMemcpyAsync(b + 16 * nv, g->view.tangents + 4 * (size_t)hg.vertexBase, 16 * nv, hipMemcpyDeviceToDevice, stream);
-    }
-    if (e != hipSuccess) {
-        for (void* p : fresh)
-            if (p)
-                (void)hipFree(p); // (waits for the device: a copy into the block that was enqueued is done)
-        if (fresh_args)
-            (void)hipFree(fresh_args);
-        return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_skin: device memory", e);
-    }
+        return e;
+    };
+    if (int rc = setup_fresh_blocks(ctx, g, stream, who, block_bytes, GiState::args_capacity(n_skins, n_joints, g->n_morphs, g->morph_targets), fresh, fill);
+        rc != NEB_OK)
+        return rc;
     // ---- commit: nothing below can fail ----
     if (g->skins.empty())
         g->skins.resize(g->n_geoms);
-    if (args_cap != g->skin_args_cap) {
-        if (g->d_skin_args)
-            (void)hipFree(g->d_skin_args);
-        g->d_skin_args = fresh_args;
-        g->skin_args_cap = args_cap;
-    }
     g->n_skins = n_skins, g->skin_joints = n_joints;
     for (uint32_t k = 0; k < n; ++k) {
-        GiState::Skin& sk = g->skins[skins[k].geometry];
-        if (sk.d_block)
-            (void)hipFree(sk.d_block);
-        sk = GiState::Skin();
-        if (skins[k].joints) {
-            sk.d_block = fresh[k];
+        GiState::Skin& sk = rebind_block(g->skins, skins[k].geometry, fresh[k]);
+        if (fresh[k])
             sk.n_joints = skins[k].numJoints;
-        }
     }
     return NEB_OK;
 }
 
 int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t n, neb_stream stream_)
 {
+    static const char who[] = "neb_gi_skin_vertices";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -1778,11 +1789,8 @@ int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t 
     size_t n_lanes = 0, n_mats = 0;
     for (uint32_t k = 0; k < n; ++k) {
         const neb_skin_update& u = updates[k];
-        if (u.geometry >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: geometry index out of range");
-        if (g->h_seen[u.geometry] == stamp)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: a geometry is named twice");
-        g->h_seen[u.geometry] = stamp;
+        if (int rc = geometry_named_once(ctx, g, stamp, u.geometry, who, NEB_ERR_INVALID_ARG); rc != NEB_OK)
+            return rc;
         if (!u.jointMatrices)
             return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_skin_vertices: null jointMatrices");
         if (g->skins.empty() || !g->skins[u.geometry].n_joints)
@@ -1791,9 +1799,8 @@ int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t 
     for (uint32_t k = 0; k < n; ++k) {
         const neb_skin_update& u = updates[k];
         const uint32_t nj = g->skins[u.geometry].n_joints;
-        for (uint32_t q = 0; q < 16u * nj; ++q)
-            if ((q & 3u) != 3u && !std::isfinite(u.jointMatrices[q]))
-                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_skin_vertices: a joint matrix entry (columns 0-2) is not a finite number");
+        if (!palette_finite(u.jointMatrices, nj))
+            return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_skin_vertices: a joint matrix entry (columns 0-2) is not a finite number");
         if (g->h_geoms[u.geometry].n_verts == 0)
             continue; // (no lane: a range is never empty)
         spans.push_back({u.geometry, k});
@@ -1805,7 +1812,6 @@ int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t 
     if (spans.empty())
         return NEB_OK;
     std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom < b.geom; });
-    hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
     GI_HIP(ctx, results_prepare(g));
     // ---- the staging slot: pinned host memory, {ranges | sources | palettes}, copied to the palette buffer in one piece ----
@@ -1815,69 +1821,50 @@ int neb_gi_skin_vertices(neb_ctx* ctx, const neb_skin_update* updates, uint32_t 
     if (bytes > g->skin_args_cap)
         return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_skin_vertices: the palette buffer is smaller than the call (internal)");
     GI_HIP(ctx, vstage_reserve(g, bytes, std::max(bytes, g->skin_args_cap))); // (at once for a call that names every skin)
-    const uint32_t call = g->epoch + 1u;
-    int slot = 0;
-    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
-    GI_HIP(ctx, results_acquire(g, slot));
-    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+    UpdateCall uc{ctx, g, (hipStream_t)stream_, true};
+    if (int rc = update_begin(uc, true); rc != NEB_OK)
         return rc;
     // ---- commit the host side: the slot; h_pos is left behind (host_stale), the boxes follow with the result record ----
-    g->epoch = call;
-    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)uc.slot * g->vstage_cap;
     GiState::DeformRange* ranges = (GiState::DeformRange*)base;
     GiState::SkinSource* sources = (GiState::SkinSource*)(base + head);
     float* palette = (float*)(base + head + src_bytes);
-    uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
-    GiState::ResultRecord& rec = g->result_rec[slot];
-    rec.geoms.clear();
     uint32_t lane = 0, mat = 0;
-    bool any_tris = false;
     for (size_t i = 0; i < spans.size(); ++i) {
         const uint32_t gi = spans[i].geom;
-        GiState::HostGeom& hg = g->h_geoms[gi];
+        const GiState::HostGeom& hg = g->h_geoms[gi];
         const GiState::Skin& sk = g->skins[gi];
         ranges[i] = {lane, hg.n_verts, hg.vertexBase, gi, 0u, hg.valid ? 0u : GiState::kNoStream, hg.valid ? 0u : GiState::kNoStream, 0u};
         sources[i] = {(const uint8_t*)sk.d_block, hg.n_verts, mat, sk.n_joints, hg.valid ? 1u : 0u, {0u, 0u}};
         memcpy(palette + 16 * (size_t)mat, updates[spans[i].k].jointMatrices, 64 * (size_t)sk.n_joints);
         roll_mark(g, gi, 0, hg.n_verts); // (the host cannot know of a refusal on the device: the roll then copies equal values)
         lane += hg.n_verts, mat += sk.n_joints;
-        hg.host_stale = true;
-        if (hg.n_tris) {
-            hg.dirty = true;
-            any_tris = true;
-            list[rec.geoms.size()] = gi;
-            rec.geoms.push_back(gi);
-        }
+        update_touch(uc, gi);
     }
-    if (any_tris)
+    if (uc.any_tris)
         refit_drop_sun_table(g);
     // ---- enqueue: arguments, check, skin, bake, records, boxes, levels, quantise, the record back ----
-    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3), n_boxed = (uint32_t)rec.geoms.size();
-    uint32_t* d_res = g->d_result + (size_t)slot * result_stride(g);
+    const uint32_t n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
+    uint32_t* refused = result_refusal_word(g, uc.slot);
     const uint8_t* d_args = (const uint8_t*)g->d_skin_args;
-    GI_HIP(ctx, results_enqueue_init(g, slot, call, n_boxed, stream));
-    GI_HIP(ctx, hipMemcpyAsync(g->d_skin_args, base, bytes, hipMemcpyHostToDevice, stream));
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
-    hipLaunchKernelGGL(skin_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+    GI_HIP(ctx, update_record_init(uc));
+    GI_HIP(ctx, hipMemcpyAsync(g->d_skin_args, base, bytes, hipMemcpyHostToDevice, uc.stream));
+    GI_HIP(ctx, stage_slot_release(g, uc.slot, uc.stream)); // (the copy was the slot's last reader: the kernels read the device buffer)
+    hipLaunchKernelGGL(skin_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)d_args, n_ranges,
                        (const GiState::SkinSource*)(d_args + head), (const float*)(d_args + head + src_bytes), lane, g->n_geoms, (const float*)g->d_xf,
-                       d_res + 1);
-    hipLaunchKernelGGL(skin_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
-                       (const GiState::SkinSource*)(d_args + head), (const float*)(d_args + head + src_bytes), lane, n_pool, g->n_geoms, call, g->d_pos,
-                       const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)(d_res + 1),
+                       refused);
+    hipLaunchKernelGGL(skin_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)d_args, n_ranges,
+                       (const GiState::SkinSource*)(d_args + head), (const float*)(d_args + head + src_bytes), lane, n_pool, g->n_geoms, uc.call, g->d_pos,
+                       const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)refused,
                        g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
-    if (any_tris && n_slots) {
-        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, true, n_boxed, stream));
-    }
-    GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
-    GI_HIP(ctx, mark_rewrite(g, stream));
-    return NEB_OK;
+    return update_finish(uc, true);
 }
 
 // ---- morph targets ----
 int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t n, neb_stream stream_)
 {
+    static const char who[] = "neb_gi_set_morph_targets";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -1894,11 +1881,8 @@ int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t
     uint32_t n_morphs = g->n_morphs, n_targets = g->morph_targets;
     for (uint32_t k = 0; k < n; ++k) {
         const neb_morph_desc& d = descs[k];
-        if (d.geometry >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: geometry index out of range");
-        if (g->h_seen[d.geometry] == stamp)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_set_morph_targets: a geometry is named twice");
-        g->h_seen[d.geometry] = stamp;
+        if (int rc = geometry_named_once(ctx, g, stamp, d.geometry, who, NEB_ERR_INVALID_ARG); rc != NEB_OK)
+            return rc;
         if (!g->morphs.empty() && g->morphs[d.geometry].n_targets)
             n_morphs -= 1u, n_targets -= g->morphs[d.geometry].n_targets;
         if (d.numTargets == 0)
@@ -1918,6 +1902,7 @@ int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t
     }
     // the deltas repacked tight and target-major, {positions | normals | tangents}, and looked at on the way
     std::vector<std::vector<float>> packed(n);
+    std::vector<size_t> block_bytes(n, 0); // (the rest pose, 40 bytes per vertex, then the deltas: GiState::Morph)
     for (uint32_t k = 0; k < n; ++k) {
         const neb_morph_desc& d = descs[k];
         if (d.numTargets == 0)
@@ -1927,6 +1912,7 @@ int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t
         const uint32_t strides[3] = {d.positionStride, d.normalStride, d.tangentStride};
         std::vector<float>& out = packed[k];
         out.resize(3 * nv * d.numTargets * (1u + (d.normalDeltas ? 1u : 0u) + (d.tangentDeltas ? 1u : 0u)));
+        block_bytes[k] = std::max<size_t>(64, (size_t)40 * nv + out.size() * sizeof(float));
         float* dst = out.data();
         for (int q = 0; q < 3; ++q) {
             if (!streams[q])
@@ -1941,61 +1927,32 @@ int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t
     }
     hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
-    // ---- what the call needs is allocated before anything is let go of ----
-    std::vector<void*> fresh(n, nullptr);
-    void* fresh_args = nullptr;
-    const size_t args_cap = GiState::args_capacity(g->n_skins, g->skin_joints, n_morphs, n_targets);
-    hipError_t e = hipSuccess;
-    for (uint32_t k = 0; k < n && e == hipSuccess; ++k)
-        if (descs[k].numTargets)
-            e = hipMalloc(&fresh[k], std::max<size_t>(64, (size_t)40 * g->h_geoms[descs[k].geometry].n_verts + packed[k].size() * sizeof(float)));
-    if (e == hipSuccess && args_cap && args_cap != g->skin_args_cap)
-        e = hipMalloc(&fresh_args, args_cap);
-    if (e == hipSuccess)
-        e = hipDeviceSynchronize(); // (a set-up call: a call still in flight reads the blocks and the argument buffer about to be replaced)
-    // Everything that can still fail fills the FRESH blocks: the deltas, and the rest pose -- read behind a rewrite enqueued on another
-    // stream (gi_scene_reader; a later rewrite waits for the copies).  Nothing of the context has changed yet.
-    if (e == hipSuccess)
-        e = gi_scene_reader(g, stream);
-    for (uint32_t k = 0; k < n && e == hipSuccess; ++k) {
+    // the fresh blocks: the deltas, and the rest pose from the pools
+    std::vector<void*> fresh;
+    const auto fill = [&](uint32_t k, uint8_t* b) {
         const GiState::HostGeom& hg = g->h_geoms[descs[k].geometry];
         const size_t nv = hg.n_verts;
-        if (!descs[k].numTargets || !nv)
-            continue;
-        uint8_t* b = (uint8_t*)fresh[k];
-        e = hipMemcpy(b + 40 * nv, packed[k].data(), packed[k].size() * sizeof(float), hipMemcpyHostToDevice);
+        if (!nv)
+            return hipSuccess;
+        hipError_t e = hipMemcpy(b + 40 * nv, packed[k].data(), packed[k].size() * sizeof(float), hipMemcpyHostToDevice);
         if (e == hipSuccess)
             e = hipMemcpyAsync(b, g->view.tangents + 4 * (size_t)hg.vertexBase, 16 * nv, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess)
             e = hipMemcpyAsync(b + 16 * nv, g->d_pos + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
         if (e == hipSuccess)
             e = hipMemcpyAsync(b + 28 * nv, g->view.normals + 3 * (size_t)hg.vertexBase, 12 * nv, hipMemcpyDeviceToDevice, stream);
-    }
-    if (e != hipSuccess) {
-        for (void* p : fresh)
-            if (p)
-                (void)hipFree(p); // (waits for the device: a copy into the block that was enqueued is done)
-        if (fresh_args)
-            (void)hipFree(fresh_args);
-        return gi_fail(ctx, NEB_ERR_HIP, "neb_gi_set_morph_targets: device memory", e);
-    }
+        return e;
+    };
+    if (int rc = setup_fresh_blocks(ctx, g, stream, who, block_bytes, GiState::args_capacity(g->n_skins, g->skin_joints, n_morphs, n_targets), fresh, fill);
+        rc != NEB_OK)
+        return rc;
     // ---- commit: nothing below can fail ----
     if (g->morphs.empty())
         g->morphs.resize(g->n_geoms);
-    if (args_cap != g->skin_args_cap) {
-        if (g->d_skin_args)
-            (void)hipFree(g->d_skin_args);
-        g->d_skin_args = fresh_args;
-        g->skin_args_cap = args_cap;
-    }
     g->n_morphs = n_morphs, g->morph_targets = n_targets;
     for (uint32_t k = 0; k < n; ++k) {
-        GiState::Morph& mo = g->morphs[descs[k].geometry];
-        if (mo.d_block)
-            (void)hipFree(mo.d_block);
-        mo = GiState::Morph();
-        if (descs[k].numTargets) {
-            mo.d_block = fresh[k];
+        GiState::Morph& mo = rebind_block(g->morphs, descs[k].geometry, fresh[k]);
+        if (fresh[k]) {
             mo.n_targets = descs[k].numTargets;
             mo.has_n = descs[k].normalDeltas != nullptr, mo.has_t = descs[k].tangentDeltas != nullptr;
         }
@@ -2005,6 +1962,7 @@ int neb_gi_set_morph_targets(neb_ctx* ctx, const neb_morph_desc* descs, uint32_t
 
 int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_t n, neb_stream stream_)
 {
+    static const char who[] = "neb_gi_morph_vertices";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -2025,11 +1983,8 @@ int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_
     size_t n_lanes = 0, n_mats = 0, n_active = 0;
     for (uint32_t k = 0; k < n; ++k) {
         const neb_morph_update& u = updates[k];
-        if (u.geometry >= g->n_geoms)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: geometry index out of range");
-        if (g->h_seen[u.geometry] == stamp)
-            return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: a geometry is named twice");
-        g->h_seen[u.geometry] = stamp;
+        if (int rc = geometry_named_once(ctx, g, stamp, u.geometry, who, NEB_ERR_INVALID_ARG); rc != NEB_OK)
+            return rc;
         if (!u.weights)
             return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_morph_vertices: null weights");
         if (g->morphs.empty() || !g->morphs[u.geometry].n_targets)
@@ -2046,9 +2001,8 @@ int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_
                 return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_morph_vertices: a weight is not a finite number");
             active += u.weights[t] != 0.f ? 1u : 0u; // (+0 and -0 both drop out)
         }
-        for (uint32_t q = 0; q < 16u * nj; ++q)
-            if ((q & 3u) != 3u && !std::isfinite(u.jointMatrices[q]))
-                return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_morph_vertices: a joint matrix entry (columns 0-2) is not a finite number");
+        if (!palette_finite(u.jointMatrices, nj))
+            return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_morph_vertices: a joint matrix entry (columns 0-2) is not a finite number");
         if (g->h_geoms[u.geometry].n_verts == 0)
             continue; // (no lane: a range is never empty)
         spans.push_back({u.geometry, k});
@@ -2061,7 +2015,6 @@ int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_
     if (spans.empty())
         return NEB_OK;
     std::sort(spans.begin(), spans.end(), [](const Span& a, const Span& b) { return a.geom < b.geom; });
-    hipStream_t stream = (hipStream_t)stream_;
     GI_GUARD(ctx);
     GI_HIP(ctx, results_prepare(g));
     // ---- the staging slot: pinned host memory, {ranges | sources | active lists | palettes}, copied to the argument buffer in one piece ----
@@ -2073,28 +2026,20 @@ int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_
     if (bytes > g->skin_args_cap)
         return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_morph_vertices: the argument buffer is smaller than the call (internal)");
     GI_HIP(ctx, vstage_reserve(g, bytes, std::max(bytes, g->skin_args_cap))); // (at once for a call that names every geometry)
-    const uint32_t call = g->epoch + 1u;
-    int slot = 0;
-    GI_HIP(ctx, stage_slot_acquire(g, call, &slot));
-    GI_HIP(ctx, results_acquire(g, slot));
-    if (int rc = refit_order_behind_readers(ctx, g, stream); rc != NEB_OK)
+    UpdateCall uc{ctx, g, (hipStream_t)stream_, true};
+    if (int rc = update_begin(uc, true); rc != NEB_OK)
         return rc;
     // ---- commit the host side: the slot; h_pos is left behind (host_stale), the boxes follow with the result record ----
-    g->epoch = call;
-    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)slot * g->vstage_cap;
+    uint8_t* base = (uint8_t*)g->h_vstage + (size_t)uc.slot * g->vstage_cap;
     GiState::DeformRange* ranges = (GiState::DeformRange*)base;
     GiState::MorphSource* sources = (GiState::MorphSource*)(base + head);
     GiState::MorphPair* pairs = (GiState::MorphPair*)(base + head + src_bytes);
     float* palette = (float*)(base + head + src_bytes + act_bytes);
-    uint32_t* list = g->h_box_list + (size_t)slot * g->n_geoms;
-    GiState::ResultRecord& rec = g->result_rec[slot];
-    rec.geoms.clear();
     uint32_t lane = 0, mat = 0, act = 0;
-    bool any_tris = false;
     for (size_t i = 0; i < spans.size(); ++i) {
         const uint32_t gi = spans[i].geom;
         const neb_morph_update& u = updates[spans[i].k];
-        GiState::HostGeom& hg = g->h_geoms[gi];
+        const GiState::HostGeom& hg = g->h_geoms[gi];
         const GiState::Morph& mo = g->morphs[gi];
         const uint32_t nj = u.jointMatrices ? g->skins[gi].n_joints : 0u, act_first = act;
         for (uint32_t t = 0; t < mo.n_targets; ++t)
@@ -2107,41 +2052,29 @@ int neb_gi_morph_vertices(neb_ctx* ctx, const neb_morph_update* updates, uint32_
             memcpy(palette + 16 * (size_t)mat, u.jointMatrices, 64 * (size_t)nj);
         roll_mark(g, gi, 0, hg.n_verts); // (the host cannot know of a refusal on the device: the roll then copies equal values)
         lane += hg.n_verts, mat += nj;
-        hg.host_stale = true;
-        if (hg.n_tris) {
-            hg.dirty = true;
-            any_tris = true;
-            list[rec.geoms.size()] = gi;
-            rec.geoms.push_back(gi);
-        }
+        update_touch(uc, gi);
     }
     if (act_bytes > (size_t)act * sizeof(GiState::MorphPair))
         pairs[act] = {0u, 0.f}; // (the padding travels too)
-    if (any_tris)
+    if (uc.any_tris)
         refit_drop_sun_table(g);
     // ---- enqueue: arguments, check, blend, bake, records, boxes, levels, quantise, the record back ----
-    const uint32_t n_slots = g->view.n_tris, n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3), n_boxed = (uint32_t)rec.geoms.size();
-    uint32_t* d_res = g->d_result + (size_t)slot * result_stride(g);
+    const uint32_t n_ranges = (uint32_t)spans.size(), n_pool = (uint32_t)(g->h_pos.size() / 3);
+    uint32_t* refused = result_refusal_word(g, uc.slot);
     const uint8_t* d_args = (const uint8_t*)g->d_skin_args;
-    GI_HIP(ctx, results_enqueue_init(g, slot, call, n_boxed, stream));
-    GI_HIP(ctx, hipMemcpyAsync(g->d_skin_args, base, bytes, hipMemcpyHostToDevice, stream));
-    GI_HIP(ctx, hipEventRecord(g->stage_ev[slot], stream));
-    g->stage_used[slot] = true;
-    hipLaunchKernelGGL(morph_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+    GI_HIP(ctx, update_record_init(uc));
+    GI_HIP(ctx, hipMemcpyAsync(g->d_skin_args, base, bytes, hipMemcpyHostToDevice, uc.stream));
+    GI_HIP(ctx, stage_slot_release(g, uc.slot, uc.stream)); // (the copy was the slot's last reader: the kernels read the device buffer)
+    hipLaunchKernelGGL(morph_check_kernel, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)d_args, n_ranges,
                        (const GiState::MorphSource*)(d_args + head), (const uint2*)(d_args + head + src_bytes),
-                       (const float*)(d_args + head + src_bytes + act_bytes), lane, g->n_geoms, (const float*)g->d_xf, d_res + 1);
-    hipLaunchKernelGGL(morph_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, stream, (const GiState::DeformRange*)d_args, n_ranges,
+                       (const float*)(d_args + head + src_bytes + act_bytes), lane, g->n_geoms, (const float*)g->d_xf, refused);
+    hipLaunchKernelGGL(morph_scatter_kernel, dim3((lane + 255) / 256), dim3(256), 0, uc.stream, (const GiState::DeformRange*)d_args, n_ranges,
                        (const GiState::MorphSource*)(d_args + head), (const uint2*)(d_args + head + src_bytes),
-                       (const float*)(d_args + head + src_bytes + act_bytes), lane, n_pool, g->n_geoms, call, g->d_pos,
-                       const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)(d_res + 1),
+                       (const float*)(d_args + head + src_bytes + act_bytes), lane, n_pool, g->n_geoms, uc.call, g->d_pos,
+                       const_cast<float*>(g->view.normals), const_cast<float*>(g->view.tangents), g->d_geom_epoch, (const uint32_t*)refused,
                        g->d_deform_dirty);
     GI_HIP(ctx, hipGetLastError());
-    if (any_tris && n_slots) {
-        GI_HIP(ctx, refit_enqueue_rewrite(g, slot, call, true, n_boxed, stream));
-    }
-    GI_HIP(ctx, results_enqueue_readback(g, slot, call, true, stream));
-    GI_HIP(ctx, mark_rewrite(g, stream));
-    return NEB_OK;
+    return update_finish(uc, true);
 }
 
 int neb_gi_download_vertices(neb_ctx* ctx, uint32_t geometry, uint32_t firstVertex, uint32_t numVertices, float* positions, float* normals,
