@@ -290,13 +290,39 @@ struct ShadeOut {
     uint32_t table = 0; // ... answered by the sun table instead of a traversal
 };
 
+// A material's maps at one uv, requested (request_maps) and turned into samples (decode_maps) in two places.  A bundled material's
+// request is the raw 32-byte entry.  One without a bundle pays its dependent fetches where it asks and keeps the eight filtered
+// channels the shaders read, as bits, in the same registers.
+template <bool FAST> __device__ __forceinline__ void request_maps(const SceneView& S, const DevMat& m, float u, float v, BundleFetch& f)
+{
+    if (m.bundle_w != 0) {
+        fetch_bundle(S, m, u, v, f);
+        return;
+    }
+    MapSamples s;
+    sample_material_maps<FAST>(S, m, u, v, s);
+    f.top = make_uint4(__float_as_uint(s.albedo.x), __float_as_uint(s.albedo.y), __float_as_uint(s.albedo.z), __float_as_uint(s.normal.x));
+    f.bot = make_uint4(__float_as_uint(s.normal.y), __float_as_uint(s.normal.z), __float_as_uint(s.rm.y), __float_as_uint(s.rm.z));
+}
+template <bool FAST> __device__ __forceinline__ void decode_maps(const DevMat& m, const BundleFetch& f, MapSamples& s)
+{
+    if (m.bundle_w != 0) {
+        filter_bundle<FAST>(f, s);
+        return;
+    }
+    s.albedo = make_float4(__uint_as_float(f.top.x), __uint_as_float(f.top.y), __uint_as_float(f.top.z), 0.0f);
+    s.normal = make_float4(__uint_as_float(f.top.w), __uint_as_float(f.bot.x), __uint_as_float(f.bot.y), 0.0f);
+    s.rm = make_float4(0.0f, __uint_as_float(f.bot.z), __uint_as_float(f.bot.w), 0.0f);
+}
+
 // Shading of path vertex a.bounce of pixel i, whose bounce ray ended in `h` {t (< 0 miss), u, v, triangle}: miss -> sky; hit ->
 // ReconstructSurfaceData, sun-disk shadow ray + BRDF contribution, and for maxPathVertices > 2 the next bounce ray.
 // FAST: the arithmetic policy of gi_device.h (1-ulp hardware rcp / rsq / sqrt / sin / cos, the forms an HLSL compiler emits);
 // FAST = false is the C arithmetic of the oracle (option "gi_exact_shade", see neb_set_option).
 // The hit triangle's shading record is in LDS at `staged` (gi_shade_kernel), and `pth`, `rd`, `ro` = R.path[i], R.ray_d[i], R.ray_o[i]
 // were loaded beside the hit, before the gather.  A hit pixel's loads wait for one another only where the data do:
-// {hit, path, rays} -> record -> {shade header, first pair of hint triangles} -> texture footprint.
+// {hit, path, rays} -> record -> {shade header, first pair of hint triangles} -> texture footprint (on the last path vertex beside the
+// second pair of hint triangles, and only for the lanes the first pair did not stop).
 template <bool FAST>
 __device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const float4 h, const float4 pth, const float4 rd, const float4 ro, ShadeOut& o,
                                             const float4* staged, uint32_t staged_swz)
@@ -327,7 +353,21 @@ __device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const flo
             ha0 = a.S.tris[3 * h0], hb0 = a.S.tris[3 * h0 + 1], hc0 = a.S.tris[3 * h0 + 2];
             ha1 = a.S.tris[3 * h1], hb1 = a.S.tris[3 * h1 + 1], hc1 = a.S.tris[3 * h1 + 2];
         }
-        const bool shaded = reconstruct_surface<FAST>(a.S, head, ts, h.y, h.z, surf);
+        // On the LAST path vertex a lane whose shadow ray a hint stops adds nothing and leaves no ray: it needs neither the material's
+        // maps -- the one fetch of this pass that misses every cache -- nor the BRDF.  There the maps are requested behind the first
+        // hint pair's tests, by the lanes those did not stop (beside the second pair's triangles: no round trip more), and decoded
+        // behind the second pair's.  Every lane asks there, also one that has no hint to test: a second place to ask from, in front
+        // of the tests, measured slower (docs/NOTEBOOK.md 10.18).  On any other vertex the next bounce needs albedo, metalness and SN
+        // whatever the sun query gives: the maps are sampled here, as ever.
+        const bool last_vertex = a.bounce + 1 >= a.c.maxPathVertices;
+        float tex_u = 0.f, tex_v = 0.f;
+        const bool shaded = reconstruct_geometry<FAST>(head, ts, h.y, h.z, surf, tex_u, tex_v);
+        BundleFetch maps_req = {make_uint4(0u, 0u, 0u, 0u), make_uint4(0u, 0u, 0u, 0u), 0.f, 0.f};
+        if (shaded && !last_vertex) {
+            MapSamples maps;
+            sample_material_maps<FAST>(a.S, head.mat, tex_u, tex_v, maps);
+            reconstruct_material<FAST>(head.mat, ts, h.y, h.z, maps, surf);
+        }
         dbg.t = h.x;
         dbg.geometry = ts.geom;
         if (a.hits)
@@ -351,32 +391,38 @@ __device__ __forceinline__ void shade_pixel(const GiArgs& a, size_t i, const flo
             const float3 inc = normalize3<false>(L + (Bv * sn_a + T * cs_a) * a.c.sunTanHalfAngle * dist);
             const bool transition = dot3(surf.GN, inc) <= 0.0f;
             const float3 so = hitP + (transition ? -surf.GN : surf.GN) * 1e-2f;
-            const float3 O = evaluate_direct_brdf<FAST>(surf, V, L) * sun_rad * throughput; // :573-574
             o.rays = 1;
             const uint32_t side = transition ? 1u : 0u;
+            // Occluder hints: the (up to) four triangles that together shadow most of this triangle (chosen once per sun
+            // position).  They are tried with the traverser's own test on the very ray the shadow pass would walk -- same
+            // operands, same arithmetic -- so a hit is a hit of the any-hit traversal too: "occluded", exactly, without the
+            // walk.  Two at a time: the second pair is only fetched by the lanes the first pair did not stop.
+            static_assert(kHints == 4, "two pairs of hints");
+            const bool hinted = a.sun_table && !((ts.lit >> side) & 1u) && ts.hint_side == side && ts.hint[0] != kNoHint && a.hint_pairs >= 1u;
             bool hinted_hit = false;
-            if (a.sun_table && !((ts.lit >> side) & 1u) && ts.hint_side == side && ts.hint[0] != kNoHint) {
-                // Occluder hints: the (up to) four triangles that together shadow most of this triangle (chosen once per sun
-                // position).  They are tried with the traverser's own test on the very ray the shadow pass would walk -- same
-                // operands, same arithmetic -- so a hit is a hit of the any-hit traversal too: "occluded", exactly, without the
-                // walk.  Two at a time: the second pair is only fetched by the lanes the first pair did not stop.
-                float tt, uu, vv;
-#pragma unroll
-                for (int pair = 0; pair < kHints && !hinted_hit; pair += 2) {
-                    const uint32_t h0 = ts.hint[pair];
-                    if (h0 == kNoHint || (uint32_t)pair >= 2u * a.hint_pairs)
-                        break;
-                    if (pair == 0) { // (fetched beside the header; every lane that gets here has them)
-                        hinted_hit = intersect_tri_regs(ha0, hb0, hc0, so, inc, 0.001f, kTraceMax, tt, uu, vv) ||
-                                     intersect_tri_regs(ha1, hb1, hc1, so, inc, 0.001f, kTraceMax, tt, uu, vv);
-                        continue;
-                    }
-                    const uint32_t h1 = ts.hint[pair + 1] != kNoHint ? ts.hint[pair + 1] : h0;
-                    const float4 a0 = a.S.tris[3 * h0], b0 = a.S.tris[3 * h0 + 1], c0 = a.S.tris[3 * h0 + 2];
-                    const float4 a1 = a.S.tris[3 * h1], b1 = a.S.tris[3 * h1 + 1], c1 = a.S.tris[3 * h1 + 2];
-                    hinted_hit = intersect_tri_regs(a0, b0, c0, so, inc, 0.001f, kTraceMax, tt, uu, vv) ||
-                                 intersect_tri_regs(a1, b1, c1, so, inc, 0.001f, kTraceMax, tt, uu, vv);
+            float tt, uu, vv;
+            if (hinted) // (fetched beside the header; every lane that gets here has them)
+                hinted_hit = intersect_tri_regs(ha0, hb0, hc0, so, inc, 0.001f, kTraceMax, tt, uu, vv) ||
+                             intersect_tri_regs(ha1, hb1, hc1, so, inc, 0.001f, kTraceMax, tt, uu, vv);
+            const bool second_pair = hinted && !hinted_hit && ts.hint[2] != kNoHint && a.hint_pairs >= 2u;
+            if (second_pair) {
+                const uint32_t h0 = ts.hint[2], h1 = ts.hint[3] != kNoHint ? ts.hint[3] : h0;
+                ha0 = a.S.tris[3 * h0], hb0 = a.S.tris[3 * h0 + 1], hc0 = a.S.tris[3 * h0 + 2];
+                ha1 = a.S.tris[3 * h1], hb1 = a.S.tris[3 * h1 + 1], hc1 = a.S.tris[3 * h1 + 2];
+            }
+            if (last_vertex && !hinted_hit) // (a lane the second pair then stops has fetched for nothing)
+                request_maps<FAST>(a.S, head.mat, tex_u, tex_v, maps_req);
+            if (second_pair)
+                hinted_hit = intersect_tri_regs(ha0, hb0, hc0, so, inc, 0.001f, kTraceMax, tt, uu, vv) ||
+                             intersect_tri_regs(ha1, hb1, hc1, so, inc, 0.001f, kTraceMax, tt, uu, vv);
+            float3 O = f3(0.f, 0.f, 0.f);
+            if (!hinted_hit) {
+                if (last_vertex) {
+                    MapSamples maps;
+                    decode_maps<FAST>(head.mat, maps_req, maps);
+                    reconstruct_material<FAST>(head.mat, ts, h.y, h.z, maps, surf);
                 }
+                O = evaluate_direct_brdf<FAST>(surf, V, L) * sun_rad * throughput; // :573-574
             }
             if (hinted_hit) {
                 o.table = 1; // occluded: nothing is added, no ray

@@ -748,30 +748,46 @@ template <bool FAST = false> __device__ float4 sample_texture(const SceneView& S
 struct MapSamples {
     float4 albedo = {0.f, 0.f, 0.f, 0.f}, normal = {0.f, 0.f, 0.f, 0.f}, rm = {0.f, 0.f, 0.f, 0.f};
 };
+// One entry of a material's interleaved footprint table, requested (fetch_bundle) and filtered (filter_bundle) in two steps, so
+// that a caller may put other work -- or a reason not to filter at all -- between the request and the use.
+struct BundleFetch {
+    uint4 top, bot; // {t00.lo, t00.hi, t10.lo, t10.hi}, {t01.lo, t01.hi, t11.lo, t11.hi}
+    float fx, fy;
+};
+__device__ __forceinline__ void fetch_bundle(const SceneView& S, const DevMat& m, float u, float v, BundleFetch& f)
+{
+    int x0, y0;
+    texel_position(m.bundle_w, m.bundle_h, u, v, x0, y0, f.fx, f.fy);
+    // one 32-byte entry: the four texels of the footprint, 8 bytes each {albedo.rgb, normal.rgb, roughness (rm.g), metalness (rm.b)}
+    // -- the eight channels the shaders read (alpha and rm.r are never sampled); same UNORM8 values, same filter arithmetic
+    const uint4* e = S.bundles + 2 * ((size_t)m.bundle + (size_t)y0 * m.bundle_w + x0);
+    f.top = e[0], f.bot = e[1];
+}
+template <bool FAST = false> __device__ __forceinline__ void filter_bundle(const BundleFetch& f, MapSamples& out)
+{
+    const uint4 top = f.top, bot = f.bot;
+    const float fx = f.fx, fy = f.fy;
+    float ch[8];
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        auto un = [&](uint32_t lo, uint32_t hi) {
+            const float q = (float)(((c < 4 ? lo : hi) >> (8 * (c & 3))) & 0xffu);
+            return FAST ? q * (1.0f / 255.0f) : q / 255.0f;
+        };
+        const float a = un(top.x, top.y), b = un(top.z, top.w), cc = un(bot.x, bot.y), dd = un(bot.z, bot.w);
+        const float tp = a + fx * (b - a), bt = cc + fx * (dd - cc);
+        ch[c] = tp + fy * (bt - tp);
+    }
+    out.albedo = make_float4(ch[0], ch[1], ch[2], 0.0f);
+    out.normal = make_float4(ch[3], ch[4], ch[5], 0.0f);
+    out.rm = make_float4(0.0f, ch[6], ch[7], 0.0f);
+}
 template <bool FAST = false> __device__ __forceinline__ void sample_material_maps(const SceneView& S, const DevMat& m, float u, float v, MapSamples& out)
 {
     if (m.bundle_w != 0) { // then all three maps exist
-        int x0, y0;
-        float fx, fy;
-        texel_position(m.bundle_w, m.bundle_h, u, v, x0, y0, fx, fy);
-        // one 32-byte entry: the four texels of the footprint, 8 bytes each {albedo.rgb, normal.rgb, roughness (rm.g), metalness (rm.b)}
-        // -- the eight channels the shaders read (alpha and rm.r are never sampled); same UNORM8 values, same filter arithmetic
-        const uint4* e = S.bundles + 2 * ((size_t)m.bundle + (size_t)y0 * m.bundle_w + x0);
-        const uint4 top = e[0], bot = e[1]; // {t00.lo, t00.hi, t10.lo, t10.hi}, {t01.lo, t01.hi, t11.lo, t11.hi}
-        float ch[8];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            auto un = [&](uint32_t lo, uint32_t hi) {
-                const float q = (float)(((c < 4 ? lo : hi) >> (8 * (c & 3))) & 0xffu);
-                return FAST ? q * (1.0f / 255.0f) : q / 255.0f;
-            };
-            const float a = un(top.x, top.y), b = un(top.z, top.w), cc = un(bot.x, bot.y), dd = un(bot.z, bot.w);
-            const float tp = a + fx * (b - a), bt = cc + fx * (dd - cc);
-            ch[c] = tp + fy * (bt - tp);
-        }
-        out.albedo = make_float4(ch[0], ch[1], ch[2], 0.0f);
-        out.normal = make_float4(ch[3], ch[4], ch[5], 0.0f);
-        out.rm = make_float4(0.0f, ch[6], ch[7], 0.0f);
+        BundleFetch f;
+        fetch_bundle(S, m, u, v, f);
+        filter_bundle<FAST>(f, out);
         return;
     }
     if (m.tex[0] >= 0)
@@ -852,8 +868,9 @@ __device__ __forceinline__ ShadeHead load_shade_header(const ShadeHeader* heads,
     return h;
 }
 
-// ReconstructSurfaceData (pathtracer.hlsl:299-395) of a hit on the triangle of record `ts`, whose geometry's header is `g`.
-template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface(const SceneView& S, const ShadeHead& g, const TriShade& ts, float bu, float bv, Surface& out)
+// ReconstructSurfaceData (pathtracer.hlsl:299-395) of a hit on the triangle of record `ts`, whose geometry's header is `g`, in two
+// halves.  The geometry half: the early-outs, GN and the uv the maps are sampled at -- nothing of it touches a texture.
+template <bool FAST = false> __device__ __forceinline__ bool reconstruct_geometry(const ShadeHead& g, const TriShade& ts, float bu, float bv, Surface& out, float& u, float& v)
 {
     const float b0 = 1.0f - (bu + bv), b1 = bu, b2 = bv;
     if (!g.valid)
@@ -861,13 +878,17 @@ template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface
     const float3 n0 = ts.n0, n1 = ts.n1, n2 = ts.n2;
     const float3 gn = normalize3<FAST>(f3(n0.x * b0 + n1.x * b1 + n2.x * b2, n0.y * b0 + n1.y * b1 + n2.y * b2, n0.z * b0 + n1.z * b1 + n2.z * b2));
     out.GN = normalize3<FAST>(xform_dir(g.m, gn)); // :340
-    const float u = ts.uv0.x * b0 + ts.uv1.x * b1 + ts.uv2.x * b2;
-    const float v = ts.uv0.y * b0 + ts.uv1.y * b1 + ts.uv2.y * b2;
+    u = ts.uv0.x * b0 + ts.uv1.x * b1 + ts.uv2.x * b2;
+    v = ts.uv0.y * b0 + ts.uv1.y * b1 + ts.uv2.y * b2;
     if (g.material < 0)
         return false; // :349
-    const DevMat& m = g.mat;
-    MapSamples maps;
-    sample_material_maps<FAST>(S, m, u, v, maps);
+    return true;
+}
+// The material half, from the filtered map samples of (u, v) (sample_material_maps): albedo, the tangent-space normal, roughness and
+// metalness.  out.GN is the geometry half's.
+template <bool FAST = false> __device__ __forceinline__ void reconstruct_material(const DevMat& m, const TriShade& ts, float bu, float bv, const MapSamples& maps, Surface& out)
+{
+    const float b0 = 1.0f - (bu + bv), b1 = bu, b2 = bv;
     if (m.tex[0] < 0) {
         out.albedo = f3(m.albedo[0], m.albedo[1], m.albedo[2]);
     } else {
@@ -900,6 +921,16 @@ template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface
         out.roughness = t.y; // .g
         out.metalness = t.z; // .b
     }
+}
+// Both halves in one call, the maps sampled between them.
+template <bool FAST = false> __device__ __forceinline__ bool reconstruct_surface(const SceneView& S, const ShadeHead& g, const TriShade& ts, float bu, float bv, Surface& out)
+{
+    float u, v;
+    if (!reconstruct_geometry<FAST>(g, ts, bu, bv, out, u, v))
+        return false;
+    MapSamples maps;
+    sample_material_maps<FAST>(S, g.mat, u, v, maps);
+    reconstruct_material<FAST>(g.mat, ts, bu, bv, maps, out);
     return true;
 }
 
