@@ -799,6 +799,22 @@ int neb_gi_debug_set_tile_order(neb_ctx* ctx, const uint32_t* order, uint32_t n)
  * (out[0 .. 5]) and the hint pass (out[6 .. 11]) {node visits of all walks, the longest walk, candidate triangles tested, sum of the waves' run times and
  * the longest wave in 10-ns ticks, waves}.  Synchronises. */
 int neb_gi_debug_sun_walk_stats(neb_ctx* ctx, uint64_t out[12]);
+/* Diagnostics / tests: the sun table as the device holds it.  Copied to host[0 .. *bytes) behind the work of `stream` -- and behind the last
+ * rewrite of the table on whichever stream, as a dispatch on `stream` would be -- in this order: the 128-byte shading records of the n_slots
+ * triangle slots in leaf order (word 27 = the geometry | lit bits << 30, word 28 = the primitive, words 29-31 = four 23-bit occluder hints,
+ * each a slot index or 0x7fffff, and in bit 95 the side they were chosen for), then the 48 bytes per slot the traverser tests
+ * {v0.xyz, e1.x | e1.yz, e2.xy | e2.z, geometry, primitive, -}, then one neb_shade_records_info.  table_valid = 1: the lit bits and hints are
+ * those of (sunLightDirection, sunTanHalfAngle) and the last dispatch used them; 0: no table, or one of another sun or of a scene that has
+ * been updated since (the dispatches ignore it; the fields keep what they held).  lit_plus / lit_minus / hinted: the counters of the last
+ * build (0 without a valid table).  Launches nothing; waits for the copy.  host == NULL or capacity == 0: the size alone.
+ * NEB_ERR_STATE before a successful neb_gi_build_bvh, NEB_ERR_INVALID_ARG when capacity is below the size. */
+typedef struct neb_shade_records_info {
+    uint32_t n_slots, table_valid;
+    float sunLightDirection[3], sunTanHalfAngle;
+    uint32_t builds, reserved;
+    uint64_t lit_plus, lit_minus, hinted;
+} neb_shade_records_info;
+int neb_gi_debug_shade_records(neb_ctx* ctx, void* host, size_t capacity, size_t* bytes, neb_stream stream);
 /* Debug: when option "gi_debug_hits" is 1, every trace also records neb_gi_hit per resident pixel. */
 int neb_gi_download_hits(neb_ctx* ctx, neb_gi_hit* host, neb_stream stream);
 /* Diagnostics / tests: runs the library's ray-reordering sort (raysort.hip: stable LSD radix sort on key bits

@@ -198,6 +198,11 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_debug_texture_tables(m_svgf.Context(), host, capacity, bytes, commandList), "neb_gi_debug_texture_tables");
         }
+        // diagnostics: the shading records (lit bits, hints) in leaf order, the triangles behind them, then one neb_shade_records_info
+        void ShadeRecords(void* host, size_t capacity, size_t* bytes, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_debug_shade_records(m_svgf.Context(), host, capacity, bytes, commandList), "neb_gi_debug_shade_records");
+        }
         // No reference counterpart (its BLASes are built without ALLOW_UPDATE, RTAccelerationStructureBuilder.cpp:79): new object-space
         // vertices for ranges of submeshes -- a swaying drape, a skinned figure --, the tree refitted in place
         void UpdateVertices(const neb_vertex_update* updates, uint32_t n, neb_stream commandList)

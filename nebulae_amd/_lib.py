@@ -147,6 +147,7 @@ def _gi_sigs():
         "neb_gi_update_textures": (C.c_int, [C.c_void_p, C.POINTER(TextureUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_update_textures_device": (C.c_int, [C.c_void_p, C.POINTER(TextureUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_debug_texture_tables": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
+        "neb_gi_debug_shade_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]),
         "neb_gi_update_vertices": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_update_vertices_device": (C.c_int, [C.c_void_p, C.POINTER(VertexUpdate), C.c_uint32, C.c_void_p]),
         "neb_gi_set_skin": (C.c_int, [C.c_void_p, C.POINTER(SkinDesc), C.c_uint32, C.c_void_p]),

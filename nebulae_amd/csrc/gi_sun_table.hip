@@ -648,3 +648,48 @@ hipError_t gi_sun_table_update(GiState* g, const neb_gi_constants& c, hipStream_
 }
 
 } // namespace neb
+
+using namespace neb;
+
+extern "C" {
+
+int neb_gi_debug_shade_records(neb_ctx* ctx, void* host, size_t capacity, size_t* bytes, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built || !g->view.shade || !g->view.tris)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_debug_shade_records: no tree (neb_gi_set_scene and neb_gi_build_bvh first)");
+    static_assert(sizeof(neb_shade_records_info) == 56, "neb_shade_records_info layout (nebulae_hip.h)");
+    const size_t n = g->view.n_tris, rec_bytes = n * 8 * sizeof(float4), tri_bytes = n * 3 * sizeof(float4);
+    const size_t need = rec_bytes + tri_bytes + sizeof(neb_shade_records_info);
+    if (bytes)
+        *bytes = need;
+    if (!host || capacity == 0)
+        return NEB_OK; // (the size alone)
+    if (capacity < need)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_debug_shade_records: capacity below the records' size");
+    hipStream_t stream = (hipStream_t)stream_;
+    GI_GUARD(ctx);
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // behind the last rewrite of the flags, as a dispatch on this stream would be
+    neb_shade_records_info info{};
+    info.n_slots = (uint32_t)n;
+    info.table_valid = g->sun_table_state == 1 ? 1u : 0u;
+    info.builds = g->sun_table_builds;
+    for (int k = 0; k < 3; ++k)
+        info.sunLightDirection[k] = g->sun_table_key[k];
+    info.sunTanHalfAngle = g->sun_table_key[3];
+    unsigned long long counts[3] = {0, 0, 0};
+    if (n) {
+        GI_HIP(ctx, hipMemcpyAsync(host, g->view.shade, rec_bytes, hipMemcpyDeviceToHost, stream));
+        GI_HIP(ctx, hipMemcpyAsync((uint8_t*)host + rec_bytes, g->view.tris, tri_bytes, hipMemcpyDeviceToHost, stream));
+    }
+    if (info.table_valid && g->d_sun_counts)
+        GI_HIP(ctx, hipMemcpyAsync(counts, g->d_sun_counts, sizeof(counts), hipMemcpyDeviceToHost, stream));
+    GI_HIP(ctx, hipStreamSynchronize(stream));
+    info.lit_plus = counts[0], info.lit_minus = counts[1], info.hinted = counts[2];
+    memcpy((uint8_t*)host + rec_bytes + tri_bytes, &info, sizeof(info));
+    return NEB_OK;
+}
+
+} // extern "C"

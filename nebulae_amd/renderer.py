@@ -274,6 +274,24 @@ class DeferredRenderer:
                         "neb_gi_debug_texture_tables")
         return out
 
+    def shade_records(self, stream=None):
+        """the sun table as the device holds it (neb_gi_debug_shade_records; waits for the copy): (records, tris, info) -- records
+        (n_slots, 32) uint32, the 128-byte shading records in leaf order; tris (n_slots, 12) float32, what the traverser tests in each
+        slot; info = neb_shade_records_info as a dict (valid: the last dispatch used the table, built for sun / tan_half)"""
+        n = C.c_size_t(0)
+        self._check(self._lib.neb_gi_debug_shade_records(self._ctx, None, 0, C.byref(n), None), "neb_gi_debug_shade_records")
+        raw = np.zeros(n.value, np.uint8)
+        self._check(self._lib.neb_gi_debug_shade_records(self._ctx, raw.ctypes.data, n.value, None, self._stream_arg(stream)),
+                    "neb_gi_debug_shade_records")
+        n_slots = (n.value - 56) // 176  # (56 = sizeof(neb_shade_records_info): eight 4-byte words, three counters of 8 bytes)
+        tail = raw[176 * n_slots:].tobytes()
+        u32, f32, u64 = np.frombuffer(tail[:32], np.uint32), np.frombuffer(tail[:32], np.float32), np.frombuffer(tail[32:56], np.uint64)
+        if len(tail) != 56 or int(u32[0]) != n_slots:
+            raise NebError("neb_gi_debug_shade_records: the size does not match the slot count")
+        info = {"n_slots": n_slots, "valid": bool(u32[1]), "sun": tuple(float(x) for x in f32[2:5]), "tan_half": float(f32[5]), "builds": int(u32[6]),
+                "lit_plus": int(u64[0]), "lit_minus": int(u64[1]), "hinted": int(u64[2])}
+        return raw[:128 * n_slots].view(np.uint32).reshape(n_slots, 32), raw[128 * n_slots:176 * n_slots].view(np.float32).reshape(n_slots, 12), info
+
     # ---- no reference counterpart: its BLASes are built without ALLOW_UPDATE (RTAccelerationStructureBuilder.cpp:79) ----
     def update_vertices(self, index, positions, normals=None, tangents=None, first_vertex=0, stream=None):
         """Deform a submesh: vertices [first_vertex, first_vertex + len(positions)) of geometry `index` get new object-space positions
