@@ -831,6 +831,43 @@ int neb_tonemap(neb_ctx* ctx, neb_stream stream);
  * assets/shaders/deferred_gbuffers.hlsl:71-103 (writes ALBEDO, ROUGH_METAL, WORLDPOS, normal[cur], depth[cur]). */
 int neb_gbuffer_raycast(neb_ctx* ctx, const neb_camera* camera, neb_stream stream);
 
+/* Ray queries: the caller's own rays against the scene the context holds and keeps animated -- picking, line of sight,
+ * probe and lightmap baking, AO, audio occlusion, sweeps -- without a second acceleration structure.  NO reference counterpart as a call
+ * (it is what DXR inline queries, Embree and HIPRT offer as intersect / occluded).
+ * `rays` and `out` are DEVICE pointers the context's GPU can read and write (as the sources of neb_gi_update_vertices_device: device
+ * memory of this device with the whole range inside its allocation, managed memory, or mapped pinned memory): n rays in, and out =
+ * neb_ray_hit[n], or uint32_t[n] with NEB_RAYS_ANY_HIT.  rays is 16-byte aligned, out 32-byte aligned for hit records (a record is
+ * one 32-byte sector, written at its ray's index whatever order the rays are walked in) and 4-byte aligned for any-hit words.
+ * The call only enqueues on `stream`: it runs behind every update call enqueued before it on any stream, and an update enqueued after
+ * it waits for it.  The caller orders `stream` behind whatever wrote the rays and keeps both buffers alive until the stream has passed.
+ * Per ray: the closest hit with tmin < t < tmax by the triangle test and the barycentrics of the frame's own walks -- u weighs the
+ * triangle's second vertex, v its third (for a triangle the builder split, those of the whole triangle) -- t in units of the
+ * direction's length (directions need not be normalised; tmax = +inf is allowed), geometry / primitive as neb_gi_hit names them.
+ * Hidden submeshes are absent; every update call before it is reflected.  A miss: t = +inf, u = v = 0, geometry = primitive =
+ * 0xFFFFFFFF.  reserved is written as 0.  A ray that cannot be walked reports a miss and costs nothing: a zero direction, an origin
+ * or direction that is not finite (or so large that its squared length is not), tmin that is not >= 0 (NaN included), tmax that is
+ * not > tmin.  With NEB_RAYS_ANY_HIT the walk ends at the first hit in the interval and the answer is one word, 1 = occluded.
+ * NEB_RAYS_SORT walks the rays in the order of a 16-bit key (direction octant, then the origin's cell in the scene box), for rays
+ * that arrive in no coherent order; the answers are the same bits.  The sort uses one block of device memory per context that only
+ * grows: A SORTED CALL LARGER THAN ANY SORTED CALL BEFORE IT ALLOCATES AND WAITS (for the sorted call before it, on the host); NO
+ * OTHER CALL DOES -- sorted calls on different streams run one after the other (the later one waits on the device), unsorted calls
+ * use no scratch memory at all.  neb_gi_set_scene and neb_destroy free the block, neb_gi_build_bvh keeps it.
+ * Leaves neb_gi_ray_count, the traversal statistics, the sun table and every plane untouched.  Strip contexts accept it: every
+ * strip holds the whole scene.
+ * Refusals, each enqueuing nothing: NEB_ERR_STATE without a built tree; NEB_ERR_INVALID_ARG for unknown flag bits, a null,
+ * misaligned or unreadable pointer (or a range that leaves its allocation) and for out overlapping rays; NEB_ERR_OUT_OF_RANGE for
+ * n above 2^28.  n == 0 succeeds and looks at neither pointer. */
+typedef struct neb_ray {
+    float origin[3], tmin, direction[3], tmax; /* 32 bytes, the layout of D3D12's RayDesc */
+} neb_ray;
+typedef struct neb_ray_hit {
+    float t, u, v;
+    uint32_t geometry, primitive, reserved[3]; /* 32 bytes */
+} neb_ray_hit;
+#define NEB_RAYS_ANY_HIT 1u /* first hit ends the walk; the output is one uint32_t per ray, 1 = occluded */
+#define NEB_RAYS_SORT 2u    /* reorder the rays for coherence before the walk; the answers do not change */
+int neb_gi_cast_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, void* out, neb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

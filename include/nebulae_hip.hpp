@@ -263,6 +263,14 @@ namespace Neb
             ThrowIfFailed(m_svgf.Context(), neb_gi_trace_finish(m_svgf.Context(), commandList, afterShadeEvent), "neb_gi_trace_finish");
         }
 
+        // Ray queries (no reference counterpart as a call: DXR's inline RayQuery is the nearest thing): n rays from a device buffer against the
+        // scene as the update calls have left it; hits = neb_ray_hit[n] on the device, or uint32_t[n] with NEB_RAYS_ANY_HIT in flags.
+        // NEB_RAYS_SORT reorders the rays for coherence first.  Only enqueues -- a sorted call larger than any before it allocates and waits.
+        void CastRays(const neb_ray* rays, uint32_t n, uint32_t flags, void* hits, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_cast_rays(m_svgf.Context(), rays, n, flags, hits, commandList), "neb_gi_cast_rays");
+        }
+
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const
         {

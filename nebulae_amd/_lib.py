@@ -129,6 +129,7 @@ class TextureUpdate(C.Structure):
                 ("pitchBytes", C.c_uint32), ("rgba8", C.c_void_p)]
 
 
+RAYS_ANY_HIT, RAYS_SORT = 1, 2  # NEB_RAYS_*: flags of neb_gi_cast_rays
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -182,6 +183,7 @@ def _gi_sigs():
         "neb_pbr_direct": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p]),
         "neb_tonemap": (C.c_int, [C.c_void_p, C.c_void_p]),
         "neb_gbuffer_raycast": (C.c_int, [C.c_void_p, C.POINTER(S.CameraDesc), C.c_void_p]),
+        "neb_gi_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
         "neb_svgf_set_camera": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(S.CameraDesc)]),
         "neb_strip_frame": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p, C.POINTER(StripPlan), C.c_void_p]),
         "neb_strip_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),

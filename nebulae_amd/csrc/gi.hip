@@ -26,20 +26,7 @@ namespace neb {
 // Splitting keeps the two traversal kernels at <= 64 VGPRs (8 waves/SIMD) and the register-hungry shading
 // away from them.
 // ------------------------------------------------------------------------------------------------
-// Radix-sort key width for ray ordering: the top kSortBits bits of the 30-bit Morton code of the ray origin
-// (each 8 bits are one pass of raysort.hip over the pairs).
-#ifndef NEB_SORT_BITS
-#define NEB_SORT_BITS 16
-#endif
-constexpr int kSortBits = NEB_SORT_BITS;
-static_assert(kSortBits >= 1 && kSortBits <= 16, "raysort.hip sorts at most two 8-bit digits");
-
-__device__ __forceinline__ uint32_t bounce_sort_key(float3 o, float3 d, const float* smin, const float* sinv)
-{
-    const uint32_t oct = (d.x < 0.f ? 1u : 0u) | (d.y < 0.f ? 2u : 0u) | (d.z < 0.f ? 4u : 0u);
-    const uint32_t key = (oct << (kSortBits - 3)) | (morton30(o, smin, sinv) >> (30 - (kSortBits - 3)));
-    return min(key, (1u << kSortBits) - 2u);
-}
+// (the width of the ray-ordering keys, kSortBits, and bounce_sort_key: gi_device.h -- gi_query.hip sorts by the same key)
 
 struct GiRecords {
     float4* ray_o;   // {origin.xyz, tmin}      bounce ray of the path

@@ -86,6 +86,10 @@ void gi_destroy(GiState* g)
         (void)hipFree(g->d_skin_args);
     if (g->d_tstage)
         (void)hipFree(g->d_tstage);
+    if (g->d_query_sort)
+        (void)hipFree(g->d_query_sort);
+    if (g->query_ev)
+        (void)hipEventDestroy(g->query_ev);
     delete g;
 }
 

@@ -951,4 +951,21 @@ __device__ __forceinline__ uint32_t morton30(float3 p, const float* smin, const 
     return (expand_bits10(qx) << 2) | (expand_bits10(qy) << 1) | expand_bits10(qz);
 }
 
+// Radix-sort key width for ray ordering: the top kSortBits bits of the 30-bit Morton code of the ray origin
+// (each 8 bits are one pass of raysort.hip over the pairs).
+#ifndef NEB_SORT_BITS
+#define NEB_SORT_BITS 16
+#endif
+constexpr int kSortBits = NEB_SORT_BITS;
+static_assert(kSortBits >= 1 && kSortBits <= 16, "raysort.hip sorts at most two 8-bit digits");
+
+// The key of a ray that goes anywhere (the bounce rays of gi.hip, the caller's rays of gi_query.hip): the direction's octant above the
+// origin's Morton bits.  The largest key, (1 << kSortBits) - 1, is left to the callers for "no ray".
+__device__ __forceinline__ uint32_t bounce_sort_key(float3 o, float3 d, const float* smin, const float* sinv)
+{
+    const uint32_t oct = (d.x < 0.f ? 1u : 0u) | (d.y < 0.f ? 2u : 0u) | (d.z < 0.f ? 4u : 0u);
+    const uint32_t key = (oct << (kSortBits - 3)) | (morton30(o, smin, sinv) >> (30 - (kSortBits - 3)));
+    return min(key, (1u << kSortBits) - 2u);
+}
+
 } // namespace neb

@@ -403,6 +403,16 @@ struct GiState {
     // texel is read by four lanes, and by every use of its texture).  Allocated by the first call, grown to the largest seen.
     void* d_tstage = nullptr;
     size_t d_tstage_cap = 0;
+    // ---- the caller's rays: neb_gi_cast_rays with NEB_RAYS_SORT (gi_query.hip) ----
+    // One grow-only block {keys | indices | their ping-pong partners, n words each | ray_sort_scratch_bytes(n)}: every sorted call of
+    // the context uses it, so they run one after the other -- a sorted call records query_ev behind its last kernel, a sorted call on
+    // another stream waits for it on the device, and growing waits for it on the host before the block is freed.  Unsorted calls use
+    // none of this.  Freed by gi_destroy (neb_gi_set_scene, neb_destroy), kept across neb_gi_build_bvh.
+    void* d_query_sort = nullptr;
+    size_t query_sort_cap = 0;
+    hipEvent_t query_ev = nullptr;
+    hipStream_t query_stream = nullptr; // the stream query_ev was recorded on
+    bool query_ev_pending = false;
 };
 // ---- what every update call does with the ring and with its streams (gi_refit.hip) ----
 // An update takes slot call % kStageSlots of the pinned rings once that slot's last user has read it (stage_slot_acquire), orders its

@@ -1,0 +1,189 @@
+// gi_query.hip -- the caller's own rays against the scene the context holds: neb_gi_cast_rays.
+//
+// Rays and answers live in device buffers of the caller.  One lane per ray walks the tree the frame's kernels walk, with the
+// traverser they use (traverse, gi_device.h: same boxes, same triangle test, same barycentrics), closest hit or first hit; with
+// NEB_RAYS_SORT the rays are visited in the order of a 16-bit key (direction octant above the origin's Morton bits, bounce_sort_key)
+// and every answer still lands at its ray's own index.  A ray's walk depends on the ray and the tree alone, so the order changes
+// no answer.  Nothing of the frame is touched: no plane, no ray counter, no statistics, no sun table.
+#include "gi_device.h" // (turns floating-point contraction off for this file: see there)
+
+namespace neb {
+
+namespace {
+
+constexpr uint32_t kQueryMaxRays = 1u << 28; // 8 GiB of rays; the sort's indices and raysort.hip's tile counts stay far inside 32 bits
+constexpr uint32_t kNoId = 0xffffffffu;
+constexpr uint32_t kUnwalkableKey = (1u << kSortBits) - 1u; // above every key of bounce_sort_key: such rays gather at the end
+
+// The interval the walk assumes: the triangle screen of intersect_tri_regs takes tmin >= 0 for granted, and an empty interval holds
+// no hit.  Written so that a NaN on either side says no.
+__device__ __forceinline__ bool interval_ok(float tmin, float tmax) { return tmin >= 0.0f && tmax > tmin; }
+
+// One lane per ray, one wave per workgroup, the LDS stack of gbuffer_kernel.  Lane j takes ray j, or ray order[j] (SORTED), reads it
+// as two float4 and writes its answer AT THE RAY'S OWN INDEX: a hit record as two 16-byte stores of one 32-byte sector (ANY_HIT =
+// false), or one word, 1 = something lies in (tmin, tmax) (ANY_HIT = true).
+// A ray that cannot be walked reports a miss without entering the tree: traverse_t keeps a zero or non-finite direction and a
+// non-finite origin out (its `walkable`), and a ray whose interval is not in order is handed to it with a zero direction.
+template <bool ANY_HIT, bool SORTED>
+__global__ __launch_bounds__(64) void ray_query_kernel(SceneView S, const float4* __restrict__ rays, uint32_t n, const uint32_t* __restrict__ order,
+                                                       void* __restrict__ out)
+{
+    __shared__ int stack_mem[kLdsStack * 64];
+    const uint32_t lane = threadIdx.x;
+    int* stack = stack_mem + lane;
+    const uint32_t j = blockIdx.x * 64u + lane;
+    if (j >= n)
+        return;
+    const uint32_t i = SORTED ? order[j] : j;
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1]; // {origin, tmin} {direction, tmax}
+    const float tmin = r0.w, tmax = r1.w;
+    const float3 o = f3(r0.x, r0.y, r0.z);
+    const float3 d = interval_ok(tmin, tmax) ? f3(r1.x, r1.y, r1.z) : f3(0.0f, 0.0f, 0.0f);
+    Hit h;
+    const bool found = traverse(S, o, d, tmin, tmax, ANY_HIT, stack, h);
+    if constexpr (ANY_HIT) {
+        static_cast<uint32_t*>(out)[i] = found ? 1u : 0u;
+    } else {
+        float4 a = make_float4(__builtin_inff(), 0.0f, 0.0f, __uint_as_float(kNoId)); // {t, u, v, geometry}
+        uint4 b = make_uint4(kNoId, 0u, 0u, 0u);                                      // {primitive, reserved x 3}
+        if (found) {
+            const float4 ids = S.tris[3 * h.tri + 2]; // {e2.z, geometry, primitive, -}
+            a = make_float4(h.t, h.u, h.v, ids.y);
+            b.x = __float_as_uint(ids.z);
+        }
+        float4* rec = static_cast<float4*>(out) + 2 * (size_t)i;
+        rec[0] = a;
+        *reinterpret_cast<uint4*>(rec + 1) = b;
+    }
+}
+
+struct QueryBox {
+    float smin[3], sinv[3]; // the scene box the dispatches sort by (neb_gi_trace)
+};
+
+// One lane per ray: (key, index) for ray_sort_pairs.  Rays the walk kernel will not walk get the largest key.
+__global__ __launch_bounds__(256) void ray_query_key_kernel(const float4* __restrict__ rays, uint32_t n, QueryBox box, uint32_t* __restrict__ keys,
+                                                            uint32_t* __restrict__ vals)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n)
+        return;
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1];
+    const float3 o = f3(r0.x, r0.y, r0.z), d = f3(r1.x, r1.y, r1.z);
+    const float dd = dot3(d, d), oo = dot3(o, o);
+    const bool walkable = dd > 0.0f && dd < __builtin_inff() && oo < __builtin_inff() && interval_ok(r0.w, r1.w); // (traverse_t's guard)
+    keys[i] = walkable ? bounce_sort_key(o, d, box.smin, box.sinv) : kUnwalkableKey;
+    vals[i] = i;
+}
+
+bool ranges_overlap(const void* a, size_t na, const void* b, size_t nb)
+{
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + nb && b0 < a0 + na;
+}
+
+// The sort block of a call of n rays, ordered behind the sorted call before it (GiState::d_query_sort).  Only a call larger than any
+// before it gets past the first test: it waits for the last sorted call on the host, frees and allocates.
+hipError_t query_sort_block(GiState* g, size_t bytes, hipStream_t stream)
+{
+    if (!g->query_ev)
+        if (hipError_t e = hipEventCreateWithFlags(&g->query_ev, hipEventDisableTiming); e != hipSuccess)
+            return e;
+    if (bytes > g->query_sort_cap) {
+        if (g->query_ev_pending)
+            if (hipError_t e = hipEventSynchronize(g->query_ev); e != hipSuccess)
+                return e;
+        g->query_ev_pending = false;
+        if (g->d_query_sort)
+            (void)hipFree(g->d_query_sort);
+        g->d_query_sort = nullptr;
+        g->query_sort_cap = 0;
+        if (hipError_t e = hipMalloc(&g->d_query_sort, bytes); e != hipSuccess)
+            return e;
+        g->query_sort_cap = bytes;
+    } else if (g->query_ev_pending && g->query_stream != stream) {
+        if (hipError_t e = hipStreamWaitEvent(stream, g->query_ev, 0); e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+} // namespace
+
+} // namespace neb
+
+using namespace neb;
+
+extern "C" int neb_gi_cast_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, void* out, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_cast_rays: scene/BVH not ready");
+    if (flags & ~(NEB_RAYS_ANY_HIT | NEB_RAYS_SORT))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_cast_rays: unknown flag bits");
+    if (n == 0)
+        return NEB_OK;
+    if (n > kQueryMaxRays)
+        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_cast_rays: more than 2^28 rays in one call");
+    const bool any_hit = (flags & NEB_RAYS_ANY_HIT) != 0, sorted = (flags & NEB_RAYS_SORT) != 0;
+    const size_t ray_bytes = (size_t)n * sizeof(neb_ray), out_bytes = (size_t)n * (any_hit ? sizeof(uint32_t) : sizeof(neb_ray_hit));
+    if (!rays || !out)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_cast_rays: null rays or out");
+    if (((uintptr_t)rays & 15u) || ((uintptr_t)out & (any_hit ? 3u : 31u)))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_cast_rays: misaligned pointer (rays: 16 bytes; out: 32 bytes for hit records, 4 for any-hit words)");
+    if (ranges_overlap(rays, ray_bytes, out, out_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_cast_rays: out overlaps rays");
+    GI_GUARD(ctx);
+    if (!device_readable(ctx, rays, ray_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_cast_rays: rays is not memory this context's device reads, or n rays leave its allocation");
+    if (!device_readable(ctx, out, out_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_cast_rays: out is not memory this context's device reads, or n answers leave its allocation");
+    hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t* order = nullptr;
+    if (sorted) { // (before anything is enqueued: a failed allocation leaves the stream as it was)
+        const size_t bytes = 4 * (size_t)n * sizeof(uint32_t) + ray_sort_scratch_bytes(n);
+        GI_HIP(ctx, query_sort_block(g, bytes, stream));
+    }
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // behind any update enqueued on another stream; a later update waits for this stream
+    const float4* r4 = reinterpret_cast<const float4*>(rays);
+    auto enqueue = [&]() -> hipError_t {
+        if (sorted) {
+            uint32_t* keys = static_cast<uint32_t*>(g->d_query_sort);
+            uint32_t *vals = keys + n, *keys_tmp = keys + 2 * (size_t)n, *vals_tmp = keys + 3 * (size_t)n;
+            QueryBox box;
+            for (int q = 0; q < 3; ++q) {
+                box.smin[q] = g->scene_min[q];
+                box.sinv[q] = 1.0f / fmaxf(g->scene_max[q] - g->scene_min[q], 1e-20f);
+            }
+            hipLaunchKernelGGL(ray_query_key_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, r4, n, box, keys, vals);
+            if (hipError_t e = hipGetLastError(); e != hipSuccess)
+                return e;
+            if (hipError_t e = ray_sort_pairs(keys, vals, keys_tmp, vals_tmp, vals, n, kSortBits, keys + 4 * (size_t)n, stream); e != hipSuccess)
+                return e;
+            order = vals;
+        }
+        const dim3 grid((n + 63u) / 64u), block(64);
+        if (any_hit) {
+            if (sorted)
+                hipLaunchKernelGGL((ray_query_kernel<true, true>), grid, block, 0, stream, g->view, r4, n, order, out);
+            else
+                hipLaunchKernelGGL((ray_query_kernel<true, false>), grid, block, 0, stream, g->view, r4, n, order, out);
+        } else {
+            if (sorted)
+                hipLaunchKernelGGL((ray_query_kernel<false, true>), grid, block, 0, stream, g->view, r4, n, order, out);
+            else
+                hipLaunchKernelGGL((ray_query_kernel<false, false>), grid, block, 0, stream, g->view, r4, n, order, out);
+        }
+        return hipGetLastError();
+    };
+    const hipError_t launched = enqueue();
+    if (sorted) { // (also behind a chain that broke off half way: whatever of it was enqueued uses the block)
+        GI_HIP(ctx, hipEventRecord(g->query_ev, stream));
+        g->query_stream = stream;
+        g->query_ev_pending = true;
+    }
+    GI_HIP(ctx, launched);
+    return NEB_OK;
+}

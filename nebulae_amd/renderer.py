@@ -157,6 +157,35 @@ class DeferredRenderer:
                                              idx.size, st)
         self._check(rc, "neb_gi_set_visibility")
 
+    # ---- ray queries: the caller's rays against the scene as it stands (no reference counterpart) ----
+    def cast_rays(self, rays, any_hit=False, sort=False, out=None, stream=None):
+        """Cast n rays from a device buffer into the scene the renderer holds (neb_gi_cast_rays): `rays` is a contiguous float32 CUDA
+        tensor [n, 8], a row = {origin xyz, tmin, direction xyz, tmax} (directions need not be normalised, tmax may be inf).  Closest
+        hit: returns a dict of tensors t, u, v (float32), geometry, primitive (uint32 bit patterns as int32: -1 = no hit; t = inf
+        then), all views of one [n, 8] float32 buffer, which is under "records" -- `out`, when given.  any_hit=True: returns
+        {"occluded": int32 [n]}, 1 = something lies in (tmin, tmax) -- `out`, when given.  sort=True reorders the rays for coherence
+        before the walk; the answers are the same bits.  The call only enqueues on `stream` (a raw stream handle; default: the
+        frame's), behind every update enqueued before it; nothing is copied to the host."""
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
+                and rays.is_contiguous()):
+            raise NebError("cast_rays: rays must be a contiguous float32 CUDA tensor [n, 8]")
+        n = rays.shape[0]
+        shape, dtype = ((n,), torch.int32) if any_hit else ((n, 8), torch.float32)
+        if out is None:
+            with torch.cuda.device(rays.device):
+                out = torch.empty(shape, dtype=dtype, device=rays.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype and tuple(out.shape) == shape and out.is_contiguous()):
+            raise NebError(f"cast_rays: out must be a contiguous {dtype} CUDA tensor of shape {shape}")
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        flags = (_lib.RAYS_ANY_HIT if any_hit else 0) | (_lib.RAYS_SORT if sort else 0)
+        rc = self._lib.neb_gi_cast_rays(self._ctx, C.c_void_p(rays.data_ptr() if n else 0), n, flags, C.c_void_p(out.data_ptr() if n else 0), st)
+        self._check(rc, "neb_gi_cast_rays")
+        if any_hit:
+            return {"occluded": out}
+        ids = out.view(torch.int32)
+        return {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "geometry": ids[:, 3], "primitive": ids[:, 4], "records": out}
+
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
         n = C.c_uint32(0)
