@@ -868,6 +868,72 @@ typedef struct neb_ray_hit {
 #define NEB_RAYS_SORT 2u    /* reorder the rays for coherence before the walk; the answers do not change */
 int neb_gi_cast_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, void* out, neb_stream stream);
 
+/* Shaded ray queries: the rays of neb_gi_cast_rays, and at each closest hit the surface the frame's shade pass would
+ * reconstruct there (NEB_SHADE_SURFACE) or what the frame's path adds at a vertex reached along the ray with throughput 1
+ * (NEB_SHADE_RADIANCE) -- the closest-hit shader's inputs of DXR, Embree and HIPRT, from the shading records, headers, footprint
+ * tables and material bundles the device keeps, which no host copy follows across the update calls.  NO reference counterpart as a call.
+ * `rays` and `out` are DEVICE pointers the context's GPU can read and write (as neb_gi_cast_rays takes them): n rays in, and out =
+ * neb_ray_surface[n] or neb_ray_radiance[n].  rays is 16-byte aligned, out 32-byte aligned (a surface record is three 32-byte
+ * sectors, a radiance record one, written at its ray's index whatever order the rays are walked in); the two do not overlap.
+ * The call only enqueues on `stream`: it runs behind every update call enqueued before it on any stream, and an update enqueued after
+ * it waits for it.  The caller orders `stream` behind whatever wrote the rays and keeps both buffers alive until the stream has passed.
+ * Per ray: the closest hit with tmin < t < tmax; t, u, v, geometry and primitive are THE BITS neb_gi_cast_rays RETURNS FOR THE SAME
+ * RAY.  Hidden submeshes are absent; every update call before it is reflected, materials and texels included.  The arithmetic policy
+ * is the shade pass's ("gi_exact_shade").  flags (NEB_HIT_*): FOUND; ATTRIBUTES, the geometry has all its attribute streams, so
+ * geometricNormal and texcoord are valid; MATERIAL, it has a material too, so shadingNormal, albedo, roughness and metalness are
+ * valid; BACKFACE, dot(geometricNormal, direction) > 0 (defined only with ATTRIBUTES); NOT_WALKED; SUN_VISIBLE (radiance records).
+ * A field whose flag is clear is written as 0 -- except material = -1, and shadingNormal = geometricNormal for a geometry with
+ * attributes and no material.  A miss: t = +inf, geometry = primitive = 0xFFFFFFFF, material = -1, everything else 0.  A ray that
+ * cannot be walked (the six kinds of neb_gi_cast_rays) never enters the tree: the miss record with NEB_HIT_NOT_WALKED set.
+ * NEB_SHADE_SURFACE: position = origin + direction * t, each product and sum rounded by itself (the frame's hit point);
+ * geometricNormal: world space, unit, as the vertex normals say, NOT flipped towards the ray; shadingNormal: the normal map applied;
+ * texcoord: the interpolated uv the maps are sampled at; albedo, roughness, metalness: maps (bilinear, wrap) or factors, as the frame.
+ * `constants` is ignored and may be NULL.
+ * NEB_SHADE_RADIANCE: a miss gives skyColor (the constants' bits); a ray that was not walked gives 0, so that it can be told from a
+ * miss; a hit without attributes or material gives 0 (the frame's path ends there too); a hit with NEB_HIT_MATERIAL casts ONE sun-disk
+ * shadow ray, built as the frame builds it (pathtracer.hlsl:546-557): the two disk draws come from rng = JenkinsHash(i ^
+ * JenkinsHash(frameIndex)), i = the ray's index in `rays` (vary frameIndex to average over the disk); origin = position -+ 1e-2
+ * geometricNormal, on the side the ray leaves to; tmin 0.001, tmax 10000.  Unoccluded: rgb = EvaluateDirectBRDF(surface, V =
+ * normalize(-direction), L = normalize(-sunLightDirection)) * sunLightRadiance -- the BRDF at the disk's CENTRE, no N.L factor, as
+ * the frame -- and NEB_HIT_SUN_VISIBLE is set; occluded: 0.  Of the constants only frameIndex, skyColor, sunLightDirection,
+ * sunLightRadiance and sunTanHalfAngle are read; they are taken as neb_gi_trace takes them, which refuses no value of them.  So a
+ * degenerate sun acts as it acts on the frame: a zero (or non-finite) sunLightDirection gives a NaN sun frame, the shadow ray is one
+ * the walk refuses -- hence "unoccluded" -- and every hit with a material reports NaN radiance with NEB_HIT_SUN_VISIBLE set.  Every
+ * shadow ray is walked: the sun table is neither read nor touched.
+ * NEB_RAYS_SORT: as neb_gi_cast_rays -- the same key, the same block of device memory and its rule (A SORTED CALL LARGER THAN ANY
+ * SORTED CALL BEFORE IT, OF EITHER ENTRY POINT, ALLOCATES AND WAITS; NO OTHER CALL DOES); the answers are the same bits.
+ * Leaves neb_gi_ray_count, the traversal statistics, the sun table with its hold counters and every plane untouched.  Strip contexts
+ * accept it.
+ * Refusals, each enqueuing nothing: NEB_ERR_STATE without a built tree; NEB_ERR_INVALID_ARG for an unknown `what`, unknown flag
+ * bits or NEB_RAYS_ANY_HIT, NEB_SHADE_RADIANCE without constants, a null, misaligned or unreadable pointer (or a range that leaves its
+ * allocation) and for out overlapping rays; NEB_ERR_OUT_OF_RANGE for n above 2^28.  n == 0 succeeds and looks at no pointer. */
+typedef struct neb_ray_surface {
+    float position[3], t;
+    float geometricNormal[3];
+    uint32_t geometry;
+    float shadingNormal[3];
+    uint32_t primitive;
+    float albedo[3], roughness;
+    float metalness, texcoord[2];
+    int32_t material; /* -1: none */
+    float u, v;       /* barycentrics, as neb_ray_hit */
+    uint32_t flags, reserved; /* 96 bytes */
+} neb_ray_surface;
+typedef struct neb_ray_radiance {
+    float r, g, b, t;
+    uint32_t geometry, primitive, flags, reserved; /* 32 bytes */
+} neb_ray_radiance;
+#define NEB_SHADE_SURFACE 0u
+#define NEB_SHADE_RADIANCE 1u
+#define NEB_HIT_FOUND 1u
+#define NEB_HIT_ATTRIBUTES 2u
+#define NEB_HIT_MATERIAL 4u
+#define NEB_HIT_BACKFACE 8u
+#define NEB_HIT_NOT_WALKED 16u
+#define NEB_HIT_SUN_VISIBLE 32u
+int neb_gi_shade_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t what, uint32_t flags /* 0 or NEB_RAYS_SORT */,
+                      const neb_gi_constants* constants /* RADIANCE: required; SURFACE: ignored, may be NULL */, void* out, neb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -270,6 +270,13 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_cast_rays(m_svgf.Context(), rays, n, flags, hits, commandList), "neb_gi_cast_rays");
         }
+        // The same rays, shaded at their closest hits (the inputs of a closest-hit shader): what = NEB_SHADE_SURFACE writes neb_ray_surface[n]
+        // (constants may be null), NEB_SHADE_RADIANCE neb_ray_radiance[n]: sky on a miss, the sun's direct light through one disk-sampled shadow
+        // ray on a hit (frameIndex seeds the draws).  flags: 0 or NEB_RAYS_SORT.  Only enqueues, as CastRays.
+        void ShadeRays(const neb_ray* rays, uint32_t n, uint32_t what, uint32_t flags, const neb_gi_constants* constants, void* out, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_shade_rays(m_svgf.Context(), rays, n, what, flags, constants, out, commandList), "neb_gi_shade_rays");
+        }
 
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const

@@ -1,4 +1,5 @@
-// gi_query.hip -- the caller's own rays against the scene the context holds: neb_gi_cast_rays.
+// gi_query.hip -- the caller's own rays against the scene the context holds: neb_gi_cast_rays and neb_gi_shade_rays
+// (3.8a), which walks the same way and then shades the hit as the frame's shade pass would.
 //
 // Rays and answers live in device buffers of the caller.  One lane per ray walks the tree the frame's kernels walk, with the
 // traverser they use (traverse, gi_device.h: same boxes, same triangle test, same barycentrics), closest hit or first hit; with
@@ -57,6 +58,117 @@ __global__ __launch_bounds__(64) void ray_query_kernel(SceneView S, const float4
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// neb_gi_shade_rays: the walk above, then the surface at the hit (NEB_SHADE_SURFACE) or what the frame's path adds there (NEB_SHADE_RADIANCE)
+// ------------------------------------------------------------------------------------------------
+// What the RADIANCE kernel reads of the constants: the sun frame of the dispatch (sun_frame, on the host, as neb_gi_trace), the
+// radiances and the seed of the disk draws.
+static_assert(sizeof(neb_ray_surface) == 96 && offsetof(neb_ray_surface, flags) == 88 && sizeof(neb_ray_radiance) == 32, "records of neb_gi_shade_rays");
+struct ShadeSun {
+    float L[3], B[3], T[3];
+    float radiance[3], sky[3];
+    float tan_half;
+    uint32_t frame_index;
+};
+
+// traverse_t's guard and interval_ok in one: the rays ray_query_key_kernel gives the largest key.  (The walk kernels need not ask --
+// the traverser refuses such a ray by itself -- but the shade kernel has to tell "not walked" from "walked and missed".)
+__device__ __forceinline__ bool ray_walkable(float3 o, float3 d, float tmin, float tmax)
+{
+    const float dd = dot3(d, d), oo = dot3(o, o);
+    return dd > 0.0f && dd < __builtin_inff() && oo < __builtin_inff() && interval_ok(tmin, tmax);
+}
+
+// ray_query_kernel's shape: one lane per ray, one wave per workgroup, its LDS stack; lane j takes ray j or order[j] and answers at
+// the ray's own index with 16-byte stores, six for a neb_ray_surface, two for a neb_ray_radiance.  After the closest-hit walk a lane
+// that hit loads the triangle's shading record and its geometry's shade header -- the two lines the shade pass reads for that hit --
+// and runs the halves of reconstruct_surface<FAST> on them.  RADIANCE then builds shade_pixel's sun-disk shadow ray (its exact-
+// arithmetic sequence under both policies) and walks it any-hit on the same stack; a lane that has no shadow ray hands the traverser
+// a zero direction, which it refuses without entering the tree.  The BRDF runs where the walk found nothing.
+template <uint32_t WHAT, bool SORTED, bool FAST>
+__global__ __launch_bounds__(64) void ray_shade_kernel(SceneView S, const ShadeHeader* __restrict__ heads, const float4* __restrict__ rays, uint32_t n,
+                                                       const uint32_t* __restrict__ order, ShadeSun sun, float4* __restrict__ out)
+{
+    __shared__ int stack_mem[kLdsStack * 64];
+    const uint32_t lane = threadIdx.x;
+    int* stack = stack_mem + lane;
+    const uint32_t j = blockIdx.x * 64u + lane;
+    if (j >= n)
+        return;
+    const uint32_t i = SORTED ? order[j] : j;
+    const float4 r0 = rays[2 * (size_t)i], r1 = rays[2 * (size_t)i + 1]; // {origin, tmin} {direction, tmax}
+    const float tmin = r0.w, tmax = r1.w;
+    const float3 o = f3(r0.x, r0.y, r0.z), dir = f3(r1.x, r1.y, r1.z);
+    const bool walked = ray_walkable(o, dir, tmin, tmax);
+    Hit h;
+    const bool found = traverse(S, o, walked ? dir : f3(0.0f, 0.0f, 0.0f), tmin, tmax, false, stack, h);
+
+    uint32_t flags = walked ? 0u : (uint32_t)NEB_HIT_NOT_WALKED;
+    float t = __builtin_inff(), bu = 0.0f, bv = 0.0f, tex_u = 0.0f, tex_v = 0.0f;
+    uint32_t geometry = kNoId, primitive = kNoId;
+    int32_t material = -1;
+    float3 hitP = f3(0.0f, 0.0f, 0.0f);
+    Surface surf;
+    surf.GN = surf.SN = surf.albedo = f3(0.0f, 0.0f, 0.0f);
+    surf.roughness = surf.metalness = 0.0f;
+    if (found) {
+        const float4 ids = S.tris[3 * h.tri + 2]; // {e2.z, geometry, primitive, -}: the words neb_gi_cast_rays reports
+        const TriShade ts = load_tri_shade(S, h.tri);
+        const ShadeHead head = load_shade_header(heads, ts.geom);
+        t = h.t, bu = h.u, bv = h.v;
+        geometry = __float_as_uint(ids.y), primitive = __float_as_uint(ids.z);
+        hitP = o + dir * h.t;
+        flags |= NEB_HIT_FOUND;
+        // reconstruct_surface, its two halves called as it calls them: the uv between them is part of the record
+        const bool shaded = reconstruct_geometry<FAST>(head, ts, h.u, h.v, surf, tex_u, tex_v);
+        if (head.valid) {
+            flags |= NEB_HIT_ATTRIBUTES | (dot3(surf.GN, dir) > 0.0f ? (uint32_t)NEB_HIT_BACKFACE : 0u);
+            surf.SN = surf.GN; // (a geometry without a material; the material half replaces it)
+        }
+        if (shaded) {
+            MapSamples maps;
+            sample_material_maps<FAST>(S, head.mat, tex_u, tex_v, maps);
+            reconstruct_material<FAST>(head.mat, ts, h.u, h.v, maps, surf);
+            flags |= NEB_HIT_MATERIAL;
+            material = head.material;
+        }
+    }
+    if constexpr (WHAT == NEB_SHADE_SURFACE) {
+        float4* rec = out + 6 * (size_t)i;
+        rec[0] = make_float4(hitP.x, hitP.y, hitP.z, t);
+        rec[1] = make_float4(surf.GN.x, surf.GN.y, surf.GN.z, __uint_as_float(geometry));
+        rec[2] = make_float4(surf.SN.x, surf.SN.y, surf.SN.z, __uint_as_float(primitive));
+        rec[3] = make_float4(surf.albedo.x, surf.albedo.y, surf.albedo.z, surf.roughness);
+        rec[4] = make_float4(surf.metalness, tex_u, tex_v, __uint_as_float((uint32_t)material));
+        rec[5] = make_float4(bu, bv, __uint_as_float(flags), 0.0f);
+    } else {
+        const bool shaded = (flags & NEB_HIT_MATERIAL) != 0;
+        // shade_pixel's shadow ray (gi.hip; pathtracer.hlsl:546-557), the draws seeded by the ray's index in the caller's array
+        uint32_t rng = jenkins(i ^ jenkins(sun.frame_index));
+        const float a0 = rand01(rng), a1 = rand01(rng);
+        const float angle = a0 * 2.0f * 3.1415926535f, dist = fsqrt<false>(a1);
+        const float3 L = f3(sun.L[0], sun.L[1], sun.L[2]), Bv = f3(sun.B[0], sun.B[1], sun.B[2]), T = f3(sun.T[0], sun.T[1], sun.T[2]);
+        float sn_a, cs_a;
+        det_sincosf(angle, sn_a, cs_a);
+        const float3 inc = normalize3<false>(L + (Bv * sn_a + T * cs_a) * sun.tan_half * dist);
+        const bool transition = dot3(surf.GN, inc) <= 0.0f;
+        const float3 so = hitP + (transition ? -surf.GN : surf.GN) * 1e-2f;
+        Hit sh;
+        const bool occluded = traverse(S, so, shaded ? inc : f3(0.0f, 0.0f, 0.0f), 0.001f, kTraceMax, true, stack, sh);
+        float3 rgb = f3(0.0f, 0.0f, 0.0f);
+        if (walked && !found)
+            rgb = f3(sun.sky[0], sun.sky[1], sun.sky[2]); // :508
+        if (shaded && !occluded) {
+            const float3 V = normalize3<FAST>(-dir); // :522
+            rgb = evaluate_direct_brdf<FAST>(surf, V, L) * f3(sun.radiance[0], sun.radiance[1], sun.radiance[2]); // :573-574
+            flags |= NEB_HIT_SUN_VISIBLE;
+        }
+        float4* rec = out + 2 * (size_t)i;
+        rec[0] = make_float4(rgb.x, rgb.y, rgb.z, t);
+        rec[1] = make_float4(__uint_as_float(geometry), __uint_as_float(primitive), __uint_as_float(flags), 0.0f);
+    }
+}
+
 struct QueryBox {
     float smin[3], sinv[3]; // the scene box the dispatches sort by (neb_gi_trace)
 };
@@ -108,6 +220,27 @@ hipError_t query_sort_block(GiState* g, size_t bytes, hipStream_t stream)
     return hipSuccess;
 }
 
+// The walk order of a sorted call into the block query_sort_block has made room for: keys, the radix sort -> the sorted indices.
+hipError_t enqueue_ray_order(GiState* g, const float4* r4, uint32_t n, hipStream_t stream, const uint32_t*& order)
+{
+    uint32_t* keys = static_cast<uint32_t*>(g->d_query_sort);
+    uint32_t *vals = keys + n, *keys_tmp = keys + 2 * (size_t)n, *vals_tmp = keys + 3 * (size_t)n;
+    QueryBox box;
+    for (int q = 0; q < 3; ++q) {
+        box.smin[q] = g->scene_min[q];
+        box.sinv[q] = 1.0f / fmaxf(g->scene_max[q] - g->scene_min[q], 1e-20f);
+    }
+    hipLaunchKernelGGL(ray_query_key_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, r4, n, box, keys, vals);
+    if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        return e;
+    if (hipError_t e = ray_sort_pairs(keys, vals, keys_tmp, vals_tmp, vals, n, kSortBits, keys + 4 * (size_t)n, stream); e != hipSuccess)
+        return e;
+    order = vals;
+    return hipSuccess;
+}
+
+size_t query_sort_bytes(uint32_t n) { return 4 * (size_t)n * sizeof(uint32_t) + ray_sort_scratch_bytes(n); }
+
 } // namespace
 
 } // namespace neb
@@ -143,27 +276,14 @@ extern "C" int neb_gi_cast_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, u
     hipStream_t stream = (hipStream_t)stream_;
     const uint32_t* order = nullptr;
     if (sorted) { // (before anything is enqueued: a failed allocation leaves the stream as it was)
-        const size_t bytes = 4 * (size_t)n * sizeof(uint32_t) + ray_sort_scratch_bytes(n);
-        GI_HIP(ctx, query_sort_block(g, bytes, stream));
+        GI_HIP(ctx, query_sort_block(g, query_sort_bytes(n), stream));
     }
     GI_HIP(ctx, gi_scene_reader(g, stream)); // behind any update enqueued on another stream; a later update waits for this stream
     const float4* r4 = reinterpret_cast<const float4*>(rays);
     auto enqueue = [&]() -> hipError_t {
-        if (sorted) {
-            uint32_t* keys = static_cast<uint32_t*>(g->d_query_sort);
-            uint32_t *vals = keys + n, *keys_tmp = keys + 2 * (size_t)n, *vals_tmp = keys + 3 * (size_t)n;
-            QueryBox box;
-            for (int q = 0; q < 3; ++q) {
-                box.smin[q] = g->scene_min[q];
-                box.sinv[q] = 1.0f / fmaxf(g->scene_max[q] - g->scene_min[q], 1e-20f);
-            }
-            hipLaunchKernelGGL(ray_query_key_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, r4, n, box, keys, vals);
-            if (hipError_t e = hipGetLastError(); e != hipSuccess)
+        if (sorted)
+            if (hipError_t e = enqueue_ray_order(g, r4, n, stream, order); e != hipSuccess)
                 return e;
-            if (hipError_t e = ray_sort_pairs(keys, vals, keys_tmp, vals_tmp, vals, n, kSortBits, keys + 4 * (size_t)n, stream); e != hipSuccess)
-                return e;
-            order = vals;
-        }
         const dim3 grid((n + 63u) / 64u), block(64);
         if (any_hit) {
             if (sorted)
@@ -176,6 +296,79 @@ extern "C" int neb_gi_cast_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, u
             else
                 hipLaunchKernelGGL((ray_query_kernel<false, false>), grid, block, 0, stream, g->view, r4, n, order, out);
         }
+        return hipGetLastError();
+    };
+    const hipError_t launched = enqueue();
+    if (sorted) { // (also behind a chain that broke off half way: whatever of it was enqueued uses the block)
+        GI_HIP(ctx, hipEventRecord(g->query_ev, stream));
+        g->query_stream = stream;
+        g->query_ev_pending = true;
+    }
+    GI_HIP(ctx, launched);
+    return NEB_OK;
+}
+
+extern "C" int neb_gi_shade_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t what, uint32_t flags, const neb_gi_constants* constants, void* out,
+                                 neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_shade_rays: scene/BVH not ready");
+    if (what != NEB_SHADE_SURFACE && what != NEB_SHADE_RADIANCE)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: unknown `what` (NEB_SHADE_SURFACE or NEB_SHADE_RADIANCE)");
+    if (flags & ~NEB_RAYS_SORT)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, flags & NEB_RAYS_ANY_HIT ? "neb_gi_shade_rays: NEB_RAYS_ANY_HIT is not a flag of this call (a first hit has no surface to report)"
+                                                                          : "neb_gi_shade_rays: unknown flag bits");
+    const bool radiance = what == NEB_SHADE_RADIANCE, sorted = (flags & NEB_RAYS_SORT) != 0;
+    if (n == 0)
+        return NEB_OK;
+    if (n > kQueryMaxRays)
+        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gi_shade_rays: more than 2^28 rays in one call");
+    if (radiance && !constants)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: NEB_SHADE_RADIANCE needs constants (null)");
+    const size_t ray_bytes = (size_t)n * sizeof(neb_ray), out_bytes = (size_t)n * (radiance ? sizeof(neb_ray_radiance) : sizeof(neb_ray_surface));
+    if (!rays || !out)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: null rays or out");
+    if (((uintptr_t)rays & 15u) || ((uintptr_t)out & 31u))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: misaligned pointer (rays: 16 bytes; out: 32 bytes)");
+    if (ranges_overlap(rays, ray_bytes, out, out_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: out overlaps rays");
+    GI_GUARD(ctx);
+    if (!device_readable(ctx, rays, ray_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: rays is not memory this context's device reads, or n rays leave its allocation");
+    if (!device_readable(ctx, out, out_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_shade_rays: out is not memory this context's device reads, or n records leave its allocation");
+    hipStream_t stream = (hipStream_t)stream_;
+    ShadeSun sun = {};
+    if (radiance) { // (neb_gi_trace refuses no value of the sun fields, so none is refused here: they act as they act on the frame)
+        sun_frame(constants->sunLightDirection, sun.L, sun.B, sun.T);
+        for (int q = 0; q < 3; ++q) {
+            sun.radiance[q] = constants->sunLightRadiance[q];
+            sun.sky[q] = constants->skyColor[q];
+        }
+        sun.tan_half = constants->sunTanHalfAngle;
+        sun.frame_index = constants->frameIndex;
+    }
+    if (sorted) // (before anything is enqueued: a failed allocation leaves the stream as it was)
+        GI_HIP(ctx, query_sort_block(g, query_sort_bytes(n), stream));
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // behind any update enqueued on another stream; a later update waits for this stream
+    const float4* r4 = reinterpret_cast<const float4*>(rays);
+    auto enqueue = [&]() -> hipError_t {
+        const uint32_t* order = nullptr;
+        if (sorted)
+            if (hipError_t e = enqueue_ray_order(g, r4, n, stream, order); e != hipSuccess)
+                return e;
+        // {what, sorted, fast}: the arithmetic policy is the shade pass's ("gi_exact_shade")
+        using Kernel = void (*)(SceneView, const ShadeHeader*, const float4*, uint32_t, const uint32_t*, ShadeSun, float4*);
+        static const Kernel kernels[2][2][2] = {
+            {{ray_shade_kernel<NEB_SHADE_SURFACE, false, false>, ray_shade_kernel<NEB_SHADE_SURFACE, false, true>},
+             {ray_shade_kernel<NEB_SHADE_SURFACE, true, false>, ray_shade_kernel<NEB_SHADE_SURFACE, true, true>}},
+            {{ray_shade_kernel<NEB_SHADE_RADIANCE, false, false>, ray_shade_kernel<NEB_SHADE_RADIANCE, false, true>},
+             {ray_shade_kernel<NEB_SHADE_RADIANCE, true, false>, ray_shade_kernel<NEB_SHADE_RADIANCE, true, true>}}};
+        hipLaunchKernelGGL(kernels[radiance][sorted][!g->exact_shade], dim3((n + 63u) / 64u), dim3(64), 0, stream, g->view, g->shade_heads, r4, n, order, sun,
+                           static_cast<float4*>(out));
         return hipGetLastError();
     };
     const hipError_t launched = enqueue();

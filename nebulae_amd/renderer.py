@@ -186,6 +186,43 @@ class DeferredRenderer:
         ids = out.view(torch.int32)
         return {"t": out[:, 0], "u": out[:, 1], "v": out[:, 2], "geometry": ids[:, 3], "primitive": ids[:, 4], "records": out}
 
+    def shade_rays(self, rays, what="surface", constants=None, sort=False, out=None, stream=None):
+        """Cast n rays as cast_rays does and shade their closest hits (neb_gi_shade_rays).  what="surface": returns
+        views of one [n, 24] float32 buffer (neb_ray_surface) -- position [n, 3], t, geometric_normal, shading_normal, albedo [n, 3],
+        roughness, metalness, texcoord [n, 2], material, u, v, geometry, primitive, flags (the ids and flags as int32; flags of
+        _lib.HIT_*) -- with the buffer under "records".  what="radiance": views of one [n, 8] buffer (neb_ray_radiance) -- radiance
+        [n, 3], t, geometry, primitive, flags -- where a miss carries the sky and a hit the sun's direct light through one disk-sampled
+        shadow ray; `constants` (a scene.GIConstants; default: global_constants() of the frame) gives sky, sun and the frameIndex that
+        seeds the disk draws.  `out`, when given, is the buffer.  sort=True reorders the rays for coherence; the answers are the same
+        bits.  The call only enqueues on `stream`, behind every update enqueued before it; nothing is copied to the host."""
+        import torch
+        if what not in ("surface", "radiance"):
+            raise NebError('shade_rays: what is "surface" or "radiance"')
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
+                and rays.is_contiguous()):
+            raise NebError("shade_rays: rays must be a contiguous float32 CUDA tensor [n, 8]")
+        n = rays.shape[0]
+        radiance = what == "radiance"
+        shape = (n, 8) if radiance else (n, 24)
+        if out is None:
+            with torch.cuda.device(rays.device):
+                out = torch.empty(shape, dtype=torch.float32, device=rays.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+            raise NebError(f"shade_rays: out must be a contiguous torch.float32 CUDA tensor of shape {shape}")
+        if radiance and constants is None:
+            constants = self.global_constants()
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        rc = self._lib.neb_gi_shade_rays(self._ctx, C.c_void_p(rays.data_ptr() if n else 0), n, _lib.SHADE_RADIANCE if radiance else _lib.SHADE_SURFACE,
+                                         _lib.RAYS_SORT if sort else 0, C.byref(constants) if constants is not None else None,
+                                         C.c_void_p(out.data_ptr() if n else 0), st)
+        self._check(rc, "neb_gi_shade_rays")
+        ids = out.view(torch.int32)
+        if radiance:
+            return {"radiance": out[:, 0:3], "t": out[:, 3], "geometry": ids[:, 4], "primitive": ids[:, 5], "flags": ids[:, 6], "records": out}
+        return {"position": out[:, 0:3], "t": out[:, 3], "geometric_normal": out[:, 4:7], "geometry": ids[:, 7], "shading_normal": out[:, 8:11],
+                "primitive": ids[:, 11], "albedo": out[:, 12:15], "roughness": out[:, 15], "metalness": out[:, 16], "texcoord": out[:, 17:19],
+                "material": ids[:, 19], "u": out[:, 20], "v": out[:, 21], "flags": ids[:, 22], "records": out}
+
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
         n = C.c_uint32(0)
