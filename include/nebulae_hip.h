@@ -934,6 +934,62 @@ typedef struct neb_ray_radiance {
 int neb_gi_shade_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t what, uint32_t flags /* 0 or NEB_RAYS_SORT */,
                       const neb_gi_constants* constants /* RADIANCE: required; SURFACE: ignored, may be NULL */, void* out, neb_stream stream);
 
+/* Path queries: the rays of neb_gi_cast_rays, each followed as the frame follows a pixel's path -- the bounce loop of
+ * pathtracer.hlsl:495-621 with up to maxPathVertices - 1 segments, its RNG stream, its by-value EvaluateIndirectBRDF draws and its
+ * throughput rule -- for probes and lightmap bakers that need indirect light.  NO reference counterpart as a call.
+ * `rays`, `out` and `vertices` are DEVICE pointers (as neb_gi_shade_rays takes them): n rays in, out = neb_ray_path[n], and vertices
+ * = NULL or neb_path_vertex[n * (maxPathVertices - 1)].  rays is 16-byte aligned, out and vertices 32-byte aligned; no two of the
+ * three overlap.  Stream ordering behind and ahead of the update calls, n == 0, the 2^28 limit, NEB_RAYS_SORT (the same key, the same
+ * block of device memory and its rule: A SORTED CALL LARGER THAN ANY SORTED CALL BEFORE IT, OF ANY OF THE THREE ENTRY POINTS, ALLOCATES
+ * AND WAITS; NO OTHER CALL DOES) and the arithmetic policy are those of neb_gi_shade_rays.  Only the first segment is walked in sorted
+ * order; the answers are the same bits.
+ * Per ray i: throughput = 1, rng = JenkinsHash(i ^ JenkinsHash(frameIndex)), i the index in `rays`; segment 1 is the caller's ray.  A ray
+ * that cannot be walked (the six kinds of neb_gi_cast_rays) gives the miss record with NEB_HIT_NOT_WALKED, radiance 0, segments 0.
+ * For k = 1 .. maxPathVertices - 1 the closest hit is walked.  A miss adds skyColor * throughput, sets NEB_PATH_ESCAPED and ends the
+ * path.  A hit without attributes or material ends the path and adds nothing.  A hit with NEB_HIT_MATERIAL takes two disk draws from
+ * rng and casts the sun-disk shadow ray of NEB_SHADE_RADIANCE (every shadow ray is walked); unoccluded, it adds EvaluateDirectBRDF *
+ * sunLightRadiance * throughput and sets NEB_HIT_SUN_VISIBLE.  If k + 1 < maxPathVertices the next segment is sampled: e0, e1 from a
+ * COPY of rng, direction = the cosine-weighted hemisphere sample about normalize(shadingNormal), origin = position + 1e-2
+ * geometricNormal, tmin 0.001, tmax 10000; pdiff = 1 - specular probability(saturate(V.N), F0, albedo); throughput *= albedo * (1 -
+ * metalness); then, if Rand(rng) < pdiff, throughput /= pdiff (NEB_PATH_DIVIDED).  A later segment the walk refuses (a direction that
+ * is not finite) is a miss, as on the frame, and its vertex carries NEB_HIT_NOT_WALKED.
+ * Vertex 1 ASSIGNS the sum and later vertices add to it: with maxPathVertices = 2 the record is NEB_SHADE_RADIANCE's bit for bit (r, g,
+ * b, t, geometry, primitive, flags & 0x3F), the NaN of a degenerate sun included.  t, geometry, primitive and the NEB_HIT_* flags of
+ * the record are those of the first segment.
+ * With vertices != NULL, record i * (maxPathVertices - 1) + (k - 1) describes segment k of ray i: the segment's ray (k = 1: the
+ * caller's bits), t / geometry / primitive / u / v as neb_gi_cast_rays answers that ray (t = +inf, ids 0xFFFFFFFF: it missed),
+ * throughput and rng on ENTERING the vertex, what the vertex added to the sum (throughput included), its flags, and pdiff (0 where no
+ * next segment is sampled).  A record past the path's end is 96 zero bytes; every record is written.  `out` is the same bits with and
+ * without `vertices`.
+ * Of the constants only frameIndex, maxPathVertices, skyColor, sunLightDirection, sunLightRadiance and sunTanHalfAngle are read
+ * (samplesPerPixel is not: average calls with different frameIndex).  Leaves neb_gi_ray_count, the traversal statistics, the sun
+ * table with its hold counters and every plane untouched.  Strip contexts accept it.
+ * Refusals, each enqueuing nothing: NEB_ERR_STATE without a built tree; NEB_ERR_INVALID_ARG for unknown flag bits or
+ * NEB_RAYS_ANY_HIT, null constants, maxPathVertices outside 2..8, a null (rays, out), misaligned or unreadable pointer (or a range that
+ * leaves its allocation) and for overlapping ranges; NEB_ERR_OUT_OF_RANGE for n above 2^28.  n == 0 succeeds and looks at no pointer. */
+typedef struct neb_ray_path { /* 32 bytes, the layout of neb_ray_radiance */
+    float r, g, b, t;             /* path radiance; t of the FIRST hit (+inf: none) */
+    uint32_t geometry, primitive; /* of the first hit */
+    uint32_t flags;               /* NEB_HIT_* of vertex 1 (SUN_VISIBLE included) | NEB_PATH_ESCAPED */
+    uint32_t segments;            /* closest-hit walks this path made: 0 (not walked) .. maxPathVertices - 1 */
+} neb_ray_path;
+typedef struct neb_path_vertex { /* 96 bytes, three 32-byte sectors */
+    float origin[3], tmin; /* the segment's ray; k = 1: the caller's bits */
+    float direction[3], t; /* t = +inf: this segment missed */
+    float throughput[3];
+    uint32_t rng; /* both on ENTERING the vertex, before its disk draws */
+    float added[3];
+    uint32_t flags; /* what this vertex added to the sum (throughput included); NEB_HIT_* of this vertex | NEB_PATH_DIVIDED */
+    uint32_t geometry, primitive;
+    float u, v;
+    float tmax, pdiff; /* pdiff: 1 - specular probability used for the next bounce (0 where none is sampled) */
+    uint32_t reserved[2];
+} neb_path_vertex;
+#define NEB_PATH_ESCAPED 64u  /* some segment missed: the sky (times throughput) is in the sum */
+#define NEB_PATH_DIVIDED 128u /* the throughput leaving this vertex was divided by pdiff (Rand < pdiff) */
+int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags /* 0 or NEB_RAYS_SORT */, const neb_gi_constants* constants,
+                       void* out /* neb_ray_path[n] */, void* vertices /* NULL, or neb_path_vertex[n * (maxPathVertices - 1)] */, neb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -277,6 +277,13 @@ namespace Neb
         {
             ThrowIfFailed(m_svgf.Context(), neb_gi_shade_rays(m_svgf.Context(), rays, n, what, flags, constants, out, commandList), "neb_gi_shade_rays");
         }
+        // The same rays followed as the frame follows a path, up to constants->maxPathVertices - 1 segments (2..8): paths = neb_ray_path[n],
+        // the radiance summed along each; vertices = null, or neb_path_vertex[n * (maxPathVertices - 1)], one record per segment.  With
+        // maxPathVertices = 2 the record is NEB_SHADE_RADIANCE's.  flags: 0 or NEB_RAYS_SORT.  Only enqueues, as CastRays.
+        void TracePaths(const neb_ray* rays, uint32_t n, uint32_t flags, const neb_gi_constants* constants, void* paths, void* vertices, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_trace_paths(m_svgf.Context(), rays, n, flags, constants, paths, vertices, commandList), "neb_gi_trace_paths");
+        }
 
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const

@@ -223,6 +223,57 @@ class DeferredRenderer:
                 "primitive": ids[:, 11], "albedo": out[:, 12:15], "roughness": out[:, 15], "metalness": out[:, 16], "texcoord": out[:, 17:19],
                 "material": ids[:, 19], "u": out[:, 20], "v": out[:, 21], "flags": ids[:, 22], "records": out}
 
+    def trace_paths(self, rays, constants=None, max_path_vertices=None, sort=False, vertices=False, out=None, stream=None):
+        """Cast n rays as cast_rays does and follow each as the frame follows a pixel's path (neb_gi_trace_paths): up to
+        K - 1 segments, K = max_path_vertices (2..8; default: the constants' maxPathVertices), the sun's direct light at every vertex and
+        the sky where a segment misses.  Returns views of one [n, 8] float32 buffer (neb_ray_path) -- radiance [n, 3], t, geometry,
+        primitive, flags (of the first hit; _lib.HIT_* | _lib.PATH_ESCAPED), segments -- with the buffer under "records" (`out`, when
+        given).  vertices=True also returns one record per segment (neb_path_vertex) as views of one [n, K - 1, 24] buffer under
+        "vertex_records": origin, tmin, direction, vertex_t, throughput, rng, added, vertex_flags, vertex_geometry, vertex_primitive, u, v,
+        tmax, pdiff; a record past the path's end is zero.  `constants` (default: global_constants() of the frame) is not changed.  With
+        K = 2 the records are shade_rays("radiance")'s.  sort=True reorders the rays for coherence; the answers are the same bits.  The
+        call only enqueues on `stream`, behind every update enqueued before it; nothing is copied to the host."""
+        import torch
+        if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
+                and rays.is_contiguous()):
+            raise NebError("trace_paths: rays must be a contiguous float32 CUDA tensor [n, 8]")
+        n = rays.shape[0]
+        if constants is None:
+            constants = self.global_constants()
+        if max_path_vertices is not None:
+            constants = type(constants).from_buffer_copy(constants)
+            constants.maxPathVertices = int(max_path_vertices)
+        K = int(constants.maxPathVertices)
+        if not 2 <= K <= 8:
+            raise NebError("trace_paths: max_path_vertices must be 2..8")
+        if out is None:
+            with torch.cuda.device(rays.device):
+                out = torch.empty((n, 8), dtype=torch.float32, device=rays.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and out.is_contiguous()):
+            raise NebError(f"trace_paths: out must be a contiguous torch.float32 CUDA tensor of shape {(n, 8)}")
+        vert = None
+        if vertices is True:
+            with torch.cuda.device(rays.device):
+                vert = torch.empty((n, K - 1, 24), dtype=torch.float32, device=rays.device)
+        elif vertices is not False and vertices is not None:
+            vert = vertices
+            if not (isinstance(vert, torch.Tensor) and vert.is_cuda and vert.dtype == torch.float32 and tuple(vert.shape) == (n, K - 1, 24)
+                    and vert.is_contiguous()):
+                raise NebError(f"trace_paths: vertices must be a bool or a contiguous torch.float32 CUDA tensor of shape {(n, K - 1, 24)}")
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        rc = self._lib.neb_gi_trace_paths(self._ctx, C.c_void_p(rays.data_ptr() if n else 0), n, _lib.RAYS_SORT if sort else 0, C.byref(constants),
+                                          C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(vert.data_ptr() if vert is not None and n else 0), st)
+        self._check(rc, "neb_gi_trace_paths")
+        ids = out.view(torch.int32)
+        res = {"radiance": out[:, 0:3], "t": out[:, 3], "geometry": ids[:, 4], "primitive": ids[:, 5], "flags": ids[:, 6], "segments": ids[:, 7], "records": out}
+        if vert is not None:
+            vi = vert.view(torch.int32)
+            res.update({"origin": vert[..., 0:3], "tmin": vert[..., 3], "direction": vert[..., 4:7], "vertex_t": vert[..., 7], "throughput": vert[..., 8:11],
+                        "rng": vi[..., 11], "added": vert[..., 12:15], "vertex_flags": vi[..., 15], "vertex_geometry": vi[..., 16],
+                        "vertex_primitive": vi[..., 17], "u": vert[..., 18], "v": vert[..., 19], "tmax": vert[..., 20], "pdiff": vert[..., 21],
+                        "vertex_records": vert})
+        return res
+
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
         n = C.c_uint32(0)
