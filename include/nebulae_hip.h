@@ -990,6 +990,71 @@ typedef struct neb_path_vertex { /* 96 bytes, three 32-byte sectors */
 int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags /* 0 or NEB_RAYS_SORT */, const neb_gi_constants* constants,
                        void* out /* neb_ray_path[n] */, void* vertices /* NULL, or neb_path_vertex[n * (maxPathVertices - 1)] */, neb_stream stream);
 
+/* Probe baking: S path samples per probe generated, followed and reduced on the device, one 128-byte record per probe
+ * -- second-order spherical harmonics of the incoming radiance (NEB_BAKE_SH: an irradiance probe) or the irradiance of a surface point
+ * (NEB_BAKE_IRRADIANCE: a lightmap texel).  NO reference counterpart as a call.
+ * `probes` and `out` (neb_gi_probe_rays: `rays`) are DEVICE pointers, as neb_gi_trace_paths takes them: probes and rays 16-byte
+ * aligned, out 32-byte aligned, the two ranges of a call not overlapping.  samples = S is a multiple of 64 in 64..4096 and n * S <= 2^28.
+ * Sample s of probe p is ray index i = p * S + s.  neb_gi_probe_rays writes these n * S rays; neb_gi_bake_probes follows, for every i,
+ * EXACTLY the path neb_gi_trace_paths follows for ray i of a call over those rays with the same constants (the same stream rng =
+ * JenkinsHash(i ^ JenkinsHash(frameIndex)), the same arithmetic policy, maxPathVertices 2..8), the first segment over the probe's
+ * (tmin, tmax), and reduces the path radiances L_i.  So neb_gi_bake_probes(...) == reduce(neb_gi_trace_paths(neb_gi_probe_rays(...)))
+ * bit for bit, at 0 bytes of scratch memory against 64 bytes per sample.
+ * DIRECTIONS, one IEEE operation per step under both policies (no contraction, the roundings as written), from a stream of their own:
+ *   rng_d = JenkinsHash(~i ^ JenkinsHash(frameIndex + 0x9E3779B9));  r0 = Rand(rng_d);  r1 = Rand(rng_d);
+ *   u0 = (float(s) + r0) / float(S)       (a sum, then an IEEE division: one stratum of [0, 1] per sample);   u1 = r1
+ *   NEB_BAKE_SH (the whole sphere, uniform; `normal` is ignored):
+ *     z = 1 - 2 * u0;  rho = sqrt(max(0, 1 - z * z))  (IEEE square root);  (sin, cos) = det_sincosf(6.2831853f * u1)
+ *     d = (rho * cos, rho * sin, z) / sqrt((x * x + y * y) + z * z)        (IEEE square root, three IEEE divisions)
+ *   NEB_BAKE_IRRADIANCE (cosine-distributed about the normal):
+ *     N = normal / sqrt((nx * nx + ny * ny) + nz * nz);  d = the bounce sample of the frame about N with (u0, u1) in its exact form
+ *     (brdf.hlsli:166-185 with IEEE sqrt and division and det_sincosf: cosine_hemisphere_aligned<false> of the library)
+ * det_sincosf is the fixed sequence the frame uses for its bounce directions (the same text in the library and in oracle/trace_ref.cpp).
+ * PROJECTION, per sample, every product and difference rounded by itself (no fused multiply-add anywhere):
+ *   Y00 = 0.282095f;  Y1-1 = 0.488603f * y;  Y10 = 0.488603f * z;  Y11 = 0.488603f * x;  Y2-2 = 1.092548f * (x * y);
+ *   Y2-1 = 1.092548f * (y * z);  Y20 = 0.315392f * ((3 * z) * z - 1);  Y21 = 1.092548f * (x * z);  Y22 = 0.546274f * (x * x - y * y)
+ *   word[3 * lm + c] = L.c * Y_lm  (NEB_BAKE_SH, 27 words);  word[c] = L.c  (NEB_BAKE_IRRADIANCE, 3 words)
+ * REDUCTION, round-major: for r = 0 .. S / 64 - 1 the 64 samples s = 64 r + l, l = 0 .. 63, are reduced per word by a butterfly over
+ * the masks 32, 16, 8, 4, 2, 1 in this order -- v[l] = v[l] + v[l ^ m] for every l at once -- and the round's sum (v[0]) is added to
+ * the running total, which starts at +0, in round order; the total is multiplied ONCE by float(4 pi / S) (SH) or float(3.14159265f /
+ * S) (irradiance: E = pi * mean(L)), the factor computed in double and rounded once.  hits, backfaces and segments are exact integer sums.
+ * A probe is NOT BAKED -- its record all zero but flags = NEB_PROBE_NOT_BAKED, samples = 0, no walk made; neb_gi_probe_rays writes S
+ * rays of zeroes for it, which the queries report as NEB_HIT_NOT_WALKED -- if the position's squared length (x x + y y) + z z is not
+ * finite in float (a component that is not finite, or above about 1.8e19: the origins neb_gi_cast_rays does not walk from), tmin is not
+ * >= 0 or tmax is not > tmin (a NaN says no), or, under NEB_BAKE_IRRADIANCE, the normal's squared length is not positive and finite in
+ * float (a normal below about 1e-19 in every component is a zero normal).  Both squared lengths are formed with every product and sum
+ * rounded by itself.
+ * A baked probe's record does not depend on which other probes are in the call, except through i.
+ * Everything else is neb_gi_trace_paths': the call only enqueues on `stream`, behind every update call enqueued before it on any stream
+ * (an update enqueued after it waits for it); it allocates nothing; hidden submeshes are absent; every shadow ray is walked; of the
+ * constants only frameIndex, maxPathVertices, skyColor and the three sun fields are read; neb_gi_ray_count, the traversal statistics,
+ * the sun table and every plane are left untouched.  To refine a bake, average the records of calls with different frameIndex.
+ * neb_gi_probe_rays needs a context but no scene.
+ * Refusals, each enqueuing nothing: NEB_ERR_STATE without a built tree (bake); NEB_ERR_INVALID_ARG for an unknown `what`, samples
+ * not a multiple of 64 in 64..4096, flags other than 0 (NEB_RAYS_SORT with a message of its own: a wave's rays share their origin),
+ * null constants, maxPathVertices outside 2..8, a null, misaligned or unreadable pointer (or a range that leaves its allocation) and
+ * for overlapping ranges; NEB_ERR_OUT_OF_RANGE for n * samples above 2^28.  n == 0 (with valid `what` and samples) succeeds and looks
+ * at no pointer. */
+typedef struct neb_probe { /* 32 bytes, the layout of neb_ray */
+    float position[3], tmin; /* the first segment's interval: tmin > 0 keeps samples off the surface a texel lies on */
+    float normal[3], tmax;   /* normal: NEB_BAKE_IRRADIANCE only, need not be normalised */
+} neb_probe;
+typedef struct neb_probe_record { /* 128 bytes, four 32-byte sectors */
+    float sh[9][3];     /* NEB_BAKE_SH: coefficient (l,m) x rgb in the order above; NEB_BAKE_IRRADIANCE: sh[0] = E, the other 24 words 0 */
+    uint32_t samples;   /* S, or 0 for a probe that was not baked */
+    uint32_t hits;      /* samples whose first segment found a hit (NEB_HIT_FOUND) */
+    uint32_t backfaces; /* ... of those, first hits flagged NEB_HIT_BACKFACE (a probe inside geometry shows here) */
+    uint32_t segments;  /* sum of neb_ray_path.segments over the samples */
+    uint32_t flags;     /* NEB_PROBE_NOT_BAKED */
+} neb_probe_record;
+#define NEB_BAKE_SH 0u
+#define NEB_BAKE_IRRADIANCE 1u
+#define NEB_PROBE_NOT_BAKED 1u
+int neb_gi_probe_rays(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t frame_index,
+                      neb_ray* rays /* n * samples */, neb_stream stream);
+int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags /* 0 */,
+                       const neb_gi_constants* constants, neb_probe_record* out /* n */, neb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -285,6 +285,20 @@ namespace Neb
             ThrowIfFailed(m_svgf.Context(), neb_gi_trace_paths(m_svgf.Context(), rays, n, flags, constants, paths, vertices, commandList), "neb_gi_trace_paths");
         }
 
+        // Probe baking: ProbeRays writes the n * samples rays of n probes (sample s of probe p is ray p * samples + s; what = NEB_BAKE_SH: the
+        // sphere, NEB_BAKE_IRRADIANCE: cosine-distributed about the normal) and needs no scene; BakeProbes follows the same rays as TracePaths
+        // would and reduces them on the device to neb_probe_record[n] -- second-order SH of the incoming radiance, or the irradiance -- with no
+        // buffer for rays or paths.  samples: a multiple of 64 in 64..4096; flags: 0.  Only enqueues, as CastRays.
+        void ProbeRays(const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t frameIndex, neb_ray* rays, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_probe_rays(m_svgf.Context(), probes, n, samples, what, frameIndex, rays, commandList), "neb_gi_probe_rays");
+        }
+        void BakeProbes(const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags, const neb_gi_constants* constants,
+                        neb_probe_record* out, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_bake_probes(m_svgf.Context(), probes, n, samples, what, flags, constants, out, commandList), "neb_gi_bake_probes");
+        }
+
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const
         {

@@ -133,6 +133,21 @@ RAYS_ANY_HIT, RAYS_SORT = 1, 2  # NEB_RAYS_*: flags of neb_gi_cast_rays
 SHADE_SURFACE, SHADE_RADIANCE = 0, 1  # NEB_SHADE_*: `what` of neb_gi_shade_rays
 HIT_FOUND, HIT_ATTRIBUTES, HIT_MATERIAL, HIT_BACKFACE, HIT_NOT_WALKED, HIT_SUN_VISIBLE = 1, 2, 4, 8, 16, 32  # NEB_HIT_*: flags of its records
 PATH_ESCAPED, PATH_DIVIDED = 64, 128  # NEB_PATH_*: flags of neb_gi_trace_paths' records, beside NEB_HIT_*
+BAKE_SH, BAKE_IRRADIANCE = 0, 1  # NEB_BAKE_*: `what` of neb_gi_probe_rays / neb_gi_bake_probes
+PROBE_NOT_BAKED = 1  # NEB_PROBE_NOT_BAKED: flags of neb_probe_record
+
+
+class Probe(C.Structure):
+    """neb_probe"""
+    _fields_ = [("position", C.c_float * 3), ("tmin", C.c_float), ("normal", C.c_float * 3), ("tmax", C.c_float)]
+
+
+class ProbeRecord(C.Structure):
+    """neb_probe_record"""
+    _fields_ = [("sh", (C.c_float * 3) * 9), ("samples", C.c_uint32), ("hits", C.c_uint32), ("backfaces", C.c_uint32), ("segments", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -189,6 +204,8 @@ def _gi_sigs():
         "neb_gi_cast_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
         "neb_gi_shade_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p]),
         "neb_gi_trace_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p, C.c_void_p]),
+        "neb_gi_probe_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+        "neb_gi_bake_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p]),
         "neb_svgf_set_camera": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(S.CameraDesc)]),
         "neb_strip_frame": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p, C.POINTER(StripPlan), C.c_void_p]),
         "neb_strip_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),

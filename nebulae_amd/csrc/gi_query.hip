@@ -183,6 +183,7 @@ static_assert(sizeof(neb_ray_path) == 32 && offsetof(neb_ray_path, segments) == 
 // sum and later vertices add to it, so that with max_vertices = 2 the record is NEB_SHADE_RADIANCE's, bit for bit.
 // VERTICES: record i * (max_vertices - 1) + (k - 1) describes segment k of ray i, six 16-byte stores; a record past the path's end is
 // written as zeroes.
+// The loop itself is path_segments.h, one text that probe_bake_kernel (below) includes too.
 template <bool SORTED, bool FAST, bool VERTICES>
 __global__ __launch_bounds__(64) void ray_path_kernel(SceneView S, const ShadeHeader* __restrict__ heads, const float4* __restrict__ rays, uint32_t n,
                                                       const uint32_t* __restrict__ order, ShadeSun sun, uint32_t max_vertices, float4* __restrict__ out,
@@ -202,123 +203,196 @@ __global__ __launch_bounds__(64) void ray_path_kernel(SceneView S, const ShadeHe
     const uint32_t last = max_vertices - 1u; // segments a path can have
     float4* vrec = VERTICES ? vertices + 6 * ((size_t)i * last) : nullptr;
 
-    bool alive = ray_walkable(o, dir, tmin, tmax);
-    uint32_t rng = jenkins(i ^ jenkins(sun.frame_index));
-    float3 throughput = f3(1.0f, 1.0f, 1.0f), sum = f3(0.0f, 0.0f, 0.0f);
-    float first_t = __builtin_inff();
-    uint32_t first_geometry = kNoId, first_primitive = kNoId, path_flags = alive ? 0u : (uint32_t)NEB_HIT_NOT_WALKED, segments = 0u;
-    uint32_t k = 1u;
-    for (; k <= last; ++k) {
-        if (__ballot(alive) == 0ull)
-            break;
-        Hit h;
-        const bool found = traverse(S, o, alive ? dir : f3(0.0f, 0.0f, 0.0f), tmin, tmax, false, stack, h);
-        // (a later segment the traverser refuses -- a direction that is not finite -- is a miss, as it is one in the frame)
-        uint32_t flags = alive && k > 1u && !ray_walkable(o, dir, tmin, tmax) ? (uint32_t)NEB_HIT_NOT_WALKED : 0u;
-        float t = __builtin_inff(), bu = 0.0f, bv = 0.0f;
-        uint32_t geometry = kNoId, primitive = kNoId;
-        float3 hitP = f3(0.0f, 0.0f, 0.0f);
-        Surface surf;
-        surf.GN = surf.SN = surf.albedo = f3(0.0f, 0.0f, 0.0f);
-        surf.roughness = surf.metalness = 0.0f;
-        if (found) { // (ray_shade_kernel's reconstruction, its flags)
-            const float4 ids = S.tris[3 * h.tri + 2]; // {e2.z, geometry, primitive, -}
-            const TriShade ts = load_tri_shade(S, h.tri);
-            const ShadeHead head = load_shade_header(heads, ts.geom);
-            float tex_u = 0.0f, tex_v = 0.0f;
-            t = h.t, bu = h.u, bv = h.v;
-            geometry = __float_as_uint(ids.y), primitive = __float_as_uint(ids.z);
-            hitP = o + dir * h.t;
-            flags |= NEB_HIT_FOUND;
-            const bool has_material = reconstruct_geometry<FAST>(head, ts, h.u, h.v, surf, tex_u, tex_v);
-            if (head.valid)
-                flags |= NEB_HIT_ATTRIBUTES | (dot3(surf.GN, dir) > 0.0f ? (uint32_t)NEB_HIT_BACKFACE : 0u);
-            if (has_material) {
-                MapSamples maps;
-                sample_material_maps<FAST>(S, head.mat, tex_u, tex_v, maps);
-                reconstruct_material<FAST>(head.mat, ts, h.u, h.v, maps, surf);
-                flags |= NEB_HIT_MATERIAL;
-            }
-        }
-        const bool shaded = (flags & NEB_HIT_MATERIAL) != 0;
-        // shade_pixel's shadow ray, its exact-arithmetic sequence under both policies; the two disk draws advance the path's stream
-        // where there is a surface to shade
-        const uint32_t rng_in = rng;
-        const float3 throughput_in = throughput;
-        uint32_t rng_disk = rng;
-        const float a0 = rand01(rng_disk), a1 = rand01(rng_disk);
-        const float angle = a0 * 2.0f * 3.1415926535f, dist = fsqrt<false>(a1);
-        float sn_a, cs_a;
-        det_sincosf(angle, sn_a, cs_a);
-        const float3 inc = normalize3<false>(L + (Bv * sn_a + T * cs_a) * sun.tan_half * dist);
-        const bool transition = dot3(surf.GN, inc) <= 0.0f;
-        const float3 so = hitP + (transition ? -surf.GN : surf.GN) * 1e-2f;
-        Hit sh;
-        const bool occluded = traverse(S, so, shaded ? inc : f3(0.0f, 0.0f, 0.0f), 0.001f, kTraceMax, true, stack, sh);
-        float3 added = f3(0.0f, 0.0f, 0.0f);
-        const float3 V = normalize3<FAST>(-dir); // :522
-        if (alive && !found) { // :508
-            added = f3(sun.sky[0], sun.sky[1], sun.sky[2]) * throughput;
-            path_flags |= NEB_PATH_ESCAPED;
-        }
-        if (shaded) {
-            rng = rng_disk;
-            if (!occluded) {
-                added = evaluate_direct_brdf<FAST>(surf, V, L) * f3(sun.radiance[0], sun.radiance[1], sun.radiance[2]) * throughput; // :573-574
-                flags |= NEB_HIT_SUN_VISIBLE;
-            }
-        }
-        if (alive) {
-            sum = k == 1u ? added : sum + added;
-            ++segments;
-        }
-        if (k == 1u) {
-            first_t = t, first_geometry = geometry, first_primitive = primitive;
-            path_flags |= flags;
-        }
-        float4 seg_o = make_float4(o.x, o.y, o.z, tmin), seg_d = make_float4(dir.x, dir.y, dir.z, t);
-        const float seg_tmax = tmax;
-        float pdiff = 0.0f;
-        const bool bounce = shaded && k < last; // (:579-583; `shaded` implies `alive`)
-        if (bounce) {
-            // EvaluateIndirectBRDF (:230-259) takes rng BY VALUE: the Rand(rng) of :614 returns the same number as the first of its draws
-            uint32_t rng_copy = rng;
-            const float3 SNn = normalize3<FAST>(surf.SN);
-            const float e0 = rand01(rng_copy), e1 = rand01(rng_copy);
-            const float3 Ld = cosine_hemisphere_aligned<FAST>(e0, e1, SNn);
-            pdiff = 1.0f - specular_probability<FAST>(saturate1(dot3(V, SNn)), specular_f0(surf.albedo, surf.metalness), surf.albedo);
-            o = hitP + surf.GN * 1e-2f; // :607
-            dir = Ld;
-            tmin = 0.001f, tmax = kTraceMax;
-            throughput = throughput * (surf.albedo * (1.0f - surf.metalness)); // :613
-            if (rand01(rng) < pdiff) {
-                throughput = f3(fdiv<FAST>(throughput.x, pdiff), fdiv<FAST>(throughput.y, pdiff), fdiv<FAST>(throughput.z, pdiff)); // :614-618
-                flags |= NEB_PATH_DIVIDED;
-            }
-        }
-        if constexpr (VERTICES) {
-            float4* rec = vrec + 6 * (size_t)(k - 1u);
-            if (alive) {
-                rec[0] = seg_o;
-                rec[1] = seg_d;
-                rec[2] = make_float4(throughput_in.x, throughput_in.y, throughput_in.z, __uint_as_float(rng_in));
-                rec[3] = make_float4(added.x, added.y, added.z, __uint_as_float(flags));
-                rec[4] = make_float4(__uint_as_float(geometry), __uint_as_float(primitive), bu, bv);
-                rec[5] = make_float4(seg_tmax, pdiff, 0.0f, 0.0f);
-            } else {
-                for (int q = 0; q < 6; ++q)
-                    rec[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            }
-        }
-        alive = bounce;
-    }
-    if constexpr (VERTICES)
-        for (; k <= last; ++k) // (the wave left the loop early: every record is written)
-            for (int q = 0; q < 6; ++q)
-                vrec[6 * (size_t)(k - 1u) + q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#include "path_segments.h" // -> sum, first_t, first_geometry, first_primitive, path_flags, segments
     float4* rec = out + 2 * (size_t)i;
     rec[0] = make_float4(sum.x, sum.y, sum.z, first_t);
     rec[1] = make_float4(__uint_as_float(first_geometry), __uint_as_float(first_primitive), __uint_as_float(path_flags), __uint_as_float(segments));
+}
+
+// ------------------------------------------------------------------------------------------------
+// neb_gi_probe_rays / neb_gi_bake_probes: S path samples per probe, generated, followed and reduced on the device
+// ------------------------------------------------------------------------------------------------
+static_assert(sizeof(neb_probe) == 32 && sizeof(neb_probe_record) == 128 && offsetof(neb_probe_record, samples) == 108 && offsetof(neb_probe_record, flags) == 124,
+              "records of neb_gi_bake_probes");
+constexpr uint32_t kProbeMaxSamples = 4096;
+// Waves per SIMD asked of probe_bake_kernel: ray_path_kernel's five under the default policy, four under the exact one.
+// -DNEB_PROBE_BAKE_FOUR_WAVES holds every instantiation to four: the A/B arm of DESIGN.md 3.8c's table, not a product build.
+#ifdef NEB_PROBE_BAKE_FOUR_WAVES
+#define NEB_PROBE_BAKE_OCCUPANCY amdgpu_waves_per_eu(4, 4)
+#else
+#define NEB_PROBE_BAKE_OCCUPANCY amdgpu_waves_per_eu(FAST ? 5 : 4)
+#endif
+
+// A product rounded by itself.  HIP's __fmul_rn is a plain operator, and the back end fuses a product into the sum that takes it
+// whatever a pragma says (gi_refit.hip's rounded_product): the empty statement is what the optimiser cannot see through.
+__device__ __forceinline__ float rounded_mul(float a, float b)
+{
+    float p = __fmul_rn(a, b);
+    asm volatile("" : "+v"(p));
+    return p;
+}
+// (x x + y y) + z z, every product and sum rounded by itself: the same bits as a float32 restatement, at the boundaries of 0 and overflow too
+__device__ __forceinline__ float rounded_square_length(float x, float y, float z)
+{
+    return __fadd_rn(__fadd_rn(rounded_mul(x, x), rounded_mul(y, y)), rounded_mul(z, z));
+}
+
+// Whether a probe is baked (include/nebulae_hip.h): a position whose squared length is finite -- ray_walkable's test of an origin, so
+// that "not baked" and "no sample could be walked" are the same probes --, an interval in order (interval_ok: a NaN on either side says
+// no) and, where the normal is used, one whose squared length is positive and finite.
+template <uint32_t WHAT> __device__ __forceinline__ bool probe_baked(float4 p0, float4 p1)
+{
+    const float inf = __builtin_inff();
+    bool ok = rounded_square_length(p0.x, p0.y, p0.z) < inf && interval_ok(p0.w, p1.w);
+    if (WHAT == NEB_BAKE_IRRADIANCE) {
+        const float nn = rounded_square_length(p1.x, p1.y, p1.z);
+        ok = ok && nn > 0.0f && nn < inf;
+    }
+    return ok;
+}
+
+// The direction of sample s of S, ray index i = p * S + s: the sequence of include/nebulae_hip.h, one IEEE operation per line of it, under
+// both shade policies.  Its two draws come from a stream of their own, so that they are independent of the path's.  `nrm` is
+// normalize3<false>(normal) (IRRADIANCE; unused otherwise).
+template <uint32_t WHAT> __device__ __forceinline__ float3 probe_direction(uint32_t i, uint32_t s, uint32_t samples, uint32_t frame_index, float3 nrm)
+{
+    uint32_t rng_d = jenkins(~i ^ jenkins(frame_index + 0x9E3779B9u));
+    const float r0 = rand01(rng_d), r1 = rand01(rng_d);
+    const float u0 = __fadd_rn((float)s, r0) / (float)samples, u1 = r1; // (one stratum of [0, 1] per sample in u0)
+    if (WHAT == NEB_BAKE_IRRADIANCE)
+        return cosine_hemisphere_aligned<false>(u0, u1, nrm);
+    const float z = __fsub_rn(1.0f, rounded_mul(2.0f, u0));
+    const float rho = sqrtf(fmaxf(0.0f, __fsub_rn(1.0f, rounded_mul(z, z)))); // (sqrtf and `/` are the correctly rounded forms in this build;
+                                                                             //  __fsqrt_rn is ocml's native, 1-ulp root)
+    float sn, cs;
+    det_sincosf(rounded_mul(kPiTwo, u1), sn, cs);
+    const float x = rounded_mul(rho, cs), y = rounded_mul(rho, sn);
+    const float l = sqrtf(rounded_square_length(x, y, z)); // normalize3<false>, its roundings spelled out
+    return f3(x / l, y / l, z / l);
+}
+
+// One lane per ray: ray p * S + s is sample s of probe p, origin and interval the probe's own bits; a probe that is not baked gets S
+// rays of zeroes, which every query reports as NEB_HIT_NOT_WALKED.
+template <uint32_t WHAT>
+__global__ __launch_bounds__(256) void probe_rays_kernel(const float4* __restrict__ probes, uint32_t n_rays, uint32_t samples, uint32_t frame_index,
+                                                         float4* __restrict__ rays)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_rays)
+        return;
+    const uint32_t p = i / samples, s = i - p * samples;
+    const float4 p0 = probes[2 * (size_t)p], p1 = probes[2 * (size_t)p + 1]; // {position, tmin} {normal, tmax}
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    if (probe_baked<WHAT>(p0, p1)) {
+        const float3 nrm = WHAT == NEB_BAKE_IRRADIANCE ? normalize3<false>(f3(p1.x, p1.y, p1.z)) : f3(0.0f, 0.0f, 0.0f);
+        const float3 d = probe_direction<WHAT>(i, s, samples, frame_index, nrm);
+        a = p0;
+        b = make_float4(d.x, d.y, d.z, p1.w);
+    }
+    rays[2 * (size_t)i] = a;
+    rays[2 * (size_t)i + 1] = b;
+}
+
+// One wave per probe, one wave per workgroup, ray_path_kernel's LDS stack.  Round r = 0 .. S / 64 - 1 gives lane l sample s = 64 r + l:
+// the lane builds the sample's direction (probe_direction), follows ray_path_kernel's path for ray index p * S + s (path_segments.h,
+// the same text) and forms its words L.c * Y_lm(d) -- 27 under NEB_BAKE_SH, the three L.c under NEB_BAKE_IRRADIANCE.  A butterfly over
+// the lane masks 32, 16, 8, 4, 2, 1 (v = v + v[lane ^ m]: both partners add the same two numbers, so every lane ends with the same sum)
+// reduces each word over the wave, and lane 0 adds the round's sums to the running totals IN ROUND ORDER.  The totals live in 128 bytes
+// of LDS, not in registers: they are no loop-carried state of the segment loop.  The counters are ballots and popcounts of the round,
+// which lane 0 adds to the record's words in LDS as well.  After the last round lane 0 multiplies the totals once by `scale` and lanes 0..7 write the record, one 16-byte store
+// each.  Every multiplication and addition of the projection is written with its rounding (no fused multiply-add anywhere in it).
+// A probe that is not baked costs one test and the same eight stores.
+template <uint32_t WHAT, bool FAST>
+__global__ __launch_bounds__(64) __attribute__((NEB_PROBE_BAKE_OCCUPANCY)) void probe_bake_kernel(
+    SceneView S, const ShadeHeader* __restrict__ heads, const float4* __restrict__ probes, uint32_t samples, ShadeSun sun, uint32_t max_vertices, float scale,
+    float4* __restrict__ out)
+{
+    constexpr bool VERTICES = false;
+    constexpr int kWords = WHAT == NEB_BAKE_SH ? 27 : 3;
+    __shared__ int stack_mem[kLdsStack * 64];
+    __shared__ float4 record[8]; // the probe's record: the running totals in words 0 .. 26
+    float* total = reinterpret_cast<float*>(record);
+    const uint32_t lane = threadIdx.x;
+    int* stack = stack_mem + lane;
+    const uint32_t p = blockIdx.x;
+    const float4 p0 = probes[2 * (size_t)p], p1 = probes[2 * (size_t)p + 1]; // {position, tmin} {normal, tmax}: the same for every lane
+    float4* rec = out + 8 * (size_t)p;
+    // (the same for every lane: read as a scalar, so that the branch is one and no execution mask is kept through the kernel)
+    if (!__builtin_amdgcn_readfirstlane((int)probe_baked<WHAT>(p0, p1))) {
+        if (lane < 8u)
+            rec[lane] = make_float4(0.0f, 0.0f, 0.0f, lane == 7u ? __uint_as_float(NEB_PROBE_NOT_BAKED) : 0.0f);
+        return;
+    }
+    if (lane < 32u)
+        total[lane] = 0.0f;
+    __syncthreads(); // (one wave: orders these writes before lane 0's additions)
+    uint32_t* const counter = reinterpret_cast<uint32_t*>(record) + 28; // hits, backfaces, segments: lane 0 adds to them too
+    const float3 L = f3(sun.L[0], sun.L[1], sun.L[2]), Bv = f3(sun.B[0], sun.B[1], sun.B[2]), T = f3(sun.T[0], sun.T[1], sun.T[2]);
+    const uint32_t last = max_vertices - 1u; // segments a path can have
+    float4* const vrec = nullptr;
+    for (uint32_t round = 0u; round < samples / 64u; ++round) {
+        // The probe again, two scalar loads per round, so that its eight words are not carried through the segment loop in scalar
+        // registers the kernel does not have.  (The empty statement keeps the compiler from hoisting the loads.)
+        const float4* probe = probes + 2 * (size_t)p;
+        asm volatile("" : "+s"(probe));
+        const float4 q0 = probe[0], q1 = probe[1];
+        const uint32_t s = 64u * round + lane, i = p * samples + s;
+        const float3 nrm = WHAT == NEB_BAKE_IRRADIANCE ? normalize3<false>(f3(q1.x, q1.y, q1.z)) : f3(0.0f, 0.0f, 0.0f);
+        float tmin = q0.w, tmax = q1.w;
+        float3 o = f3(q0.x, q0.y, q0.z), dir = probe_direction<WHAT>(i, s, samples, sun.frame_index, nrm);
+#include "path_segments.h" // -> sum, first_t, first_geometry, first_primitive, path_flags, segments
+        (void)first_t, (void)first_geometry, (void)first_primitive;
+        float w[kWords];
+        if constexpr (WHAT == NEB_BAKE_SH) {
+            // The direction again, from the lane's number alone: three registers fewer to carry through the segment loop.  (The empty
+            // statement keeps the compiler from seeing that it is the value it had before the loop.)
+            uint32_t s2 = 64u * round + lane;
+            asm volatile("" : "+v"(s2));
+            const float3 d = probe_direction<WHAT>(p * samples + s2, s2, samples, sun.frame_index, nrm);
+            float Y[9]; // the real basis, (0,0) (1,-1) (1,0) (1,1) (2,-2) (2,-1) (2,0) (2,1) (2,2)
+            Y[0] = 0.282095f;
+            Y[1] = __fmul_rn(0.488603f, d.y);
+            Y[2] = __fmul_rn(0.488603f, d.z);
+            Y[3] = __fmul_rn(0.488603f, d.x);
+            Y[4] = __fmul_rn(1.092548f, __fmul_rn(d.x, d.y));
+            Y[5] = __fmul_rn(1.092548f, __fmul_rn(d.y, d.z));
+            Y[6] = __fmul_rn(0.315392f, __fsub_rn(rounded_mul(__fmul_rn(3.0f, d.z), d.z), 1.0f));
+            Y[7] = __fmul_rn(1.092548f, __fmul_rn(d.x, d.z));
+            Y[8] = __fmul_rn(0.546274f, __fsub_rn(rounded_mul(d.x, d.x), rounded_mul(d.y, d.y)));
+#pragma unroll
+            for (int q = 0; q < 9; ++q) { // (rounded before the butterfly adds them)
+                w[3 * q] = rounded_mul(sum.x, Y[q]);
+                w[3 * q + 1] = rounded_mul(sum.y, Y[q]);
+                w[3 * q + 2] = rounded_mul(sum.z, Y[q]);
+            }
+        } else {
+            w[0] = sum.x, w[1] = sum.y, w[2] = sum.z;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1)
+#pragma unroll
+            for (int q = 0; q < kWords; ++q)
+                w[q] = __fadd_rn(w[q], __shfl_xor(w[q], m, 64));
+        const bool hit = (path_flags & NEB_HIT_FOUND) != 0u;
+        const uint32_t round_hits = (uint32_t)__popcll(__ballot(hit)), round_backfaces = (uint32_t)__popcll(__ballot(hit && (path_flags & NEB_HIT_BACKFACE) != 0u));
+        const uint32_t round_segments = (uint32_t)__popcll(__ballot((segments & 1u) != 0u)) + 2u * (uint32_t)__popcll(__ballot((segments & 2u) != 0u))
+                                        + 4u * (uint32_t)__popcll(__ballot((segments & 4u) != 0u)); // (segments <= 7)
+        if (lane == 0u) {
+#pragma unroll
+            for (int q = 0; q < kWords; ++q)
+                total[q] = __fadd_rn(total[q], w[q]);
+            counter[0] += round_hits, counter[1] += round_backfaces, counter[2] += round_segments;
+        }
+    }
+    if (lane == 0u) {
+#pragma unroll
+        for (int q = 0; q < kWords; ++q)
+            total[q] = __fmul_rn(total[q], scale);
+        counter[-1] = samples;
+    }
+    __syncthreads(); // (one wave: orders lane 0's LDS writes before the other lanes' reads)
+    if (lane < 8u)
+        rec[lane] = record[lane];
 }
 
 struct QueryBox {
@@ -607,5 +681,116 @@ extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n,
         g->query_ev_pending = true;
     }
     GI_HIP(ctx, launched);
+    return NEB_OK;
+}
+
+namespace {
+
+// What the two probe calls check of `what` and `samples` before anything else, with the caller's name in front.
+int probe_shape(neb_ctx* ctx, const char* who, uint32_t what, uint32_t samples, uint32_t n)
+{
+    char msg[160];
+    if (what != NEB_BAKE_SH && what != NEB_BAKE_IRRADIANCE) {
+        snprintf(msg, sizeof(msg), "%s: unknown `what` (NEB_BAKE_SH or NEB_BAKE_IRRADIANCE)", who);
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, msg);
+    }
+    if (samples < 64u || samples > kProbeMaxSamples || (samples & 63u)) {
+        snprintf(msg, sizeof(msg), "%s: samples must be a multiple of 64 in 64..4096", who);
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, msg);
+    }
+    if ((uint64_t)n * samples > kQueryMaxRays) {
+        snprintf(msg, sizeof(msg), "%s: more than 2^28 samples (n * samples) in one call", who);
+        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, msg);
+    }
+    return NEB_OK;
+}
+
+} // namespace
+
+extern "C" int neb_gi_probe_rays(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t frame_index, neb_ray* rays,
+                                 neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    if (int rc = probe_shape(ctx, "neb_gi_probe_rays", what, samples, n))
+        return rc;
+    if (n == 0)
+        return NEB_OK;
+    const size_t probe_bytes = (size_t)n * sizeof(neb_probe), ray_bytes = (size_t)n * samples * sizeof(neb_ray);
+    if (!probes || !rays)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_probe_rays: null probes or rays");
+    if (((uintptr_t)probes & 15u) || ((uintptr_t)rays & 15u))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_probe_rays: misaligned pointer (probes, rays: 16 bytes)");
+    if (ranges_overlap(probes, probe_bytes, rays, ray_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_probe_rays: rays overlaps probes");
+    GI_GUARD(ctx);
+    if (!device_readable(ctx, probes, probe_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_probe_rays: probes is not memory this context's device reads, or n probes leave its allocation");
+    if (!device_readable(ctx, rays, ray_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_probe_rays: rays is not memory this context's device reads, or n * samples rays leave its allocation");
+    hipStream_t stream = (hipStream_t)stream_;
+    const uint32_t n_rays = n * samples;
+    const float4* p4 = reinterpret_cast<const float4*>(probes);
+    float4* r4 = reinterpret_cast<float4*>(rays);
+    if (what == NEB_BAKE_SH)
+        hipLaunchKernelGGL(probe_rays_kernel<NEB_BAKE_SH>, dim3((n_rays + 255u) / 256u), dim3(256), 0, stream, p4, n_rays, samples, frame_index, r4);
+    else
+        hipLaunchKernelGGL(probe_rays_kernel<NEB_BAKE_IRRADIANCE>, dim3((n_rays + 255u) / 256u), dim3(256), 0, stream, p4, n_rays, samples, frame_index, r4);
+    GI_HIP(ctx, hipGetLastError());
+    return NEB_OK;
+}
+
+extern "C" int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags,
+                                  const neb_gi_constants* constants, neb_probe_record* out, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    GiState* g = ctx->gi;
+    if (!g || !g->built)
+        return gi_fail(ctx, NEB_ERR_STATE, "neb_gi_bake_probes: scene/BVH not ready");
+    if (flags)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, flags & NEB_RAYS_SORT ? "neb_gi_bake_probes: NEB_RAYS_SORT is not a flag of this call (a wave's rays share their origin)"
+                                                                       : "neb_gi_bake_probes: unknown flag bits (flags must be 0)");
+    if (int rc = probe_shape(ctx, "neb_gi_bake_probes", what, samples, n))
+        return rc;
+    if (n == 0)
+        return NEB_OK;
+    if (!constants)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: null constants");
+    const uint32_t max_vertices = constants->maxPathVertices;
+    if (max_vertices < 2u || max_vertices > 8u)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: maxPathVertices outside 2..8");
+    const size_t probe_bytes = (size_t)n * sizeof(neb_probe), out_bytes = (size_t)n * sizeof(neb_probe_record);
+    if (!probes || !out)
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: null probes or out");
+    if (((uintptr_t)probes & 15u) || ((uintptr_t)out & 31u))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: misaligned pointer (probes: 16 bytes; out: 32 bytes)");
+    if (ranges_overlap(probes, probe_bytes, out, out_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: out overlaps probes");
+    GI_GUARD(ctx);
+    if (!device_readable(ctx, probes, probe_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: probes is not memory this context's device reads, or n probes leave its allocation");
+    if (!device_readable(ctx, out, out_bytes))
+        return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: out is not memory this context's device reads, or n records leave its allocation");
+    hipStream_t stream = (hipStream_t)stream_;
+    ShadeSun sun = {}; // (as neb_gi_trace_paths: no value of the sun fields is refused)
+    sun_frame(constants->sunLightDirection, sun.L, sun.B, sun.T);
+    for (int q = 0; q < 3; ++q) {
+        sun.radiance[q] = constants->sunLightRadiance[q];
+        sun.sky[q] = constants->skyColor[q];
+    }
+    sun.tan_half = constants->sunTanHalfAngle;
+    sun.frame_index = constants->frameIndex;
+    // the one factor of the reduction: 4 pi / S over the sphere, pi / S under the cosine density, in double and rounded once
+    const double pi = 3.14159265358979323846;
+    const float scale = what == NEB_BAKE_SH ? (float)(4.0 * pi / (double)samples) : (float)((double)kPi / (double)samples);
+    GI_HIP(ctx, gi_scene_reader(g, stream)); // behind any update enqueued on another stream; a later update waits for this stream
+    // {what, fast}: the arithmetic policy is the shade pass's ("gi_exact_shade")
+    using Kernel = void (*)(SceneView, const ShadeHeader*, const float4*, uint32_t, ShadeSun, uint32_t, float, float4*);
+    static const Kernel kernels[2][2] = {{probe_bake_kernel<NEB_BAKE_SH, false>, probe_bake_kernel<NEB_BAKE_SH, true>},
+                                         {probe_bake_kernel<NEB_BAKE_IRRADIANCE, false>, probe_bake_kernel<NEB_BAKE_IRRADIANCE, true>}};
+    hipLaunchKernelGGL(kernels[what == NEB_BAKE_IRRADIANCE][!g->exact_shade], dim3(n), dim3(64), 0, stream, g->view, g->shade_heads,
+                       reinterpret_cast<const float4*>(probes), samples, sun, max_vertices, scale, reinterpret_cast<float4*>(out));
+    GI_HIP(ctx, hipGetLastError());
     return NEB_OK;
 }

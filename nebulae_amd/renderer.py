@@ -274,6 +274,76 @@ class DeferredRenderer:
                         "vertex_records": vert})
         return res
 
+    # ---- probe baking: S path samples per probe, generated, followed and reduced on the device ----
+    @staticmethod
+    def _probe_args(who, probes, samples, what):
+        import torch
+        if what not in ("sh", "irradiance"):
+            raise NebError(f'{who}: what is "sh" or "irradiance"')
+        if not (isinstance(probes, torch.Tensor) and probes.is_cuda and probes.dtype == torch.float32 and probes.dim() == 2 and probes.shape[1] == 8
+                and probes.is_contiguous()):
+            raise NebError(f"{who}: probes must be a contiguous float32 CUDA tensor [n, 8]")
+        samples = int(samples)
+        if samples < 64 or samples > 4096 or samples % 64:
+            raise NebError(f"{who}: samples must be a multiple of 64 in 64..4096")
+        return probes.shape[0], samples, _lib.BAKE_SH if what == "sh" else _lib.BAKE_IRRADIANCE
+
+    def probe_rays(self, probes, samples=64, what="sh", frame_index=None, out=None, stream=None):
+        """The rays bake_probes follows (neb_gi_probe_rays): `probes` is a contiguous float32 CUDA tensor [n, 8], a row = {position xyz,
+        tmin, normal xyz, tmax}; returns a [n * samples, 8] float32 tensor of rays (`out`, when given), ray p * samples + s being sample s
+        of probe p: uniform over the sphere (what="sh") or cosine-distributed about the normal (what="irradiance"), origin and interval
+        the probe's own.  A probe that cannot be baked gets rays of zeroes.  `frame_index` seeds the directions (default: the frame's
+        -- what bake_probes takes from global_constants() -- or 0 where no frame has begun).  Needs no scene and no frame.  The call
+        only enqueues on `stream`."""
+        import torch
+        n, samples, what_id = self._probe_args("probe_rays", probes, samples, what)
+        shape = (n * samples, 8)
+        if out is None:
+            with torch.cuda.device(probes.device):
+                out = torch.empty(shape, dtype=torch.float32, device=probes.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+            raise NebError(f"probe_rays: out must be a contiguous torch.float32 CUDA tensor of shape {shape}")
+        if frame_index is None:
+            frame_index = self.info.frame_index if self.info else 0
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        rc = self._lib.neb_gi_probe_rays(self._ctx, C.c_void_p(probes.data_ptr() if n else 0), n, samples, what_id, int(frame_index) & 0xFFFFFFFF,
+                                         C.c_void_p(out.data_ptr() if n else 0), st)
+        self._check(rc, "neb_gi_probe_rays")
+        return out
+
+    def bake_probes(self, probes, samples=64, what="sh", constants=None, max_path_vertices=None, out=None, stream=None):
+        """Bake n probes on the device (neb_gi_bake_probes): `samples` path samples per probe (a multiple of 64 in
+        64..4096), each followed as trace_paths follows ray p * samples + s of probe_rays(probes, samples, what, constants.frameIndex),
+        and reduced to one record per probe.  what="sh": the nine second-order spherical-harmonics coefficients of the incoming
+        radiance, x rgb; what="irradiance": E = pi * mean(L) over cosine-distributed directions about the probe's normal (a lightmap
+        texel).  Returns views of one [n, 32] float32 buffer (neb_probe_record) -- sh [n, 9, 3] (irradiance: sh[:, 0] = E, the rest
+        0), irradiance [n, 3] (= sh[:, 0]), samples, hits, backfaces, segments, flags (int32; _lib.PROBE_NOT_BAKED) -- with the buffer
+        under "records" (`out`, when given).  `constants` (default: global_constants() of the frame) is not changed;
+        max_path_vertices (2..8) overrides its maxPathVertices.  The result equals the documented float32 reduction of trace_paths over
+        probe_rays bit for bit and needs none of their buffers.  The call only enqueues on `stream`, behind every update enqueued
+        before it; nothing is copied to the host."""
+        import torch
+        n, samples, what_id = self._probe_args("bake_probes", probes, samples, what)
+        if constants is None:
+            constants = self.global_constants()
+        if max_path_vertices is not None:
+            constants = type(constants).from_buffer_copy(constants)
+            constants.maxPathVertices = int(max_path_vertices)
+        if not 2 <= int(constants.maxPathVertices) <= 8:
+            raise NebError("bake_probes: max_path_vertices must be 2..8")
+        if out is None:
+            with torch.cuda.device(probes.device):
+                out = torch.empty((n, 32), dtype=torch.float32, device=probes.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 32) and out.is_contiguous()):
+            raise NebError(f"bake_probes: out must be a contiguous torch.float32 CUDA tensor of shape {(n, 32)}")
+        st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
+        rc = self._lib.neb_gi_bake_probes(self._ctx, C.c_void_p(probes.data_ptr() if n else 0), n, samples, what_id, 0, C.byref(constants),
+                                          C.c_void_p(out.data_ptr() if n else 0), st)
+        self._check(rc, "neb_gi_bake_probes")
+        ids = out.view(torch.int32)
+        return {"sh": out[:, 0:27].view(n, 9, 3), "irradiance": out[:, 0:3], "samples": ids[:, 27], "hits": ids[:, 28], "backfaces": ids[:, 29],
+                "segments": ids[:, 30], "flags": ids[:, 31], "records": out}
+
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
         n = C.c_uint32(0)
