@@ -381,6 +381,17 @@ const char* neb_strips_last_error(void); /* message of the last failed neb_strip
  * or `peers` = the neighbouring strips' contexts of a host that drives all strips from ONE thread (any devices: rows are pushed with
  * hipMemcpyPeerAsync; scheme ONCE only).  Such a host calls neb_strip_frame_begin for every strip, then neb_strip_frame_finish for every
  * strip, frame after frame; a host with a communicator calls neb_strip_frame (= begin + finish).
+ * The contract of `peers` (strip r on stream[r]; the streams may all be one stream or N different ones; the calls only enqueue, no host wait):
+ *   - strip r's inputs of the frame (its G-buffer, the direct term in radiance[cur], whatever else touches its planes) are enqueued on
+ *     stream[r] before neb_strip_frame_begin(r), and a strip keeps its stream from frame to frame (or the host orders its streams itself);
+ *   - ALL begin calls of a frame come before ANY finish call, from one thread, in any order inside a sweep, after each strip's neb_begin_frame.
+ *     A finish without its begin, a finish before a neighbour's begin, a second begin and a begin while a neighbour is still in the frame
+ *     before are refused with NEB_ERR_STATE before anything is enqueued;
+ *   - the rows cross an edge when the LATER of its two strips begins, each way on the sending strip's stream: behind the sender's temporal
+ *     pass (stream order), behind everything the receiver's stream holds up to its begin of this frame (the receiver's `inputs` event,
+ *     recorded where the two streams differ) and behind the receiver's previous frame (its `frame_done` event: the halo rows were that
+ *     frame's ping-pong buffer); the receiver's border rows of level 0 wait for the sender's `pushed` event, its interior rows for nothing.
+ * Tested with N contexts on N streams of ONE device; two devices have not run yet.
  * flags: NEB_STRIP_RESET_HISTORY = neb_svgf_reset_history first (the frame policy's reset, src/DeferredRenderer.cpp:601-609).
  * constants == NULL: no GI dispatch (radiance[cur] is complete as it is). */
 enum { NEB_STRIPS_ONCE = 0, NEB_STRIPS_PER_LEVEL = 1, NEB_STRIPS_OVERLAP = 2 };

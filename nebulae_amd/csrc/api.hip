@@ -249,7 +249,7 @@ int neb_destroy(neb_ctx* ctx)
     free_planes(ctx);
     for (hipEvent_t e : ctx->prof_events)
         (void)hipEventDestroy(e);
-    for (hipEvent_t e : {ctx->strip.ready, ctx->strip.done, ctx->strip.pushed, ctx->strip.frame_done})
+    for (hipEvent_t e : {ctx->strip.ready, ctx->strip.done, ctx->strip.pushed, ctx->strip.frame_done, ctx->strip.inputs})
         if (e)
             (void)hipEventDestroy(e);
     if (ctx->strip.xstream)
@@ -284,6 +284,7 @@ int neb_begin_frame(neb_ctx* ctx, uint32_t frame_index)
     ctx->cur = (int)(frame_index & 1u); // SVGFDenoiser.cpp:41-42
     ctx->hist = ctx->cur ^ 1;
     ++ctx->frame_serial;
+    ctx->strip.begun = ctx->strip.linked[0] = ctx->strip.linked[1] = false; // (a strip frame the host abandoned half way does not block the next)
     geometry_invalidate(ctx); // a new frame has a new G-buffer
     return NEB_OK;
 }

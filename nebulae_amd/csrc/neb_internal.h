@@ -238,6 +238,10 @@ struct neb_ctx {
         hipEvent_t pushed = nullptr;                // local transport: this strip's boundary rows are in its neighbours' halos
         hipEvent_t frame_done = nullptr;            // ... this strip's frame has been enqueued to its end (its halo rows may be overwritten after it)
         bool frame_done_recorded = false;
+        hipEvent_t inputs = nullptr;                // ... what its stream holds up to its neb_strip_frame_begin of this frame (a push into its rows from another stream waits for it)
+        hipStream_t stream = nullptr;               // the stream of that call: a neighbour that begins later enqueues this strip's push into it there
+        bool begun = false;                         // between this frame's neb_strip_frame_begin and _finish (neb_begin_frame clears it)
+        bool linked[2] = {false, false};            // [0] up, [1] down: both pushes across that edge are enqueued for this frame
     } strip;
     std::string last_error;
 };

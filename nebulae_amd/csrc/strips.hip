@@ -326,10 +326,10 @@ uint32_t strip_swaps(const StripRows& R, uint32_t n, neb_halo_swap out[2])
 int strip_sync(neb_ctx* ctx)
 {
     auto& s = ctx->strip;
-    if (s.xstream && s.ready && s.done && s.pushed && s.frame_done)
+    if (s.xstream && s.ready && s.done && s.pushed && s.frame_done && s.inputs)
         return NEB_OK;
     hipError_t e = s.xstream ? hipSuccess : hipStreamCreateWithFlags(&s.xstream, hipStreamNonBlocking);
-    for (hipEvent_t* ev : {&s.ready, &s.done, &s.pushed, &s.frame_done})
+    for (hipEvent_t* ev : {&s.ready, &s.done, &s.pushed, &s.frame_done, &s.inputs})
         if (e == hipSuccess && !*ev) // (a call that failed half way is completed by the next one)
             e = hipEventCreateWithFlags(ev, hipEventDisableTiming);
     if (e != hipSuccess)
@@ -362,18 +362,46 @@ int check_context(neb_ctx* ctx, const StripRows& R, const char* who)
     return NEB_OK;
 }
 
-// pushes rows [row0, row1) of (plane, slot) of `src` into the same rows of `dst` (another context: a neighbouring strip, any device)
-int push_rows(neb_ctx* src, neb_ctx* dst, int plane, int slot, uint32_t row0, uint32_t row1, hipStream_t stream)
+// pushes rows [row0, row1) of (plane, slot) of `src` into the same rows of `dst` (another context: a neighbouring strip, any device);
+// `who` = the context whose call this is (it gets the message)
+int push_rows(neb_ctx* who, neb_ctx* src, neb_ctx* dst, int plane, int slot, uint32_t row0, uint32_t row1, hipStream_t stream)
 {
     if (row0 < src->row_begin || row1 > src->row_end || row0 < dst->row_begin || row1 > dst->row_end || dst->W != src->W)
-        return strip_fail(src, NEB_ERR_OUT_OF_RANGE, "neb_strip_frame_begin: a neighbour's context does not hold the halo rows of this plan");
+        return strip_fail(who, NEB_ERR_OUT_OF_RANGE, "neb_strip_frame_begin: a neighbour's context does not hold the halo rows of this plan");
     const size_t pitch = (size_t)src->W * neb::kPlaneInfo[plane].bytes_per_px;
     const char* from = (const char*)src->planes[plane][slot] + (size_t)(row0 - src->row_begin) * pitch;
     char* to = (char*)dst->planes[plane][slot] + (size_t)(row0 - dst->row_begin) * pitch;
     if (dst->device == src->device)
-        STRIP_HIP(src, hipMemcpyAsync(to, from, (size_t)(row1 - row0) * pitch, hipMemcpyDeviceToDevice, stream));
+        STRIP_HIP(who, hipMemcpyAsync(to, from, (size_t)(row1 - row0) * pitch, hipMemcpyDeviceToDevice, stream));
     else
-        STRIP_HIP(src, hipMemcpyPeerAsync(to, dst->device, from, src->device, (size_t)(row1 - row0) * pitch, stream));
+        STRIP_HIP(who, hipMemcpyPeerAsync(to, dst->device, from, src->device, (size_t)(row1 - row0) * pitch, stream));
+    return NEB_OK;
+}
+
+// The local transport's push across one edge, once BOTH strips have begun the frame: rows [row0, row1) of `src`'s accumulated radiance and of its
+// variance go into `dst`'s halo, on src's stream (behind src's temporal pass), and there
+//   behind dst's `inputs`: whatever dst's stream held in front of its neb_strip_frame_begin also writes these rows -- the direct term over all
+//     resident rows, anything else its host enqueued -- and the history reset's copy reads them.  The event is recorded here, at the end of what
+//     dst's stream holds by now (dst has begun: all of that is in it), and only where the two strips run on different streams: on one stream
+//     the stream's order says the same and costs nothing;
+//   behind dst's `frame_done`: dst's halo rows of radiance[cur] were a ping-pong buffer of ITS previous frame's levels.
+// src's `pushed` is recorded again behind it: the neighbours' waits in neb_strip_frame_finish are made after every begin, so they take the last record.
+int push_halo(neb_ctx* who, neb_ctx* src, neb_ctx* dst, uint32_t row0, uint32_t row1)
+{
+    hipStream_t st = src->strip.stream;
+    const bool other_stream = dst->strip.stream != st || dst->device != src->device; // (the null stream is every device's)
+    if (other_stream) {
+        neb::DeviceGuard at_dst(dst->device);
+        STRIP_HIP(who, hipEventRecord(dst->strip.inputs, dst->strip.stream));
+    }
+    neb::DeviceGuard guard(src->device);
+    if (other_stream)
+        STRIP_HIP(who, hipStreamWaitEvent(st, dst->strip.inputs, 0));
+    if (dst->strip.frame_done_recorded)
+        STRIP_HIP(who, hipStreamWaitEvent(st, dst->strip.frame_done, 0));
+    STRIP_OK(push_rows(who, src, dst, NEB_PLANE_RADIANCE, src->cur, row0, row1, st));
+    STRIP_OK(push_rows(who, src, dst, NEB_PLANE_VARIANCE, 0, row0, row1, st));
+    STRIP_HIP(who, hipEventRecord(src->strip.pushed, st));
     return NEB_OK;
 }
 
@@ -410,6 +438,18 @@ int neb_strip_frame_begin(neb_ctx* ctx, const neb_gi_constants* constants, const
         return strip_fail(ctx, NEB_ERR_INVALID_ARG, "neb_strip_frame_begin: the local transport (peers) serves scheme NEB_STRIPS_ONCE only");
     if (peers && R.N > 1 && ((R.r > 0 && !peers->up) || (R.r + 1 < R.N && !peers->down)))
         return strip_fail(ctx, NEB_ERR_INVALID_ARG, "neb_strip_frame_begin: a neighbouring strip's context is missing");
+    const bool local = peers && R.N > 1 && R.L > 0; // local transport: rows travel between the contexts, ordered by their events
+    neb_ctx* nb[2] = {nullptr, nullptr};            // [0] the strip above, [1] the strip below
+    auto& sy = ctx->strip;
+    if (local) {
+        nb[0] = R.r > 0 ? peers->up : nullptr, nb[1] = R.r + 1 < R.N ? peers->down : nullptr;
+        // every strip begins, then every strip finishes: refused here, before anything is enqueued
+        if (sy.begun)
+            return strip_fail(ctx, NEB_ERR_STATE, "neb_strip_frame_begin: this strip has begun a frame that neb_strip_frame_finish has not ended");
+        for (int side = 0; side < 2; ++side)
+            if (nb[side] && nb[side]->strip.begun && nb[side]->strip.linked[side ^ 1])
+                return strip_fail(ctx, NEB_ERR_STATE, "neb_strip_frame_begin: a neighbouring strip has not finished its previous frame");
+    }
     if (plan->flags & NEB_STRIP_RESET_HISTORY)
         STRIP_OK(neb_svgf_reset_history(ctx, stream));
     if (constants)
@@ -417,21 +457,29 @@ int neb_strip_frame_begin(neb_ctx* ctx, const neb_gi_constants* constants, const
     if (R.N == 1) // one strip = the whole frame: the whole-frame calls (the fused chain when the context opted in)
         return neb_svgf_temporal(ctx, stream);
     STRIP_OK(neb_svgf_temporal_rows(ctx, R.gi0, R.gi1, stream));
-    if (peers && R.L > 0) {
-        // local transport: this strip's boundary rows of the accumulated radiance and of the variance go straight into the neighbours' halos.
-        // A neighbour's halo rows of radiance[cur] were a ping-pong buffer of ITS previous frame's levels: the push waits for that frame's end.
-        neb::DeviceGuard guard(ctx->device);
-        STRIP_OK(strip_sync(ctx));
+    if (local) {
+        // this strip's boundary rows of the accumulated radiance and of the variance go straight into the neighbours' halos, and theirs into this
+        // strip's -- across every edge whose other strip has begun the frame too (push_halo: a push waits for what the receiver's stream holds in
+        // front of ITS begin, which is enqueued only then).  The other edges are served by the neighbour's call, which comes before any
+        // neb_strip_frame_finish.
+        {
+            neb::DeviceGuard guard(ctx->device);
+            STRIP_OK(strip_sync(ctx));
+        }
+        sy.stream = (hipStream_t)stream;
+        sy.begun = true;
+        sy.linked[0] = sy.linked[1] = false;
         neb_halo_swap sw[2];
         const uint32_t n = strip_swaps(R, R.halo, sw);
         for (uint32_t k = 0; k < n; ++k) {
-            neb_ctx* peer = sw[k].peer < (int32_t)R.r ? peers->up : peers->down;
-            if (peer->strip.frame_done_recorded)
-                STRIP_HIP(ctx, hipStreamWaitEvent((hipStream_t)stream, peer->strip.frame_done, 0));
-            STRIP_OK(push_rows(ctx, peer, NEB_PLANE_RADIANCE, ctx->cur, sw[k].send_row0, sw[k].send_row1, (hipStream_t)stream));
-            STRIP_OK(push_rows(ctx, peer, NEB_PLANE_VARIANCE, 0, sw[k].send_row0, sw[k].send_row1, (hipStream_t)stream));
+            const int side = sw[k].peer < (int32_t)R.r ? 0 : 1;
+            neb_ctx* peer = nb[side];
+            if (!peer->strip.begun)
+                continue;
+            STRIP_OK(push_halo(ctx, ctx, peer, sw[k].send_row0, sw[k].send_row1));
+            STRIP_OK(push_halo(ctx, peer, ctx, sw[k].recv_row0, sw[k].recv_row1));
+            sy.linked[side] = peer->strip.linked[side ^ 1] = true;
         }
-        STRIP_HIP(ctx, hipEventRecord(ctx->strip.pushed, (hipStream_t)stream));
     }
     return NEB_OK;
 }
@@ -453,10 +501,16 @@ int neb_strip_frame_finish(neb_ctx* ctx, void* comm, const neb_strip_plan* plan,
         return strip_fail(ctx, NEB_ERR_INVALID_ARG, "neb_strip_frame_finish: more than one strip needs a transport (an RCCL communicator or the neighbours' contexts)");
     if (peers && R.scheme != NEB_STRIPS_ONCE)
         return strip_fail(ctx, NEB_ERR_INVALID_ARG, "neb_strip_frame_finish: the local transport (peers) serves scheme NEB_STRIPS_ONCE only");
+    auto& sy = ctx->strip;
+    if (peers && R.L > 0) { // the neighbours' rows are on their way only once every strip has begun: refused here, before anything is enqueued
+        if (!sy.begun)
+            return strip_fail(ctx, NEB_ERR_STATE, "neb_strip_frame_finish: without the neb_strip_frame_begin of this frame");
+        if ((R.r > 0 && !sy.linked[0]) || (R.r + 1 < R.N && !sy.linked[1]))
+            return strip_fail(ctx, NEB_ERR_STATE, "neb_strip_frame_finish: before the neb_strip_frame_begin of a neighbouring strip (every strip begins, then every strip finishes)");
+    }
     neb::DeviceGuard guard(ctx->device);
     STRIP_OK(strip_sync(ctx));
     hipStream_t st = (hipStream_t)stream;
-    auto& sy = ctx->strip;
     neb_halo_swap sw[2];
     const uint32_t L = R.L;
     for (uint32_t level = 0; level < L; ++level) {
@@ -483,7 +537,7 @@ int neb_strip_frame_finish(neb_ctx* ctx, void* comm, const neb_strip_plan* plan,
                 STRIP_OK(neb_svgf_atrous_level_rows(ctx, 0, top, bot, stream));
             if (comm) {
                 STRIP_HIP(ctx, hipStreamWaitEvent(st, sy.done, 0));
-            } else { // local transport: the neighbours pushed their rows in their neb_strip_frame_begin
+            } else { // local transport: the neighbours' rows were pushed when the later strip of each edge began (the last record of `pushed`)
                 if (R.r > 0)
                     STRIP_HIP(ctx, hipStreamWaitEvent(st, peers->up->strip.pushed, 0));
                 if (R.r + 1 < R.N)
@@ -514,6 +568,7 @@ int neb_strip_frame_finish(neb_ctx* ctx, void* comm, const neb_strip_plan* plan,
     if (peers) {
         STRIP_HIP(ctx, hipEventRecord(sy.frame_done, st));
         sy.frame_done_recorded = true;
+        sy.begun = sy.linked[0] = sy.linked[1] = false;
     }
     return NEB_OK;
 }

@@ -340,7 +340,8 @@ class StripRenderer(DeferredRenderer):
     def submit_strip_frame_local(self, phase, up, down, with_gi=True, stream=None):
         """The same frame for a host that drives ALL strips from one thread (several contexts, any devices): `phase` "begin" for every strip,
         then "finish" for every strip; up / down = the neighbouring StripRenderers (None at the image's edges).  Rows travel by
-        hipMemcpyPeerAsync between the contexts (scheme "once").  -> whether SVGF runs this frame."""
+        hipMemcpyPeerAsync between the contexts (scheme "once").  Every strip may have a stream of its own (RenderInfo.stream): its inputs of
+        the frame are enqueued there before its "begin", and it keeps the stream from frame to frame.  -> whether SVGF runs this frame."""
         import ctypes as C
 
         from . import _lib
