@@ -1039,7 +1039,8 @@ int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t f
  * Everything else is neb_gi_trace_paths': the call only enqueues on `stream`, behind every update call enqueued before it on any stream
  * (an update enqueued after it waits for it); it allocates nothing; hidden submeshes are absent; every shadow ray is walked; of the
  * constants only frameIndex, maxPathVertices, skyColor and the three sun fields are read; neb_gi_ray_count, the traversal statistics,
- * the sun table and every plane are left untouched.  To refine a bake, average the records of calls with different frameIndex.
+ * the sun table and every plane are left untouched.  To refine a bake, fold the records of calls with different frameIndex
+ * into one buffer with neb_gi_accumulate_probes (below).
  * neb_gi_probe_rays needs a context but no scene.
  * Refusals, each enqueuing nothing: NEB_ERR_STATE without a built tree (bake); NEB_ERR_INVALID_ARG for an unknown `what`, samples
  * not a multiple of 64 in 64..4096, flags other than 0 (NEB_RAYS_SORT with a message of its own: a wave's rays share their origin),
@@ -1065,6 +1066,71 @@ int neb_gi_probe_rays(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_
                       neb_ray* rays /* n * samples */, neb_stream stream);
 int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags /* 0 */,
                        const neb_gi_constants* constants, neb_probe_record* out /* n */, neb_stream stream);
+
+/* Probe volumes: the probes of a regular grid, a running mean of bakes kept on the device, and the irradiance a grid of
+ * NEB_BAKE_SH records gives at points -- bake -> accumulate -> gather with no record leaving the device.  NO reference counterpart.
+ * All three calls need a context but NO SCENE and no frame, as neb_gi_probe_rays does.  Each only enqueues on `stream`, allocates nothing
+ * and touches no plane, counter or sun table.  `probes`, `acc`, `add`, `records`, `points` and `out` are DEVICE pointers: probes and
+ * points 16-byte aligned, records (acc, add) and gather records (out) 32-byte aligned, the ranges of a call not overlapping.
+ * GRID.  Probe (x, y, z) has index x + nx * (y + ny * z) and sits at origin + float(x) * spacing per axis: ONE PRODUCT AND ONE SUM, EACH
+ * ROUNDED BY ITSELF (no fused multiply-add).  neb_gi_probe_grid writes exactly these bits, the normal (0, 0, 1) and the interval (tmin,
+ * tmax) it is given -- which it does not judge: neb_gi_bake_probes does --, and neb_gi_gather_probes forms a probe's position by the
+ * same two operations, so that a point copied from a probe coincides with it.  Its output feeds neb_gi_bake_probes unchanged.
+ * ACCUMULATION, per probe, with sa = acc.samples and sb = add.samples:
+ *   sb == 0 (not baked, or an empty record): acc keeps all its bits (nothing is stored);
+ *   sa == 0: acc becomes add, all 32 words -- a zeroed buffer is a valid start;
+ *   sa + sb does not fit 32 bits: acc keeps its words and gains NEB_PROBE_SATURATED;
+ *   otherwise  sh word = acc * wa + add * wb  (two products and a sum, each rounded by itself) with wa = float(double(sa) / double(sa +
+ *   sb)), wb = float(double(sb) / double(sa + sb)), each rounded once; samples = sa + sb; hits, backfaces and segments are sums that
+ *   stop at 2^32 - 1; flags = (acc.flags | add.flags) & ~NEB_PROBE_NOT_BAKED.
+ * It serves NEB_BAKE_SH and NEB_BAKE_IRRADIANCE records alike.
+ * GATHER, per point, DDGI's blend without its distance moments (light leaks through thin walls remain), one IEEE operation per step:
+ *   usable: (px px + py py) + pz pz finite and the normal's squared length, formed the same way, positive and finite -- the tests
+ *     neb_gi_bake_probes makes under NEB_BAKE_IRRADIANCE; tmin and tmax are not read.  Otherwise the record is zero but for
+ *     NEB_GATHER_NOT_GATHERED and no record of the grid is loaded.
+ *   N = normal / sqrt(nn)  (IEEE square root, three IEEE divisions)
+ *   per axis: t = (p - origin) / spacing (IEEE division);  tc = min(max(t, 0), float(dims - 1));  NEB_GATHER_CLAMPED if tc != t on any
+ *     axis;  base = min(uint(floor(tc)), max(dims - 2, 0));  f = tc - float(base).  An axis with dims == 1 has base = 0, f = 0 and only
+ *     its low corner: high corners along it are not loaded and their bit stays clear.  cell = bx + nx * (by + ny * bz).
+ *   corner c = cx + 2 cy + 4 cz, in this order:
+ *     w_tri = ((cx ? fx : 1 - fx) * (cy ? fy : 1 - fy)) * (cz ? fz : 1 - fz)
+ *     q = origin + float(base + c) * spacing  (the grid's two operations);  v = q - p;  vv = (vx vx + vy vy) + vz vz
+ *     d = ((vx Nx + vy Ny) + vz Nz) / sqrt(vv)  (IEEE), or 0 where vv == 0: the probe coincides with the point
+ *     h = (d + 1) * 0.5;  w_n = h * h + 0.2
+ *     valid = 0 if the record has samples == 0, or NEB_PROBE_NOT_BAKED, or float(backfaces) > backface_limit * float(samples)
+ *     w = valid ? w_tri * w_n : 0.  A corner with w == 0 contributes nothing: its bit is clear and its sh words are not used, so a NaN
+ *     among them cannot reach the result; the sh words of an invalid corner are not even loaded.
+ *   W = the sum of w over c in order from +0;  W == 0: NEB_GATHER_NO_PROBE, E = 0, weight = 0, corners = 0.  Otherwise r = 1 / W (IEEE)
+ *   and word k of the blend is the sum, over the contributing corners in order from +0, of (w * r) * sh[k] -- every product rounded.
+ *   Y_lm(N) by the projection's formulas above; k_lm = A_l * Y_lm with A = (3.14159265f, 2.0943951f, 0.78539816f) = (pi, 2 pi / 3, pi / 4)
+ *   E.c = max(0, sum over lm = 0 .. 8 in order from +0 of blend[3 lm + c] * k_lm)
+ * A point's answer does not depend on which other points are in the call or where it stands in it: the kernel fetches a cell's records
+ * once per wave where a wave's points share their cell and per lane where they do not, and both routes perform the operations above.
+ * Refusals, each enqueuing nothing: NEB_ERR_INVALID_ARG for a null grid, a dims of 0, more than 2^24 probes, an origin that is not
+ * finite, a spacing that is not finite and > 0, a backface_limit outside 0..1, a null, misaligned or unreadable pointer (or a range that
+ * leaves its allocation) and for overlapping ranges.  n == 0 (with a valid grid, where there is one) succeeds and looks at no pointer. */
+typedef struct neb_probe_grid { /* host struct, passed by pointer, 40 bytes */
+    float origin[3], spacing[3]; /* probe (x, y, z) sits at origin + (x, y, z) * spacing; spacing finite and > 0 */
+    uint32_t dims[3];            /* >= 1 each; dims[0] * dims[1] * dims[2] <= 2^24 */
+    float backface_limit;        /* a probe whose backfaces > backface_limit * samples is ignored by the gather; 0..1, 0.25 is DDGI's */
+} neb_probe_grid;
+typedef struct neb_probe_gather { /* 32 bytes per point */
+    float irradiance[3];          /* E at the point for its normal, >= 0 */
+    float weight;                 /* sum of the corner weights */
+    uint32_t corners;             /* bit (cx + 2 cy + 4 cz) set: that corner of the cell contributed */
+    uint32_t cell;                /* linear index of the cell's base probe */
+    uint32_t flags;               /* NEB_GATHER_* */
+    uint32_t reserved;            /* 0 */
+} neb_probe_gather;
+#define NEB_PROBE_SATURATED 2u     /* flags of neb_probe_record: an accumulation was refused because samples would pass 2^32 - 1 */
+#define NEB_GATHER_NO_PROBE 1u     /* every corner was ignored: E = 0, weight = 0 */
+#define NEB_GATHER_CLAMPED 2u      /* the point lies outside the grid's box and was clamped to it */
+#define NEB_GATHER_NOT_GATHERED 4u /* position or normal unusable: record zero but this flag */
+int neb_gi_probe_grid(neb_ctx* ctx, const neb_probe_grid* grid, float tmin, float tmax, neb_probe* probes /* nx * ny * nz */, neb_stream stream);
+int neb_gi_accumulate_probes(neb_ctx* ctx, neb_probe_record* acc, const neb_probe_record* add, uint32_t n, neb_stream stream);
+int neb_gi_gather_probes(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records /* nx * ny * nz, NEB_BAKE_SH */,
+                         const neb_probe* points /* n: position and normal read, tmin / tmax ignored */, uint32_t n,
+                         neb_probe_gather* out /* n */, neb_stream stream);
 
 #ifdef __cplusplus
 }

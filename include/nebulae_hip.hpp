@@ -299,6 +299,23 @@ namespace Neb
             ThrowIfFailed(m_svgf.Context(), neb_gi_bake_probes(m_svgf.Context(), probes, n, samples, what, flags, constants, out, commandList), "neb_gi_bake_probes");
         }
 
+        // Probe volumes: ProbeGrid writes the probes of a regular grid (what BakeProbes takes), AccumulateProbes folds one bake's records into
+        // a sample-weighted running mean (a zeroed `acc` is a valid start), GatherProbes blends the eight NEB_BAKE_SH records around each point
+        // into the irradiance for the point's normal (neb_probe_gather[n]).  None needs a scene.  Only enqueue, as CastRays.
+        void ProbeGrid(const neb_probe_grid& grid, float tmin, float tmax, neb_probe* probes, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_probe_grid(m_svgf.Context(), &grid, tmin, tmax, probes, commandList), "neb_gi_probe_grid");
+        }
+        void AccumulateProbes(neb_probe_record* acc, const neb_probe_record* add, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_accumulate_probes(m_svgf.Context(), acc, add, n, commandList), "neb_gi_accumulate_probes");
+        }
+        void GatherProbes(const neb_probe_grid& grid, const neb_probe_record* records, const neb_probe* points, uint32_t n, neb_probe_gather* out,
+                          neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_gather_probes(m_svgf.Context(), &grid, records, points, n, out, commandList), "neb_gi_gather_probes");
+        }
+
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const
         {

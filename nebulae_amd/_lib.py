@@ -135,6 +135,8 @@ HIT_FOUND, HIT_ATTRIBUTES, HIT_MATERIAL, HIT_BACKFACE, HIT_NOT_WALKED, HIT_SUN_V
 PATH_ESCAPED, PATH_DIVIDED = 64, 128  # NEB_PATH_*: flags of neb_gi_trace_paths' records, beside NEB_HIT_*
 BAKE_SH, BAKE_IRRADIANCE = 0, 1  # NEB_BAKE_*: `what` of neb_gi_probe_rays / neb_gi_bake_probes
 PROBE_NOT_BAKED = 1  # NEB_PROBE_NOT_BAKED: flags of neb_probe_record
+PROBE_SATURATED = 2  # NEB_PROBE_SATURATED: flags of neb_probe_record, set by neb_gi_accumulate_probes
+GATHER_NO_PROBE, GATHER_CLAMPED, GATHER_NOT_GATHERED = 1, 2, 4  # NEB_GATHER_*: flags of neb_probe_gather
 
 
 class Probe(C.Structure):
@@ -146,6 +148,17 @@ class ProbeRecord(C.Structure):
     """neb_probe_record"""
     _fields_ = [("sh", (C.c_float * 3) * 9), ("samples", C.c_uint32), ("hits", C.c_uint32), ("backfaces", C.c_uint32), ("segments", C.c_uint32),
                 ("flags", C.c_uint32)]
+
+
+class ProbeGrid(C.Structure):
+    """neb_probe_grid"""
+    _fields_ = [("origin", C.c_float * 3), ("spacing", C.c_float * 3), ("dims", C.c_uint32 * 3), ("backface_limit", C.c_float)]
+
+
+class ProbeGather(C.Structure):
+    """neb_probe_gather"""
+    _fields_ = [("irradiance", C.c_float * 3), ("weight", C.c_float), ("corners", C.c_uint32), ("cell", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
@@ -206,6 +219,9 @@ def _gi_sigs():
         "neb_gi_trace_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p, C.c_void_p]),
         "neb_gi_probe_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
         "neb_gi_bake_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p]),
+        "neb_gi_probe_grid": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+        "neb_gi_accumulate_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+        "neb_gi_gather_probes": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
         "neb_svgf_set_camera": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(S.CameraDesc)]),
         "neb_strip_frame": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p, C.POINTER(StripPlan), C.c_void_p]),
         "neb_strip_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),

@@ -344,6 +344,96 @@ class DeferredRenderer:
         return {"sh": out[:, 0:27].view(n, 9, 3), "irradiance": out[:, 0:3], "samples": ids[:, 27], "hits": ids[:, 28], "backfaces": ids[:, 29],
                 "segments": ids[:, 30], "flags": ids[:, 31], "records": out}
 
+    # ---- probe volumes: grid, running mean and irradiance gather, all on the device ----
+    @staticmethod
+    def _grid_arg(who, grid):
+        if not isinstance(grid, _lib.ProbeGrid):
+            raise NebError(f"{who}: grid must be a _lib.ProbeGrid (probe_grid returns one)")
+        dims = [int(d) for d in grid.dims]
+        count = dims[0] * dims[1] * dims[2]
+        if min(dims) < 1 or count > 1 << 24:
+            raise NebError(f"{who}: dims must be >= 1 each, with at most 2^24 probes")
+        if not all(np.isfinite(o) for o in grid.origin) or not all(np.isfinite(s) and s > 0 for s in grid.spacing):
+            raise NebError(f"{who}: origin must be finite, spacing finite and > 0")
+        if not 0.0 <= grid.backface_limit <= 1.0:
+            raise NebError(f"{who}: backface_limit must lie in 0..1")
+        return count
+
+    @staticmethod
+    def _records_arg(who, name, t, rows=None):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 32 and t.is_contiguous()
+                and (rows is None or t.shape[0] == rows)):
+            raise NebError(f"{who}: {name} must be a contiguous float32 CUDA tensor [{'n' if rows is None else rows}, 32]")
+        return t.shape[0]
+
+    def probe_grid(self, origin, spacing, dims, tmin=0.0, tmax=float("inf"), backface_limit=0.25, out=None, stream=None):
+        """The probes of a regular grid (neb_gi_probe_grid): returns (grid, probes) -- a _lib.ProbeGrid, which
+        gather_probes takes, and a [nx * ny * nz, 8] float32 CUDA tensor (`out`, when given) that bake_probes takes: probe
+        x + nx * (y + ny * z) at origin + (x, y, z) * spacing, normal (0, 0, 1), interval (tmin, tmax).  `spacing` is one number or
+        three.  backface_limit: a probe whose backfaces exceed this share of its samples is ignored by gather_probes.  Needs no scene
+        and no frame.  The call only enqueues on `stream`."""
+        import torch
+        origin = np.asarray(origin, np.float32).reshape(-1)
+        spacing = np.broadcast_to(np.asarray(spacing, np.float32).reshape(-1), (3,)) if np.size(spacing) in (1, 3) else np.zeros(0, np.float32)
+        dims_ = np.asarray(dims).reshape(-1)
+        if origin.size != 3 or spacing.size != 3 or dims_.size != 3 or (dims_ < 1).any() or (dims_ > 1 << 24).any():
+            raise NebError("probe_grid: origin and dims have three entries, spacing one or three; dims must be >= 1 each")
+        grid = _lib.ProbeGrid((C.c_float * 3)(*origin.tolist()), (C.c_float * 3)(*spacing.tolist()), (C.c_uint32 * 3)(*[int(d) for d in dims_]),
+                              float(backface_limit))
+        count = self._grid_arg("probe_grid", grid)
+        if out is None:
+            with torch.cuda.device(self.svgf.device):
+                out = torch.empty((count, 8), dtype=torch.float32, device=f"cuda:{self.svgf.device}")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (count, 8) and out.is_contiguous()):
+            raise NebError(f"probe_grid: out must be a contiguous torch.float32 CUDA tensor of shape {(count, 8)}")
+        rc = self._lib.neb_gi_probe_grid(self._ctx, C.byref(grid), float(tmin), float(tmax), C.c_void_p(out.data_ptr()), self._stream_arg(stream))
+        self._check(rc, "neb_gi_probe_grid")
+        return grid, out
+
+    def accumulate_probes(self, acc, add, stream=None):
+        """Fold one bake into a running mean on the device (neb_gi_accumulate_probes): `acc` and `add` are contiguous
+        float32 CUDA tensors [n, 32] of neb_probe_record ("records" of bake_probes, either mode).  Per probe acc becomes the
+        sample-weighted mean of the two, its counters their sums; a zeroed `acc` is a valid start, an `add` record that was not baked
+        changes nothing, and a probe whose samples would pass 2^32 - 1 keeps its words and gains _lib.PROBE_SATURATED.  Returns `acc`.
+        Needs no scene and no frame.  The call only enqueues on `stream`."""
+        n = self._records_arg("accumulate_probes", "acc", acc)
+        self._records_arg("accumulate_probes", "add", add, n)
+        if add.device != acc.device:
+            raise NebError("accumulate_probes: acc and add must lie on one device")
+        rc = self._lib.neb_gi_accumulate_probes(self._ctx, C.c_void_p(acc.data_ptr() if n else 0), C.c_void_p(add.data_ptr() if n else 0), n,
+                                                self._stream_arg(stream))
+        self._check(rc, "neb_gi_accumulate_probes")
+        return acc
+
+    def gather_probes(self, grid, records, points, out=None, stream=None):
+        """Irradiance at n points from a grid of SH records (neb_gi_gather_probes): `grid` is probe_grid's, `records` the
+        [nx * ny * nz, 32] float32 CUDA tensor of what="sh" records baked (and accumulated) for its probes, `points` a contiguous
+        float32 CUDA tensor [n, 8] in the layout of probes -- position and normal are read, the normal need not be normalised.  The
+        eight records around a point are blended with trilinear weights times DDGI's direction weight, probes that were not baked or
+        see too many backfaces left out, and the blend is convolved with the cosine lobe about the normal.  Returns views of one [n, 8]
+        float32 buffer (neb_probe_gather) -- irradiance [n, 3], weight, corners, cell, flags (int32; _lib.GATHER_*) -- with the buffer
+        under "records" (`out`, when given).  Needs no scene and no frame.  The call only enqueues on `stream`."""
+        import torch
+        count = self._grid_arg("gather_probes", grid)
+        self._records_arg("gather_probes", "records", records, count)
+        if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 8
+                and points.is_contiguous()):
+            raise NebError("gather_probes: points must be a contiguous float32 CUDA tensor [n, 8]")
+        if points.device != records.device:
+            raise NebError("gather_probes: records and points must lie on one device")
+        n = points.shape[0]
+        if out is None:
+            with torch.cuda.device(points.device):
+                out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and out.is_contiguous()):
+            raise NebError(f"gather_probes: out must be a contiguous torch.float32 CUDA tensor of shape {(n, 8)}")
+        rc = self._lib.neb_gi_gather_probes(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), C.c_void_p(points.data_ptr() if n else 0), n,
+                                            C.c_void_p(out.data_ptr() if n else 0), self._stream_arg(stream))
+        self._check(rc, "neb_gi_gather_probes")
+        ids = out.view(torch.int32)
+        return {"irradiance": out[:, 0:3], "weight": out[:, 3], "corners": ids[:, 4], "cell": ids[:, 5], "flags": ids[:, 6], "records": out}
+
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
         n = C.c_uint32(0)
