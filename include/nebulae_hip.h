@@ -1132,6 +1132,48 @@ int neb_gi_gather_probes(neb_ctx* ctx, const neb_probe_grid* grid, const neb_pro
                          const neb_probe* points /* n: position and normal read, tmin / tmax ignored */, uint32_t n,
                          neb_probe_gather* out /* n */, neb_stream stream);
 
+/* Probe-lit frames: the frame's G-buffer as the gather's points, and the gather's irradiance added to radiance[cur] as
+ * the frame's indirect diffuse term -- the stand-in for neb_gi_trace in a frame.  NO reference counterpart.
+ * Rows are those of neb_gi_trace_rows: image rows [row0, row1) inside the context's rows (a row-strip context holds [row_begin, row_end));
+ * neb_gi_probe_indirect is the _rows call over all the context's rows.  Neither call needs a scene: the planes may come from
+ * neb_gbuffer_raycast or from neb_upload_rows.  Both only enqueue on `stream` and allocate nothing; neither touches a counter, a GI
+ * record, a hit record or the sun table.  neb_gbuffer_points writes no plane; neb_gi_probe_indirect writes radiance[cur] and no other.
+ * POINT of pixel i (x + W * (y - row_begin) in the planes), the point neb_gi_trace's ray generation shades, one IEEE operation per step:
+ *   sky = (depth[cur][i] >> 24) == 0 (the stencil byte):  position = (0, 0, 0), normal = (0, 0, 0)
+ *   else position = the first three fp16 words of NEB_PLANE_WORLDPOS, each converted to float32 (exact);
+ *        (ex, ey) = the .zw fp16 words of NEB_PLANE_NORMAL[cur] converted likewise;  v = (ex, ey, (1 - |ex|) - |ey|);
+ *        if v.z < 0:  v.xy = ((1 - |v.y|) * (v.x > 0 ? 1 : -1), (1 - |v.x|) * (v.y > 0 ? 1 : -1))  (both from the old v.xy)
+ *        normal = v / sqrt((v.x v.x + v.y v.y) + v.z v.z)  (IEEE square root, three IEEE divisions)
+ *   tmin = 0.01f, tmax = +infinity.
+ * neb_gbuffer_points writes these 32 bytes per pixel, pixel (x, y) at index (y - row0) * W + x: a valid `points` of neb_gi_gather_probes
+ * -- whose usability rule answers NEB_GATHER_NOT_GATHERED for a sky pixel, or a pixel whose fp16 words hold an infinity or a NaN, with
+ * no special case -- and a valid `probes` of neb_gi_bake_probes(..., NEB_BAKE_IRRADIANCE).
+ * INDIRECT TERM, per pixel of the rows.  g = what neb_gi_gather_probes(grid, records, the pixel's POINT) returns: the same operations, the
+ * same bits.  g.flags with NEB_GATHER_NOT_GATHERED or NEB_GATHER_NO_PROBE: the pixel's 16 bytes of radiance are not stored to.
+ * Otherwise, with albedo = the R11G11B10 word of NEB_PLANE_ALBEDO decoded, metalness = the high fp16 word of NEB_PLANE_ROUGH_METAL:
+ *   k.c = albedo.c * (1 - metalness)                                     (the throughput ray generation starts from)
+ *   with NEB_INDIRECT_FRAME_WEIGHT:  k.c = k.c * e, where e is the expectation of the factor ray generation's draw applies to that
+ *     throughput -- it divides by pd where Rand < pd, so e = pd (1 / pd) + (1 - pd) = 2 - pd for pd > 0, else 1 --;
+ *     pd = 1 - Brdf_GetSpecularProbability(saturate(dot(normalize(V), normal)), F0, albedo), V = constants->cameraWorldPos - position,
+ *     F0 = lerp(0.04, albedo, metalness), every step as neb_gi_trace's ray generation performs it (float32, no fused multiply-add)
+ *   add.c = (k.c * g.irradiance.c) * (1 / 3.14159265f);   radiance.c = radiance.c + add.c       -- each product and the sum rounded
+ *   by itself; alpha keeps its bits.
+ * Without the flag the term is Lambert's albedo (1 - metalness) E / pi; with it a probe-lit frame converges toward what the traced frame
+ * converges toward.  Of the constants only cameraWorldPos is read, and only with the flag (else `constants` may be NULL).
+ * A pixel's answer does not depend on the rows of the call or on its neighbours: a wave takes an 8 x 8 pixel tile and the gather's
+ * wave-uniform or per-lane route, which perform the same operations.
+ * Refusals, each enqueuing nothing: NEB_ERR_INVALID_ARG for the grid as neb_gi_gather_probes refuses it, unknown flag bits,
+ * NEB_INDIRECT_FRAME_WEIGHT with null constants, a null, misaligned (records: 32 bytes, points: 16) or unreadable pointer (or a range
+ * that leaves its allocation), `records` overlapping the radiance plane, `points` overlapping a plane the call reads;
+ * NEB_ERR_OUT_OF_RANGE for rows outside the context's rows or row1 <= row0. */
+#define NEB_INDIRECT_FRAME_WEIGHT 1u
+int neb_gbuffer_points(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_probe* points /* (row1 - row0) * W */, neb_stream stream);
+int neb_gi_probe_indirect(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records /* nx * ny * nz, NEB_BAKE_SH */,
+                          const neb_gi_constants* constants /* read only with NEB_INDIRECT_FRAME_WEIGHT, else may be NULL */, uint32_t flags,
+                          neb_stream stream);
+int neb_gi_probe_indirect_rows(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records, const neb_gi_constants* constants,
+                               uint32_t flags, uint32_t row0, uint32_t row1, neb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

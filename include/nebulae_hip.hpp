@@ -316,6 +316,22 @@ namespace Neb
             ThrowIfFailed(m_svgf.Context(), neb_gi_gather_probes(m_svgf.Context(), &grid, records, points, n, out, commandList), "neb_gi_gather_probes");
         }
 
+        // Probe-lit frames: GBufferPoints writes the points ray generation shades at the pixels of rows [row0, row1) (what GatherProbes and
+        // BakeProbes take); ProbeIndirect adds the grid's irradiance at every pixel, weighted as the frame's diffuse term, to radiance[cur]
+        // -- the stand-in for the path-traced indirect term.  flags: 0 or NEB_INDIRECT_FRAME_WEIGHT (constants then needed).  rows: the
+        // context's own where row1 == 0.  Neither needs a scene.  Only enqueue, as CastRays.
+        void GBufferPoints(uint32_t row0, uint32_t row1, neb_probe* points, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gbuffer_points(m_svgf.Context(), row0, row1, points, commandList), "neb_gbuffer_points");
+        }
+        void ProbeIndirect(const neb_probe_grid& grid, const neb_probe_record* records, const neb_gi_constants* constants, uint32_t flags,
+                           neb_stream commandList, uint32_t row0 = 0, uint32_t row1 = 0)
+        {
+            const int rc = row1 == 0 ? neb_gi_probe_indirect(m_svgf.Context(), &grid, records, constants, flags, commandList)
+                                     : neb_gi_probe_indirect_rows(m_svgf.Context(), &grid, records, constants, flags, row0, row1, commandList);
+            ThrowIfFailed(m_svgf.Context(), rc, "neb_gi_probe_indirect");
+        }
+
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const
         {

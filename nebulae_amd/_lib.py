@@ -137,6 +137,7 @@ BAKE_SH, BAKE_IRRADIANCE = 0, 1  # NEB_BAKE_*: `what` of neb_gi_probe_rays / neb
 PROBE_NOT_BAKED = 1  # NEB_PROBE_NOT_BAKED: flags of neb_probe_record
 PROBE_SATURATED = 2  # NEB_PROBE_SATURATED: flags of neb_probe_record, set by neb_gi_accumulate_probes
 GATHER_NO_PROBE, GATHER_CLAMPED, GATHER_NOT_GATHERED = 1, 2, 4  # NEB_GATHER_*: flags of neb_probe_gather
+INDIRECT_FRAME_WEIGHT = 1  # NEB_INDIRECT_FRAME_WEIGHT: flags of neb_gi_probe_indirect
 
 
 class Probe(C.Structure):
@@ -222,6 +223,10 @@ def _gi_sigs():
         "neb_gi_probe_grid": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
         "neb_gi_accumulate_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "neb_gi_gather_probes": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+        "neb_gbuffer_points": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+        "neb_gi_probe_indirect": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.POINTER(S.GIConstants), C.c_uint32, C.c_void_p]),
+        "neb_gi_probe_indirect_rows": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.POINTER(S.GIConstants), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                 C.c_void_p]),
         "neb_svgf_set_camera": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(S.CameraDesc)]),
         "neb_strip_frame": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p, C.POINTER(StripPlan), C.c_void_p]),
         "neb_strip_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),

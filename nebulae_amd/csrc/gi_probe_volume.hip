@@ -212,25 +212,14 @@ __device__ __forceinline__ void gather_blend(const neb_probe_grid& G, const floa
     E = f3(fmaxf(0.0f, e[0]), fmaxf(0.0f, e[1]), fmaxf(0.0f, e[2]));
 }
 
-// One lane per point.  A lane whose point is usable finds its cell from the point alone; then one ballot asks whether every such lane
-// of the wave has the cell of the first of them.  Pixels and lightmap texels mostly do: that wave takes the UNIFORM arm of gather_blend,
-// lanes without a usable point riding along (their loads are the wave's, their result is not stored).  Any other wave takes the
-// per-lane arm with those lanes masked off.  No LDS, no atomics; the answer of a point is the same bits on both arms, since both
-// perform gather_blend's operations on the same operands.
-__global__ __launch_bounds__(256) void probe_gather_kernel(neb_probe_grid G, const float4* __restrict__ records, const float4* __restrict__ points, uint32_t n,
-                                                           float4* __restrict__ out)
+// A point's own part of the gather: is it usable, its unit normal, and per axis the cell's base probe and the fraction inside the cell.
+// p0 = {position, -}, p1 = {normal, -}; `live`: the lane has a point at all.  Both gather kernels call this, so a pixel's point is located
+// by the operations a point read from a buffer is.
+__device__ __forceinline__ bool locate_point(const neb_probe_grid& G, const float4& p0, const float4& p1, bool live, GatherPoint& P)
 {
-    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-    const bool live = i < n;
-    float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = p0;
-    if (live) {
-        p0 = points[2 * (size_t)i]; // {position, -} {normal, -}
-        p1 = points[2 * (size_t)i + 1];
-    }
     const float inf = __builtin_inff();
     const float nn = rounded_square_length(p1.x, p1.y, p1.z);
     const bool usable = live && rounded_square_length(p0.x, p0.y, p0.z) < inf && nn > 0.0f && nn < inf;
-    GatherPoint P;
     P.p = f3(p0.x, p0.y, p0.z);
     const float nl = sqrtf(nn);
     P.N = f3(p1.x / nl, p1.y / nl, p1.z / nl);
@@ -248,10 +237,16 @@ __global__ __launch_bounds__(256) void probe_gather_kernel(neb_probe_grid G, con
         P.f[a] = __fsub_rn(tc, (float)b);
     }
     P.cell = P.base[0] + G.dims[0] * (P.base[1] + G.dims[1] * P.base[2]);
+    return usable;
+}
 
-    float3 E = f3(0.0f, 0.0f, 0.0f);
-    float W = 0.0f;
-    uint32_t corners = 0u;
+// The choice between gather_blend's two arms, made once per wave (every lane of the wave calls this).
+__device__ __forceinline__ void gather_wave(const neb_probe_grid& G, const float4* __restrict__ records, const GatherPoint& P, bool usable, float3& E, float& W,
+                                            uint32_t& corners)
+{
+    E = f3(0.0f, 0.0f, 0.0f);
+    W = 0.0f;
+    corners = 0u;
     const unsigned long long gathering = __ballot(usable);
     if (gathering != 0ull) {
         const uint32_t leader = (uint32_t)__ffsll(gathering) - 1u;
@@ -261,6 +256,30 @@ __global__ __launch_bounds__(256) void probe_gather_kernel(neb_probe_grid G, con
         else if (usable)
             gather_blend<false>(G, records, P, P.cell, E, W, corners);
     }
+}
+
+// One lane per point.  A lane whose point is usable finds its cell from the point alone; then one ballot asks whether every such lane
+// of the wave has the cell of the first of them.  Pixels and lightmap texels mostly do: that wave takes the UNIFORM arm of gather_blend,
+// lanes without a usable point riding along (their loads are the wave's, their result is not stored).  Any other wave takes the
+// per-lane arm with those lanes masked off.  No LDS, no atomics; the answer of a point is the same bits on both arms, since both
+// perform gather_blend's operations on the same operands.
+__global__ __launch_bounds__(256) void probe_gather_kernel(neb_probe_grid G, const float4* __restrict__ records, const float4* __restrict__ points, uint32_t n,
+                                                           float4* __restrict__ out)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    const bool live = i < n;
+    float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = p0;
+    if (live) {
+        p0 = points[2 * (size_t)i]; // {position, -} {normal, -}
+        p1 = points[2 * (size_t)i + 1];
+    }
+    GatherPoint P;
+    const bool usable = locate_point(G, p0, p1, live, P);
+
+    float3 E;
+    float W;
+    uint32_t corners;
+    gather_wave(G, records, P, usable, E, W, corners);
     if (!live)
         return;
     float4 r0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -271,6 +290,94 @@ __global__ __launch_bounds__(256) void probe_gather_kernel(neb_probe_grid G, con
     }
     out[2 * (size_t)i] = r0;
     *reinterpret_cast<uint4*>(out + 2 * (size_t)i + 1) = r1;
+}
+
+// ------------------------------------------------------------------------------------------------
+// neb_gbuffer_points / neb_gi_probe_indirect: a frame's pixels as the gather's points
+// ------------------------------------------------------------------------------------------------
+struct FramePlanes {
+    const uint2* world_pos;    // 4 x fp16: xyz read
+    const uint32_t* normal;    // 2 words a pixel: word 1 holds the oct-packed shading normal (.zw), the only one read
+    const uint32_t* depth;     // D24 | stencil << 24: stencil 0 is sky
+    const uint32_t* albedo;    // R11G11B10
+    const uint32_t* rough_metal; // 2 x fp16: the high half is metalness
+    uint32_t W;
+};
+
+// The point gi_raygen shades at pixel i, by its expressions (gi.hip: worldPos, SN): p0 = {position, 0.01}, p1 = {shading normal, +inf}.
+// A sky pixel has position 0 and normal 0, which the gather's usability rule turns away by itself.
+__device__ __forceinline__ void pixel_point(const FramePlanes& F, size_t i, float4& p0, float4& p1)
+{
+    float3 worldPos = f3(0.0f, 0.0f, 0.0f), SN = worldPos;
+    if (F.depth[i] >> 24) {
+        const uint2 wp = F.world_pos[i];
+        worldPos = f3(half_bits_to_float(wp.x & 0xffffu), half_bits_to_float(wp.x >> 16), half_bits_to_float(wp.y & 0xffffu));
+        const uint32_t nzw = F.normal[2 * i + 1];
+        SN = oct_unpack(half_bits_to_float(nzw & 0xffffu), half_bits_to_float(nzw >> 16));
+    }
+    p0 = make_float4(worldPos.x, worldPos.y, worldPos.z, 0.01f);
+    p1 = make_float4(SN.x, SN.y, SN.z, __builtin_inff());
+}
+
+// One lane per pixel of rows first / W .. : two 16-byte stores.
+__global__ __launch_bounds__(256) void gbuffer_points_kernel(FramePlanes F, size_t first, uint32_t n, float4* __restrict__ points)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n)
+        return;
+    float4 p0, p1;
+    pixel_point(F, first + i, p0, p1);
+    points[2 * (size_t)i] = p0;
+    points[2 * (size_t)i + 1] = p1;
+}
+
+struct IndirectArgs {
+    neb_probe_grid G;
+    FramePlanes F;
+    float camera[3];
+    uint32_t row_begin, row0, row1, tiles_x, n_tiles, frame_weight;
+};
+
+// The fused pass: a wave owns an 8 x 8 pixel tile (gi.hip's gi_pixel), so that its pixels mostly share their grid cell and the wave takes
+// gather_blend's scalar-load arm; decode -> locate -> gather -> weight -> radiance += , no point or gather record in memory.  Four tiles
+// a block.  A pixel that is not gathered, or finds no probe, stores nothing.  No LDS, no atomics.  `records` and `radiance` are parameters
+// of their own, __restrict__: only then does the compiler know that the store at the end cannot reach a record, and keeps the scalar loads.
+__global__ __launch_bounds__(256) void probe_indirect_kernel(IndirectArgs a, const float4* __restrict__ records, float4* __restrict__ radiance)
+{
+    const uint32_t tile = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t tile_x = tile % a.tiles_x, tile_y = tile / a.tiles_x;
+    const uint32_t x = tile_x * 8u + (lane & 7u), y = a.row0 + tile_y * 8u + (lane >> 3);
+    const bool live = tile < a.n_tiles && x < a.F.W && y < a.row1;
+    const size_t i = live ? (size_t)(y - a.row_begin) * a.F.W + x : 0;
+    float4 p0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), p1 = p0;
+    if (live)
+        pixel_point(a.F, i, p0, p1);
+    GatherPoint P;
+    const bool usable = locate_point(a.G, p0, p1, live, P);
+    float3 E;
+    float W;
+    uint32_t corners;
+    gather_wave(a.G, records, P, usable, E, W, corners);
+    if (!usable || !(W > 0.0f))
+        return;
+    const float3 albedo = unpack_r11g11b10(a.F.albedo[i]);
+    const float metalness = half_bits_to_float(a.F.rough_metal[i] >> 16);
+    float3 k = albedo * (1.0f - metalness); // gi_raygen's throughput (:474)
+    if (a.frame_weight) {
+        // what gi_raygen's draw does to that throughput on average: with probability pd it is divided by pd, else kept, so the
+        // expectation of the factor is pd * (1 / pd) + (1 - pd) = 2 - pd; a pd that is not > 0 never passes `Rand < pd`: the factor is 1
+        const float3 worldPos = f3(p0.x, p0.y, p0.z), SN = f3(p1.x, p1.y, p1.z);
+        const float3 V = f3(a.camera[0], a.camera[1], a.camera[2]) - worldPos; // :431
+        const float3 F0 = specular_f0(albedo, metalness);
+        const float pd = 1.0f - specular_probability(saturate1(dot3(normalize3(V), SN)), F0, albedo);
+        const float factor = pd > 0.0f ? __fsub_rn(2.0f, pd) : 1.0f;
+        k = f3(rounded_mul(k.x, factor), rounded_mul(k.y, factor), rounded_mul(k.z, factor));
+    }
+    float4 r = radiance[i];
+    r.x = __fadd_rn(r.x, rounded_mul(rounded_mul(k.x, E.x), kPiInv));
+    r.y = __fadd_rn(r.y, rounded_mul(rounded_mul(k.y, E.y), kPiInv));
+    r.z = __fadd_rn(r.z, rounded_mul(rounded_mul(k.z, E.z), kPiInv));
+    radiance[i] = r;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -400,4 +507,115 @@ extern "C" int neb_gi_gather_probes(neb_ctx* ctx, const neb_probe_grid* grid, co
                        reinterpret_cast<const float4*>(records), reinterpret_cast<const float4*>(points), n, reinterpret_cast<float4*>(out));
     GI_HIP(ctx, hipGetLastError());
     return NEB_OK;
+}
+
+namespace neb {
+namespace {
+
+int rows_resident(neb_ctx* ctx, const char* who, uint32_t row0, uint32_t row1)
+{
+    if (row0 < ctx->row_begin || row1 > ctx->row_end || row1 <= row0) {
+        char msg[256];
+        snprintf(msg, sizeof(msg), "%s: rows [%u, %u) are empty or not among the context's rows [%u, %u)", who, row0, row1, ctx->row_begin, ctx->row_end);
+        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, msg);
+    }
+    return NEB_OK;
+}
+
+FramePlanes frame_planes(const neb_ctx* ctx)
+{
+    FramePlanes F;
+    F.world_pos = (const uint2*)ctx->planes[NEB_PLANE_WORLDPOS][0];
+    F.normal = (const uint32_t*)ctx->planes[NEB_PLANE_NORMAL][ctx->cur];
+    F.depth = (const uint32_t*)ctx->planes[NEB_PLANE_DEPTH][ctx->cur];
+    F.albedo = (const uint32_t*)ctx->planes[NEB_PLANE_ALBEDO][0];
+    F.rough_metal = (const uint32_t*)ctx->planes[NEB_PLANE_ROUGH_METAL][0];
+    F.W = ctx->W;
+    return F;
+}
+
+} // namespace
+} // namespace neb
+
+extern "C" int neb_gbuffer_points(neb_ctx* ctx, uint32_t row0, uint32_t row1, neb_probe* points, neb_stream stream_)
+{
+    static const char who[] = "neb_gbuffer_points";
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    if (int rc = rows_resident(ctx, who, row0, row1))
+        return rc;
+    const size_t n = (size_t)(row1 - row0) * ctx->W, point_bytes = n * sizeof(neb_probe);
+    if (n > 0xffffffffull)
+        return gi_fail(ctx, NEB_ERR_OUT_OF_RANGE, "neb_gbuffer_points: more than 2^32 - 1 pixels");
+    if (!points)
+        return fail(ctx, who, "null points");
+    if ((uintptr_t)points & 15u)
+        return fail(ctx, who, "misaligned pointer (points: 16 bytes)");
+    const size_t npx = (size_t)ctx->W * (ctx->row_end - ctx->row_begin);
+    const int read[3][2] = {{NEB_PLANE_WORLDPOS, 0}, {NEB_PLANE_NORMAL, ctx->cur}, {NEB_PLANE_DEPTH, ctx->cur}};
+    for (const auto& pl : read)
+        if (spans_overlap(points, point_bytes, ctx->planes[pl[0]][pl[1]], npx * kPlaneInfo[pl[0]].bytes_per_px))
+            return fail(ctx, who, "points overlaps a G-buffer plane the call reads");
+    if (int rc = svgf_flush_pending(ctx)) // (a held-back temporal pass is submitted before anything that follows it on the planes)
+        return rc;
+    GI_GUARD(ctx);
+    if (!device_readable(ctx, points, point_bytes))
+        return fail(ctx, who, "points is not memory this context's device reads, or the rows' points leave its allocation");
+    hipLaunchKernelGGL(gbuffer_points_kernel, dim3((uint32_t)((n + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream_, frame_planes(ctx),
+                       (size_t)(row0 - ctx->row_begin) * ctx->W, (uint32_t)n, reinterpret_cast<float4*>(points));
+    GI_HIP(ctx, hipGetLastError());
+    return NEB_OK;
+}
+
+extern "C" int neb_gi_probe_indirect_rows(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records, const neb_gi_constants* constants,
+                                          uint32_t flags, uint32_t row0, uint32_t row1, neb_stream stream_)
+{
+    static const char who[] = "neb_gi_probe_indirect";
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    uint32_t count = 0;
+    if (int rc = grid_shape(ctx, who, grid, &count))
+        return rc;
+    if (flags & ~NEB_INDIRECT_FRAME_WEIGHT)
+        return fail(ctx, who, "unknown flags (NEB_INDIRECT_FRAME_WEIGHT is the only one)");
+    if ((flags & NEB_INDIRECT_FRAME_WEIGHT) && !constants)
+        return fail(ctx, who, "null constants with NEB_INDIRECT_FRAME_WEIGHT (cameraWorldPos is read)");
+    if (int rc = rows_resident(ctx, who, row0, row1))
+        return rc;
+    const size_t record_bytes = (size_t)count * sizeof(neb_probe_record);
+    if (!records)
+        return fail(ctx, who, "null records");
+    if ((uintptr_t)records & 31u)
+        return fail(ctx, who, "misaligned pointer (records: 32 bytes)");
+    const size_t npx = (size_t)ctx->W * (ctx->row_end - ctx->row_begin);
+    if (spans_overlap(records, record_bytes, ctx->planes[NEB_PLANE_RADIANCE][ctx->cur], npx * sizeof(float4)))
+        return fail(ctx, who, "records overlaps the radiance plane");
+    if (int rc = svgf_flush_pending(ctx)) // (a held-back temporal pass reads the plane this call writes)
+        return rc;
+    GI_GUARD(ctx);
+    if (!device_readable(ctx, records, record_bytes))
+        return fail(ctx, who, "records is not memory this context's device reads, or the grid's records leave its allocation");
+    IndirectArgs a;
+    a.G = *grid;
+    a.F = frame_planes(ctx);
+    for (int q = 0; q < 3; ++q)
+        a.camera[q] = (flags & NEB_INDIRECT_FRAME_WEIGHT) ? constants->cameraWorldPos[q] : 0.0f;
+    a.row_begin = ctx->row_begin;
+    a.row0 = row0;
+    a.row1 = row1;
+    a.tiles_x = (ctx->W + 7u) / 8u;
+    a.n_tiles = a.tiles_x * ((row1 - row0 + 7u) / 8u);
+    a.frame_weight = flags & NEB_INDIRECT_FRAME_WEIGHT;
+    hipLaunchKernelGGL(probe_indirect_kernel, dim3((a.n_tiles + 3u) / 4u), dim3(256), 0, (hipStream_t)stream_, a, reinterpret_cast<const float4*>(records),
+                       (float4*)ctx->planes[NEB_PLANE_RADIANCE][ctx->cur]);
+    GI_HIP(ctx, hipGetLastError());
+    return NEB_OK;
+}
+
+extern "C" int neb_gi_probe_indirect(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records, const neb_gi_constants* constants,
+                                     uint32_t flags, neb_stream stream_)
+{
+    if (!ctx)
+        return NEB_ERR_INVALID_ARG;
+    return neb_gi_probe_indirect_rows(ctx, grid, records, constants, flags, ctx->row_begin, ctx->row_end, stream_);
 }

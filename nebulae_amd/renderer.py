@@ -434,6 +434,54 @@ class DeferredRenderer:
         ids = out.view(torch.int32)
         return {"irradiance": out[:, 0:3], "weight": out[:, 3], "corners": ids[:, 4], "cell": ids[:, 5], "flags": ids[:, 6], "records": out}
 
+    # ---- probe-lit frames: the G-buffer as the gather's points, the gather as the frame's indirect term ----
+    def _rows_arg(self, who, rows):
+        if rows is None:
+            return self.svgf.row_begin, self.svgf.row_end
+        try:
+            r0, r1 = (int(v) for v in rows)
+        except (TypeError, ValueError):
+            raise NebError(f"{who}: rows must be (row0, row1)") from None
+        if not self.svgf.row_begin <= r0 < r1 <= self.svgf.row_end:
+            raise NebError(f"{who}: rows must satisfy {self.svgf.row_begin} <= row0 < row1 <= {self.svgf.row_end}, the context's rows")
+        return r0, r1
+
+    def gbuffer_points(self, rows=None, out=None, stream=None):
+        """The points the frame's ray generation shades, one per pixel of `rows` (default: all the context's rows), as a [n, 8] float32
+        CUDA tensor in the layout of probes (neb_gbuffer_points; `out`, when given): {world position, 0.01, shading
+        normal, inf}, pixel (x, y) at row (y - rows[0]) * width + x.  A sky pixel has position and normal 0, which gather_probes answers
+        with _lib.GATHER_NOT_GATHERED.  gather_probes takes the tensor as `points`, bake_probes(what="irradiance") as `probes`.  Reads the
+        G-buffer planes of the current frame, needs no scene.  The call only enqueues on `stream`."""
+        import torch
+        r0, r1 = self._rows_arg("gbuffer_points", rows)
+        shape = ((r1 - r0) * self.width, 8)
+        if out is None:
+            with torch.cuda.device(self.svgf.device):
+                out = torch.empty(shape, dtype=torch.float32, device=f"cuda:{self.svgf.device}")
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == shape and out.is_contiguous()):
+            raise NebError(f"gbuffer_points: out must be a contiguous torch.float32 CUDA tensor of shape {shape}")
+        rc = self._lib.neb_gbuffer_points(self._ctx, r0, r1, C.c_void_p(out.data_ptr()), self._stream_arg(stream))
+        self._check(rc, "neb_gbuffer_points")
+        return out
+
+    def submit_commands_gi_probes(self, grid, records, frame_weight=True, rows=None, stream=None):
+        """Stand-in for submit_commands_gi_pathtrace in a frame: add the irradiance a probe grid gives at every pixel's point, weighted as
+        the frame's diffuse term, to radiance[cur] (neb_gi_probe_indirect).  `grid` is probe_grid's, `records` the
+        [nx * ny * nz, 32] float32 CUDA tensor of what="sh" records baked (and accumulated) for its probes.  Per pixel: albedo * (1 -
+        metalness) * E / pi; frame_weight=True multiplies by the mean of what the path tracer's ray generation does to its throughput
+        (reads the frame's camera position), so that the probe-lit frame converges toward what the traced one converges toward.  Sky
+        pixels and pixels without a valid probe keep their radiance.  No noise: the SVGF chain may follow, but is not needed.  Needs no
+        scene.  The call only enqueues on `stream`."""
+        count = self._grid_arg("submit_commands_gi_probes", grid)
+        self._records_arg("submit_commands_gi_probes", "records", records, count)
+        r0, r1 = self._rows_arg("submit_commands_gi_probes", rows)
+        if frame_weight and self.info is None:
+            raise NebError("submit_commands_gi_probes: frame_weight needs a frame (begin_frame) for its camera")
+        c = self.global_constants() if frame_weight else None
+        rc = self._lib.neb_gi_probe_indirect_rows(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), None if c is None else C.byref(c),
+                                                  _lib.INDIRECT_FRAME_WEIGHT if frame_weight else 0, r0, r1, self._stream_arg(stream))
+        self._check(rc, "neb_gi_probe_indirect")
+
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
         n = C.c_uint32(0)
