@@ -1084,7 +1084,7 @@ int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32
  *   sb)), wb = float(double(sb) / double(sa + sb)), each rounded once; samples = sa + sb; hits, backfaces and segments are sums that
  *   stop at 2^32 - 1; flags = (acc.flags | add.flags) & ~NEB_PROBE_NOT_BAKED.
  * It serves NEB_BAKE_SH and NEB_BAKE_IRRADIANCE records alike.
- * GATHER, per point, DDGI's blend without its distance moments (light leaks through thin walls remain), one IEEE operation per step:
+ * GATHER, per point, DDGI's blend without its distance moments (neb_gi_gather_probes_visible, below, adds them), one IEEE operation per step:
  *   usable: (px px + py py) + pz pz finite and the normal's squared length, formed the same way, positive and finite -- the tests
  *     neb_gi_bake_probes makes under NEB_BAKE_IRRADIANCE; tmin and tmax are not read.  Otherwise the record is zero but for
  *     NEB_GATHER_NOT_GATHERED and no record of the grid is loaded.
@@ -1173,6 +1173,65 @@ int neb_gi_probe_indirect(neb_ctx* ctx, const neb_probe_grid* grid, const neb_pr
                           neb_stream stream);
 int neb_gi_probe_indirect_rows(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records, const neb_gi_constants* constants,
                                uint32_t flags, uint32_t row0, uint32_t row1, neb_stream stream);
+
+/* Probe visibility: DDGI's distance maps -- per probe an 8 x 8 octahedral map of filtered distance moments, in a buffer
+ * PARALLEL to the records (neb_probe_record and every call above are unchanged) -- and the gather with a Chebyshev visibility factor per
+ * corner, so that a probe behind a wall thinner than a cell does not light the point.  NO reference counterpart.
+ * `out`, `acc`, `add` and `visibility` are DEVICE pointers, 32-byte aligned; the other pointers as in the calls above.  One IEEE
+ * operation per step, every product and sum rounded by itself, IEEE sqrt and division, no fused multiply-add.
+ * TEXEL k = i + 8 j has the direction n_k:  (ex, ey) = (((i + 0.5) / 8) * 2 - 1, ((j + 0.5) / 8) * 2 - 1)  (exact);  v = (ex, ey, (1 - |ex|) -
+ *   |ey|);  if v.z < 0:  v.xy = ((1 - |ey|) * sgn(ex), (1 - |ex|) * sgn(ey)) with sgn(0) = +1;  n_k = v / sqrt((vx vx + vy vy) + vz vz).
+ * BAKE.  The directions are those of neb_gi_probe_rays(probes, n, samples, NEB_BAKE_SH, frame_index): the same ray index i = p * S + s,
+ * stratification and stream, so that neb_gi_probe_rays yields the very rays followed.  Each is walked ONCE by the closest-hit walk of
+ * neb_gi_cast_rays over the probe's (tmin, tmax): no shading, no sun, no bounce, the same bits under both arithmetic policies.
+ *   per sample s:  dist = hit ? min(t, max_distance) : max_distance
+ *   per texel k, over s = 0 .. S - 1 IN SAMPLE ORDER, the three sums starting from +0:
+ *     c = (nx dx + ny dy) + nz dz;  c < 0.25: the sample counts nothing for this texel (keeps the filter free of denormals);  otherwise
+ *     g = c^32 by five squarings;  A += g;  M1 += g * dist;  M2 += g * (dist * dist)
+ *   A > 0:  weight = A, moments = (M1 / A, M2 / A);  otherwise weight = 0, moments = (max_distance, max_distance * max_distance).
+ * A probe neb_gi_bake_probes would not bake under NEB_BAKE_SH (position not finite in its squared length, tmin not >= 0 or tmax not >
+ * tmin) gets every texel (max_distance, max_distance^2, weight 0) at no walk.  A probe's record does not depend on the other probes of
+ * the call except through i.  samples, ordering behind updates, hidden submeshes, allocation (none) and what is left untouched (every
+ * plane, neb_gi_ray_count, the statistics, the sun table) are neb_gi_bake_probes'; so are the refusals, with NEB_ERR_INVALID_ARG also
+ * for a max_distance that is not finite and > 0.
+ * ACCUMULATION, per texel, wa = acc.weight, wb = add.weight:  wb == 0: acc keeps its bits;  wa == 0: acc becomes add;  otherwise W = wa +
+ *   wb, moment = acc * (wa / W) + add * (wb / W) for both moments, weight = W.  A zeroed buffer is a valid start.  Needs no scene.
+ * VISIBLE GATHER: neb_gi_gather_probes (above) with one more factor per corner, computed only for corners whose record is valid:
+ *     pb = p + normal_bias * N;  u = pb - q  (q by the grid's two operations);  rr = (ux ux + uy uy) + uz uz;  r = sqrt(rr)
+ *     rr == 0: vis = 1.  Otherwise  s = (|ux| + |uy|) + |uz|;  ox = ux / s;  oy = uy / s;
+ *     if uz < 0:  (ox, oy) = ((1 - |oy|) * sgn(ox), (1 - |ox|) * sgn(oy))  (both from the old values, sgn(0) = +1)
+ *     tx = ox * 4 + 3.5;  ix = floor(tx)  (-1 .. 7);  fx = tx - float(ix);  likewise ty, iy, fy
+ *     taps (ix, iy), (ix + 1, iy), (ix, iy + 1), (ix + 1, iy + 1), each wrapped, x first and then y: an index outside 0..7 on an axis is
+ *     clamped on that axis and the index b on the other axis becomes 7 - b  (so (-1, -1) lands on (7, 7): the octahedral map's own edges)
+ *     m = ((1 - fx) t00 + fx t10) (1 - fy) + ((1 - fx) t01 + fx t11) fy   for both moments, every product and sum rounded
+ *     var = max(m2 - m1 * m1, 2^-10 * m2);  cheb = r > m1 ? var / (var + (r - m1) * (r - m1)) : 1;  vis = max(0.05, (cheb * cheb) * cheb)
+ *     w = valid ? (w_tri * w_n) * vis : 0
+ *   W: a corner with vis == 1 (w unchanged) is added to W by the very operation of neb_gi_gather_probes, whose library build adds the
+ *   product w_tri * w_n to W in one fused step (W may differ from the sum of the rounded w by an ulp; w itself is rounded); a corner
+ *   with vis < 1 is added as the rounded w.  Only so do the two calls agree to the bit where nothing is hidden.
+ *   Everything else is the plain gather's: the sum order, r = 1 / W, the convolution, the flags, the validity rule.  With maps whose
+ *   every texel is (D, D^2), D above every r that occurs, the call returns the bits of neb_gi_gather_probes; a point's answer does not
+ *   depend on the other points of the call.
+ * neb_gi_probe_indirect_visible(_rows) is neb_gi_probe_indirect(_rows) over the visible gather: the same pixels' points, the same
+ * weighting, the same flags.
+ * Refusals of the two gathers: those of neb_gi_gather_probes / neb_gi_probe_indirect, and NEB_ERR_INVALID_ARG for a normal_bias that is
+ * not finite and >= 0 and for a visibility pointer that is null, misaligned (32 bytes), unreadable, leaves its allocation (one record per
+ * probe of the grid) or overlaps what the call writes. */
+typedef struct neb_probe_visibility { /* 768 bytes per probe, 32-byte aligned */
+    float moments[64][2]; /* texel k = i + 8 j: filtered mean distance, mean squared distance */
+    float weight[64];     /* the texel's sum of filter weights: what a running mean needs; 0 = the texel was never filled */
+} neb_probe_visibility;
+int neb_gi_bake_visibility(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t frame_index, float max_distance,
+                           neb_probe_visibility* out /* n */, neb_stream stream);
+int neb_gi_accumulate_visibility(neb_ctx* ctx, neb_probe_visibility* acc, const neb_probe_visibility* add, uint32_t n, neb_stream stream);
+int neb_gi_gather_probes_visible(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records,
+                                 const neb_probe_visibility* visibility /* nx * ny * nz */, float normal_bias, const neb_probe* points, uint32_t n,
+                                 neb_probe_gather* out /* n */, neb_stream stream);
+int neb_gi_probe_indirect_visible(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records, const neb_probe_visibility* visibility,
+                                  float normal_bias, const neb_gi_constants* constants, uint32_t flags, neb_stream stream);
+int neb_gi_probe_indirect_visible_rows(neb_ctx* ctx, const neb_probe_grid* grid, const neb_probe_record* records,
+                                       const neb_probe_visibility* visibility, float normal_bias, const neb_gi_constants* constants, uint32_t flags,
+                                       uint32_t row0, uint32_t row1, neb_stream stream);
 
 #ifdef __cplusplus
 }

@@ -332,6 +332,36 @@ namespace Neb
             ThrowIfFailed(m_svgf.Context(), rc, "neb_gi_probe_indirect");
         }
 
+        // Probe visibility: BakeVisibility walks the rays of ProbeRays(..., NEB_BAKE_SH, frameIndex) once and filters their distances (cut at
+        // maxDistance) into neb_probe_visibility[n], an 8 x 8 octahedral map of distance moments per probe, in a buffer parallel to the
+        // records; AccumulateVisibility folds one such bake into a running mean (a zeroed `acc` is a valid start; needs no scene);
+        // GatherProbesVisible and ProbeIndirectVisible are GatherProbes and ProbeIndirect with a Chebyshev visibility factor per corner, looked
+        // up toward the point moved by normalBias along its normal.  Only enqueue, as CastRays.
+        void BakeVisibility(const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t frameIndex, float maxDistance, neb_probe_visibility* out,
+                            neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_bake_visibility(m_svgf.Context(), probes, n, samples, frameIndex, maxDistance, out, commandList),
+                          "neb_gi_bake_visibility");
+        }
+        void AccumulateVisibility(neb_probe_visibility* acc, const neb_probe_visibility* add, uint32_t n, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_accumulate_visibility(m_svgf.Context(), acc, add, n, commandList), "neb_gi_accumulate_visibility");
+        }
+        void GatherProbesVisible(const neb_probe_grid& grid, const neb_probe_record* records, const neb_probe_visibility* visibility, float normalBias,
+                                 const neb_probe* points, uint32_t n, neb_probe_gather* out, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_gather_probes_visible(m_svgf.Context(), &grid, records, visibility, normalBias, points, n, out, commandList),
+                          "neb_gi_gather_probes_visible");
+        }
+        void ProbeIndirectVisible(const neb_probe_grid& grid, const neb_probe_record* records, const neb_probe_visibility* visibility, float normalBias,
+                                  const neb_gi_constants* constants, uint32_t flags, neb_stream commandList, uint32_t row0 = 0, uint32_t row1 = 0)
+        {
+            const int rc = row1 == 0 ? neb_gi_probe_indirect_visible(m_svgf.Context(), &grid, records, visibility, normalBias, constants, flags, commandList)
+                                     : neb_gi_probe_indirect_visible_rows(m_svgf.Context(), &grid, records, visibility, normalBias, constants, flags, row0,
+                                                                          row1, commandList);
+            ThrowIfFailed(m_svgf.Context(), rc, "neb_gi_probe_indirect_visible");
+        }
+
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const
         {

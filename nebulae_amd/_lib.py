@@ -162,6 +162,11 @@ class ProbeGather(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class ProbeVisibility(C.Structure):
+    """neb_probe_visibility"""
+    _fields_ = [("moments", (C.c_float * 2) * 64), ("weight", C.c_float * 64)]
+
+
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
 STRIP_RESET_HISTORY = 1
 
@@ -227,6 +232,14 @@ def _gi_sigs():
         "neb_gi_probe_indirect": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.POINTER(S.GIConstants), C.c_uint32, C.c_void_p]),
         "neb_gi_probe_indirect_rows": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.POINTER(S.GIConstants), C.c_uint32, C.c_uint32, C.c_uint32,
                                                  C.c_void_p]),
+        "neb_gi_bake_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]),
+        "neb_gi_accumulate_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+        "neb_gi_gather_probes_visible": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                   C.c_void_p]),
+        "neb_gi_probe_indirect_visible": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_float, C.POINTER(S.GIConstants), C.c_uint32,
+                                                    C.c_void_p]),
+        "neb_gi_probe_indirect_visible_rows": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_float, C.POINTER(S.GIConstants),
+                                                         C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
         "neb_svgf_set_camera": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(S.CameraDesc)]),
         "neb_strip_frame": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.c_void_p, C.POINTER(StripPlan), C.c_void_p]),
         "neb_strip_frame_begin": (C.c_int, [C.c_void_p, C.POINTER(S.GIConstants), C.POINTER(StripPlan), C.POINTER(StripPeers), C.c_void_p]),

@@ -6,7 +6,7 @@
 // NEB_RAYS_SORT the rays are visited in the order of a 16-bit key (direction octant above the origin's Morton bits, bounce_sort_key)
 // and every answer still lands at its ray's own index.  A ray's walk depends on the ray and the tree alone, so the order changes
 // no answer.  Nothing of the frame is touched: no plane, no ray counter, no statistics, no sun table.
-#include "gi_device.h" // (turns floating-point contraction off for this file: see there)
+#include "probe_device.h" // (the shared probe arithmetic; turns floating-point contraction off for this file: see gi_device.h)
 
 namespace neb {
 
@@ -15,10 +15,6 @@ namespace {
 constexpr uint32_t kQueryMaxRays = 1u << 28; // 8 GiB of rays; the sort's indices and raysort.hip's tile counts stay far inside 32 bits
 constexpr uint32_t kNoId = 0xffffffffu;
 constexpr uint32_t kUnwalkableKey = (1u << kSortBits) - 1u; // above every key of bounce_sort_key: such rays gather at the end
-
-// The interval the walk assumes: the triangle screen of intersect_tri_regs takes tmin >= 0 for granted, and an empty interval holds
-// no hit.  Written so that a NaN on either side says no.
-__device__ __forceinline__ bool interval_ok(float tmin, float tmax) { return tmin >= 0.0f && tmax > tmin; }
 
 // One lane per ray, one wave per workgroup, the LDS stack of gbuffer_kernel.  Lane j takes ray j, or ray order[j] (SORTED), reads it
 // as two float4 and writes its answer AT THE RAY'S OWN INDEX: a hit record as two 16-byte stores of one 32-byte sector (ANY_HIT =
@@ -222,54 +218,6 @@ constexpr uint32_t kProbeMaxSamples = 4096;
 #else
 #define NEB_PROBE_BAKE_OCCUPANCY amdgpu_waves_per_eu(FAST ? 5 : 4)
 #endif
-
-// A product rounded by itself.  HIP's __fmul_rn is a plain operator, and the back end fuses a product into the sum that takes it
-// whatever a pragma says (gi_refit.hip's rounded_product): the empty statement is what the optimiser cannot see through.
-__device__ __forceinline__ float rounded_mul(float a, float b)
-{
-    float p = __fmul_rn(a, b);
-    asm volatile("" : "+v"(p));
-    return p;
-}
-// (x x + y y) + z z, every product and sum rounded by itself: the same bits as a float32 restatement, at the boundaries of 0 and overflow too
-__device__ __forceinline__ float rounded_square_length(float x, float y, float z)
-{
-    return __fadd_rn(__fadd_rn(rounded_mul(x, x), rounded_mul(y, y)), rounded_mul(z, z));
-}
-
-// Whether a probe is baked (include/nebulae_hip.h): a position whose squared length is finite -- ray_walkable's test of an origin, so
-// that "not baked" and "no sample could be walked" are the same probes --, an interval in order (interval_ok: a NaN on either side says
-// no) and, where the normal is used, one whose squared length is positive and finite.
-template <uint32_t WHAT> __device__ __forceinline__ bool probe_baked(float4 p0, float4 p1)
-{
-    const float inf = __builtin_inff();
-    bool ok = rounded_square_length(p0.x, p0.y, p0.z) < inf && interval_ok(p0.w, p1.w);
-    if (WHAT == NEB_BAKE_IRRADIANCE) {
-        const float nn = rounded_square_length(p1.x, p1.y, p1.z);
-        ok = ok && nn > 0.0f && nn < inf;
-    }
-    return ok;
-}
-
-// The direction of sample s of S, ray index i = p * S + s: the sequence of include/nebulae_hip.h, one IEEE operation per line of it, under
-// both shade policies.  Its two draws come from a stream of their own, so that they are independent of the path's.  `nrm` is
-// normalize3<false>(normal) (IRRADIANCE; unused otherwise).
-template <uint32_t WHAT> __device__ __forceinline__ float3 probe_direction(uint32_t i, uint32_t s, uint32_t samples, uint32_t frame_index, float3 nrm)
-{
-    uint32_t rng_d = jenkins(~i ^ jenkins(frame_index + 0x9E3779B9u));
-    const float r0 = rand01(rng_d), r1 = rand01(rng_d);
-    const float u0 = __fadd_rn((float)s, r0) / (float)samples, u1 = r1; // (one stratum of [0, 1] per sample in u0)
-    if (WHAT == NEB_BAKE_IRRADIANCE)
-        return cosine_hemisphere_aligned<false>(u0, u1, nrm);
-    const float z = __fsub_rn(1.0f, rounded_mul(2.0f, u0));
-    const float rho = sqrtf(fmaxf(0.0f, __fsub_rn(1.0f, rounded_mul(z, z)))); // (sqrtf and `/` are the correctly rounded forms in this build;
-                                                                             //  __fsqrt_rn is ocml's native, 1-ulp root)
-    float sn, cs;
-    det_sincosf(rounded_mul(kPiTwo, u1), sn, cs);
-    const float x = rounded_mul(rho, cs), y = rounded_mul(rho, sn);
-    const float l = sqrtf(rounded_square_length(x, y, z)); // normalize3<false>, its roundings spelled out
-    return f3(x / l, y / l, z / l);
-}
 
 // One lane per ray: ray p * S + s is sample s of probe p, origin and interval the probe's own bits; a probe that is not baked gets S
 // rays of zeroes, which every query reports as NEB_HIT_NOT_WALKED.

@@ -406,17 +406,83 @@ class DeferredRenderer:
         self._check(rc, "neb_gi_accumulate_probes")
         return acc
 
-    def gather_probes(self, grid, records, points, out=None, stream=None):
+    # ---- probe visibility: distance maps per probe, a running mean of them, the gather's Chebyshev factor ----
+    @staticmethod
+    def _visibility_arg(who, name, t, rows=None):
+        import torch
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 192 and t.is_contiguous()
+                and (rows is None or t.shape[0] == rows)):
+            raise NebError(f"{who}: {name} must be a contiguous float32 CUDA tensor [{'n' if rows is None else rows}, 192]")
+        return t.shape[0]
+
+    @staticmethod
+    def _bias_arg(who, normal_bias):
+        normal_bias = float(normal_bias)
+        if not (np.isfinite(normal_bias) and normal_bias >= 0.0):
+            raise NebError(f"{who}: normal_bias must be finite and >= 0")
+        return normal_bias
+
+    def bake_visibility(self, probes, samples=64, max_distance=None, constants=None, out=None, stream=None):
+        """Bake the distance maps of n probes on the device (neb_gi_bake_visibility): the `samples` rays of
+        probe_rays(probes, samples, "sh", constants.frameIndex) are walked once each, as cast_rays walks them, and their distances --
+        cut at `max_distance`, which a miss counts as; about 1.5 cell diagonals is DDGI's choice -- are filtered into an 8 x 8 octahedral
+        map of (mean distance, mean squared distance) per probe.  Returns views of one [n, 192] float32 buffer (neb_probe_visibility)
+        -- moments [n, 64, 2], weight [n, 64] -- with the buffer under "records" (`out`, when given).  `constants` (default:
+        global_constants() of the frame) gives the frame index and is not changed.  A probe that cannot be baked gets (max_distance,
+        max_distance^2, weight 0) in every texel.  The call only enqueues on `stream`, behind every update enqueued before it."""
+        import torch
+        n, samples, _ = self._probe_args("bake_visibility", probes, samples, "sh")
+        if max_distance is None or not (np.isfinite(float(max_distance)) and float(max_distance) > 0.0):
+            raise NebError("bake_visibility: max_distance must be finite and > 0")
+        if constants is None:
+            constants = self.global_constants()
+        if out is None:
+            with torch.cuda.device(probes.device):
+                out = torch.empty((n, 192), dtype=torch.float32, device=probes.device)
+        else:
+            self._visibility_arg("bake_visibility", "out", out, n)
+        rc = self._lib.neb_gi_bake_visibility(self._ctx, C.c_void_p(probes.data_ptr() if n else 0), n, samples, int(constants.frameIndex) & 0xFFFFFFFF,
+                                              float(max_distance), C.c_void_p(out.data_ptr() if n else 0), self._stream_arg(stream))
+        self._check(rc, "neb_gi_bake_visibility")
+        return {"moments": out[:, 0:128].view(n, 64, 2), "weight": out[:, 128:192], "records": out}
+
+    def accumulate_visibility(self, acc, add, stream=None):
+        """Fold one bake of distance maps into a running mean on the device (neb_gi_accumulate_visibility): `acc` and
+        `add` are contiguous float32 CUDA tensors [n, 192] ("records" of bake_visibility).  Per texel acc becomes the mean of the two
+        weighted by their filter weights, its weight their sum; a zeroed `acc` is a valid start and a texel of `add` with weight 0
+        changes nothing.  Returns `acc`.  Needs no scene and no frame.  The call only enqueues on `stream`."""
+        n = self._visibility_arg("accumulate_visibility", "acc", acc)
+        self._visibility_arg("accumulate_visibility", "add", add, n)
+        if add.device != acc.device:
+            raise NebError("accumulate_visibility: acc and add must lie on one device")
+        rc = self._lib.neb_gi_accumulate_visibility(self._ctx, C.c_void_p(acc.data_ptr() if n else 0), C.c_void_p(add.data_ptr() if n else 0), n,
+                                                    self._stream_arg(stream))
+        self._check(rc, "neb_gi_accumulate_visibility")
+        return acc
+
+    def gather_probes(self, grid, records, points, out=None, stream=None, visibility=None, normal_bias=0.0):
         """Irradiance at n points from a grid of SH records (neb_gi_gather_probes): `grid` is probe_grid's, `records` the
         [nx * ny * nz, 32] float32 CUDA tensor of what="sh" records baked (and accumulated) for its probes, `points` a contiguous
         float32 CUDA tensor [n, 8] in the layout of probes -- position and normal are read, the normal need not be normalised.  The
         eight records around a point are blended with trilinear weights times DDGI's direction weight, probes that were not baked or
         see too many backfaces left out, and the blend is convolved with the cosine lobe about the normal.  Returns views of one [n, 8]
         float32 buffer (neb_probe_gather) -- irradiance [n, 3], weight, corners, cell, flags (int32; _lib.GATHER_*) -- with the buffer
-        under "records" (`out`, when given).  Needs no scene and no frame.  The call only enqueues on `stream`."""
+        under "records" (`out`, when given).  Needs no scene and no frame.  The call only enqueues on `stream`.
+        `visibility` (the [nx * ny * nz, 192] "records" of bake_visibility for the grid's probes) switches to
+        neb_gi_gather_probes_visible: every corner's weight takes a Chebyshev factor from the probe's distance map, looked
+        up toward the point moved by `normal_bias` along its normal, so that a probe behind a thin wall keeps as little as 0.05 of its weight.
+        Without it the plain gather runs, and normal_bias must be left at 0."""
         import torch
         count = self._grid_arg("gather_probes", grid)
         self._records_arg("gather_probes", "records", records, count)
+        normal_bias = self._bias_arg("gather_probes", normal_bias)
+        if visibility is None:
+            if normal_bias != 0.0:
+                raise NebError("gather_probes: normal_bias is read only with visibility")
+        else:
+            self._visibility_arg("gather_probes", "visibility", visibility, count)
+            if visibility.device != records.device:
+                raise NebError("gather_probes: records and visibility must lie on one device")
         if not (isinstance(points, torch.Tensor) and points.is_cuda and points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 8
                 and points.is_contiguous()):
             raise NebError("gather_probes: points must be a contiguous float32 CUDA tensor [n, 8]")
@@ -428,9 +494,15 @@ class DeferredRenderer:
                 out = torch.empty((n, 8), dtype=torch.float32, device=points.device)
         elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 8) and out.is_contiguous()):
             raise NebError(f"gather_probes: out must be a contiguous torch.float32 CUDA tensor of shape {(n, 8)}")
-        rc = self._lib.neb_gi_gather_probes(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), C.c_void_p(points.data_ptr() if n else 0), n,
-                                            C.c_void_p(out.data_ptr() if n else 0), self._stream_arg(stream))
-        self._check(rc, "neb_gi_gather_probes")
+        if visibility is None:
+            rc = self._lib.neb_gi_gather_probes(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), C.c_void_p(points.data_ptr() if n else 0), n,
+                                                C.c_void_p(out.data_ptr() if n else 0), self._stream_arg(stream))
+            self._check(rc, "neb_gi_gather_probes")
+        else:
+            rc = self._lib.neb_gi_gather_probes_visible(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), C.c_void_p(visibility.data_ptr()),
+                                                        normal_bias, C.c_void_p(points.data_ptr() if n else 0), n,
+                                                        C.c_void_p(out.data_ptr() if n else 0), self._stream_arg(stream))
+            self._check(rc, "neb_gi_gather_probes_visible")
         ids = out.view(torch.int32)
         return {"irradiance": out[:, 0:3], "weight": out[:, 3], "corners": ids[:, 4], "cell": ids[:, 5], "flags": ids[:, 6], "records": out}
 
@@ -464,23 +536,39 @@ class DeferredRenderer:
         self._check(rc, "neb_gbuffer_points")
         return out
 
-    def submit_commands_gi_probes(self, grid, records, frame_weight=True, rows=None, stream=None):
+    def submit_commands_gi_probes(self, grid, records, frame_weight=True, rows=None, stream=None, visibility=None, normal_bias=0.0):
         """Stand-in for submit_commands_gi_pathtrace in a frame: add the irradiance a probe grid gives at every pixel's point, weighted as
         the frame's diffuse term, to radiance[cur] (neb_gi_probe_indirect).  `grid` is probe_grid's, `records` the
         [nx * ny * nz, 32] float32 CUDA tensor of what="sh" records baked (and accumulated) for its probes.  Per pixel: albedo * (1 -
         metalness) * E / pi; frame_weight=True multiplies by the mean of what the path tracer's ray generation does to its throughput
         (reads the frame's camera position), so that the probe-lit frame converges toward what the traced one converges toward.  Sky
         pixels and pixels without a valid probe keep their radiance.  No noise: the SVGF chain may follow, but is not needed.  Needs no
-        scene.  The call only enqueues on `stream`."""
+        scene.  The call only enqueues on `stream`.  `visibility` and `normal_bias` as gather_probes takes them: with a visibility buffer
+        the gather is the visible one (neb_gi_probe_indirect_visible), without it the plain call runs."""
         count = self._grid_arg("submit_commands_gi_probes", grid)
         self._records_arg("submit_commands_gi_probes", "records", records, count)
+        normal_bias = self._bias_arg("submit_commands_gi_probes", normal_bias)
+        if visibility is None:
+            if normal_bias != 0.0:
+                raise NebError("submit_commands_gi_probes: normal_bias is read only with visibility")
+        else:
+            self._visibility_arg("submit_commands_gi_probes", "visibility", visibility, count)
+            if visibility.device != records.device:
+                raise NebError("submit_commands_gi_probes: records and visibility must lie on one device")
         r0, r1 = self._rows_arg("submit_commands_gi_probes", rows)
         if frame_weight and self.info is None:
             raise NebError("submit_commands_gi_probes: frame_weight needs a frame (begin_frame) for its camera")
         c = self.global_constants() if frame_weight else None
-        rc = self._lib.neb_gi_probe_indirect_rows(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), None if c is None else C.byref(c),
-                                                  _lib.INDIRECT_FRAME_WEIGHT if frame_weight else 0, r0, r1, self._stream_arg(stream))
-        self._check(rc, "neb_gi_probe_indirect")
+        flags = _lib.INDIRECT_FRAME_WEIGHT if frame_weight else 0
+        if visibility is None:
+            rc = self._lib.neb_gi_probe_indirect_rows(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()), None if c is None else C.byref(c),
+                                                      flags, r0, r1, self._stream_arg(stream))
+            self._check(rc, "neb_gi_probe_indirect")
+        else:
+            rc = self._lib.neb_gi_probe_indirect_visible_rows(self._ctx, C.byref(grid), C.c_void_p(records.data_ptr()),
+                                                              C.c_void_p(visibility.data_ptr()), normal_bias, None if c is None else C.byref(c),
+                                                              flags, r0, r1, self._stream_arg(stream))
+            self._check(rc, "neb_gi_probe_indirect_visible")
 
     def visibility(self):
         """one bool per geometry of the scene: True = visible (neb_gi_get_visibility)"""
