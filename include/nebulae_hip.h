@@ -1233,6 +1233,56 @@ int neb_gi_probe_indirect_visible_rows(neb_ctx* ctx, const neb_probe_grid* grid,
                                        const neb_probe_visibility* visibility, float normal_bias, const neb_gi_constants* constants, uint32_t flags,
                                        uint32_t row0, uint32_t row1, neb_stream stream);
 
+/* Probe feedback: a path query or a bake whose paths END IN A PROBE GRID.  At the path's last possible vertex, where no
+ * further segment is sampled, the grid's irradiance stands for everything the path did not walk, so that bake -> accumulate -> bake(tail
+ * = the accumulated grid) adds one bounce per update to every probe with a bake as short as two path vertices.  NO reference counterpart.
+ * tail == NULL: the call IS neb_gi_trace_paths / neb_gi_bake_probes -- the same kernels, the same bits, the same refusals.
+ * THE TAIL.  Everything up to the path's last possible vertex is neb_gi_trace_paths' contract bit for bit: the walk, the RNG stream, the
+ * flags, the throughput, every earlier `added`.  With last = maxPathVertices - 1, the tail applies at segment k == last and only where
+ * that vertex carries NEB_HIT_MATERIAL, after the vertex's direct term, one IEEE operation per step:
+ *   1. sd = (SN.x * d.x + SN.y * d.y) + SN.z * d.z, every product and sum rounded; Ng = SN if sd <= 0, else -SN.  SN is the shading normal
+ *      as NEB_SHADE_SURFACE reports it for this hit, d the segment's own direction.  The POINT is {position = origin + direction * t as
+ *      the path forms it (NEB_SHADE_SURFACE's position), normal = Ng}.
+ *   2. g = what neb_gi_gather_probes(grid, records, POINT) returns; with `visibility`, what neb_gi_gather_probes_visible(grid, records,
+ *      visibility, normal_bias, POINT) returns: the same operations, the same bits, whichever route the wave's points take.
+ *   3. g.flags with NEB_GATHER_NOT_GATHERED or NEB_GATHER_NO_PROBE: nothing is added, no flag is set, the record is the plain call's.
+ *   4. k.c = throughput.c * (albedo.c * (1 - metalness)), the throughput on ENTERING the vertex: the two products the next bounce
+ *      would have formed.
+ *   5. with NEB_TAIL_FRAME_WEIGHT: pd = the pdiff the next bounce would have used (the same expression, under the context's arithmetic
+ *      policy, as at an inner vertex); it is written to the vertex record's pdiff, which otherwise stays 0;
+ *      k.c = k.c * (pd > 0 ? 2 - pd : 1), each operation rounded (NEB_INDIRECT_FRAME_WEIGHT's reasoning).
+ *   6. tail.c = (k.c * g.irradiance.c) * (1 / 3.14159265f), every product rounded by itself under both policies.
+ *   7. the vertex's added.c = added.c + tail.c, one rounded sum; the vertex record and the path record gain NEB_PATH_TAIL.
+ *   8. out.rgb stays the float32 running sum of the `added` words, vertex 1 assigning.
+ * A vertex that ends a path earlier -- a miss, a hit without material, a segment the walk refuses -- gets no tail.  A terminal hit
+ * flagged NEB_HIT_BACKFACE does: Ng faces the ray, thin two-sided geometry is legitimate.
+ * neb_gi_bake_probes_tail(...) == reduce(neb_gi_trace_paths_tail(neb_gi_probe_rays(...))) bit for bit: projection, reduction order,
+ * scale and counters are neb_gi_bake_probes'; hits, backfaces and segments are unchanged by a tail.
+ * `records` and `visibility` are DEVICE pointers read in stream order, like any device pointer of these calls: bake -> neb_gi_accumulate_
+ * probes -> bake on one stream is well-defined.  Everything else is the plain calls': they allocate nothing (a sorted call as
+ * neb_gi_trace_paths), run behind updates, leave planes, counters and the sun table untouched; hidden submeshes are absent; strip
+ * contexts accept them.
+ * Refusals, each enqueuing nothing: all of the plain call's, checked first and under the plain call's name; then, with a non-NULL
+ * tail, NEB_ERR_INVALID_ARG for the grid as neb_gi_gather_probes refuses it, unknown tail->flags, `records` null, misaligned (32 bytes),
+ * unreadable or leaving its allocation (one record per probe of the grid), `visibility` likewise when non-NULL, with `visibility` a
+ * normal_bias that is not finite and >= 0, and `records` or `visibility` overlapping out, vertices, rays or probes (the in-place hazard
+ * of a feedback loop: bake into a second buffer, then accumulate).  n == 0 succeeds and looks at nothing of the tail. */
+#define NEB_TAIL_FRAME_WEIGHT 1u
+#define NEB_PATH_TAIL 256u /* vertex flags: this vertex's `added` contains a grid tail; path flags: the path took one */
+typedef struct neb_probe_tail { /* host struct, passed by pointer */
+    neb_probe_grid grid;
+    const neb_probe_record* records;        /* nx * ny * nz NEB_BAKE_SH records, device, 32-byte aligned */
+    const neb_probe_visibility* visibility; /* NULL: the plain gather; else the visible gather */
+    float normal_bias;                      /* read only with visibility */
+    uint32_t flags;                         /* 0 or NEB_TAIL_FRAME_WEIGHT */
+} neb_probe_tail;
+int neb_gi_trace_paths_tail(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags /* 0 or NEB_RAYS_SORT */, const neb_gi_constants* constants,
+                            const neb_probe_tail* tail /* NULL: neb_gi_trace_paths */, void* out /* neb_ray_path[n] */,
+                            void* vertices /* NULL, or neb_path_vertex[n * (maxPathVertices - 1)] */, neb_stream stream);
+int neb_gi_bake_probes_tail(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags /* 0 */,
+                            const neb_gi_constants* constants, const neb_probe_tail* tail /* NULL: neb_gi_bake_probes */, neb_probe_record* out /* n */,
+                            neb_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

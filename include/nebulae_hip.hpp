@@ -362,6 +362,23 @@ namespace Neb
             ThrowIfFailed(m_svgf.Context(), rc, "neb_gi_probe_indirect_visible");
         }
 
+        // Probe feedback: TracePaths / BakeProbes whose paths end in a probe grid -- at a path's last possible vertex the grid's irradiance
+        // (tail.records, gathered plain, or through tail.visibility with tail.normal_bias) stands for the bounces the path did not walk, so
+        // that BakeProbes -> AccumulateProbes -> BakeProbesTail(the accumulated records) gains one bounce per update.  tail.flags: 0 or
+        // NEB_TAIL_FRAME_WEIGHT.  The grid's buffers must not be the ones the call writes.  Only enqueue, as CastRays.
+        void TracePathsTail(const neb_ray* rays, uint32_t n, uint32_t flags, const neb_gi_constants* constants, const neb_probe_tail& tail, void* paths,
+                            void* vertices, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_trace_paths_tail(m_svgf.Context(), rays, n, flags, constants, &tail, paths, vertices, commandList),
+                          "neb_gi_trace_paths_tail");
+        }
+        void BakeProbesTail(const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags, const neb_gi_constants* constants,
+                            const neb_probe_tail& tail, neb_probe_record* out, neb_stream commandList)
+        {
+            ThrowIfFailed(m_svgf.Context(), neb_gi_bake_probes_tail(m_svgf.Context(), probes, n, samples, what, flags, constants, &tail, out, commandList),
+                          "neb_gi_bake_probes_tail");
+        }
+
         // the acceleration structure is built on the device; these report what came out of it
         uint32_t BvhDepth() const
         {

@@ -133,6 +133,8 @@ RAYS_ANY_HIT, RAYS_SORT = 1, 2  # NEB_RAYS_*: flags of neb_gi_cast_rays
 SHADE_SURFACE, SHADE_RADIANCE = 0, 1  # NEB_SHADE_*: `what` of neb_gi_shade_rays
 HIT_FOUND, HIT_ATTRIBUTES, HIT_MATERIAL, HIT_BACKFACE, HIT_NOT_WALKED, HIT_SUN_VISIBLE = 1, 2, 4, 8, 16, 32  # NEB_HIT_*: flags of its records
 PATH_ESCAPED, PATH_DIVIDED = 64, 128  # NEB_PATH_*: flags of neb_gi_trace_paths' records, beside NEB_HIT_*
+PATH_TAIL = 256  # NEB_PATH_TAIL: the vertex's `added` contains a grid tail / the path took one (neb_gi_trace_paths_tail)
+TAIL_FRAME_WEIGHT = 1  # NEB_TAIL_FRAME_WEIGHT: flags of neb_probe_tail
 BAKE_SH, BAKE_IRRADIANCE = 0, 1  # NEB_BAKE_*: `what` of neb_gi_probe_rays / neb_gi_bake_probes
 PROBE_NOT_BAKED = 1  # NEB_PROBE_NOT_BAKED: flags of neb_probe_record
 PROBE_SATURATED = 2  # NEB_PROBE_SATURATED: flags of neb_probe_record, set by neb_gi_accumulate_probes
@@ -165,6 +167,11 @@ class ProbeGather(C.Structure):
 class ProbeVisibility(C.Structure):
     """neb_probe_visibility"""
     _fields_ = [("moments", (C.c_float * 2) * 64), ("weight", C.c_float * 64)]
+
+
+class ProbeTailDesc(C.Structure):
+    """neb_probe_tail"""
+    _fields_ = [("grid", ProbeGrid), ("records", C.c_void_p), ("visibility", C.c_void_p), ("normal_bias", C.c_float), ("flags", C.c_uint32)]
 
 
 STRIP_SCHEMES = {"once": 0, "per_level": 1, "overlap": 2}
@@ -225,6 +232,10 @@ def _gi_sigs():
         "neb_gi_trace_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p, C.c_void_p]),
         "neb_gi_probe_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
         "neb_gi_bake_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.c_void_p, C.c_void_p]),
+        "neb_gi_trace_paths_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants), C.POINTER(ProbeTailDesc), C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+        "neb_gi_bake_probes_tail": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(S.GIConstants),
+                                              C.POINTER(ProbeTailDesc), C.c_void_p, C.c_void_p]),
         "neb_gi_probe_grid": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
         "neb_gi_accumulate_probes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
         "neb_gi_gather_probes": (C.c_int, [C.c_void_p, C.POINTER(ProbeGrid), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),

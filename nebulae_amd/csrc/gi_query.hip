@@ -180,11 +180,27 @@ static_assert(sizeof(neb_ray_path) == 32 && offsetof(neb_ray_path, segments) == 
 // VERTICES: record i * (max_vertices - 1) + (k - 1) describes segment k of ray i, six 16-byte stores; a record past the path's end is
 // written as zeroes.
 // The loop itself is path_segments.h, one text that probe_bake_kernel (below) includes too.
-template <bool SORTED, bool FAST, bool VERTICES>
+// TAIL (neb_gi_trace_paths_tail): 0 = none, the kernel of neb_gi_trace_paths; 1 / 2 = the path's last vertex ends in the
+// probe grid of `tail`, gathered plain / with visibility after the loop.  The grid arrives as a parameter pack of one TailArgs, which is
+// empty for TAIL = 0: that kernel's signature, and with it its kernel arguments, are neb_gi_trace_paths' own.
+struct TailArgs { // neb_probe_tail as the kernels read it
+    neb_probe_grid G;
+    const float4* records;
+    const float2* visibility;
+    float normal_bias;
+    uint32_t frame_weight;
+};
+struct NoTail {};
+__device__ __forceinline__ NoTail the_tail() { return NoTail{}; }
+__device__ __forceinline__ const TailArgs& the_tail(const TailArgs& t) { return t; }
+
+template <bool SORTED, bool FAST, bool VERTICES, int TAIL = 0, typename... Tail>
 __global__ __launch_bounds__(64) void ray_path_kernel(SceneView S, const ShadeHeader* __restrict__ heads, const float4* __restrict__ rays, uint32_t n,
                                                       const uint32_t* __restrict__ order, ShadeSun sun, uint32_t max_vertices, float4* __restrict__ out,
-                                                      float4* __restrict__ vertices)
+                                                      float4* __restrict__ vertices, Tail... tail_pack)
 {
+    static_assert(sizeof...(Tail) == (TAIL != 0), "one TailArgs exactly where TAIL is set");
+    [[maybe_unused]] const auto& tail = the_tail(tail_pack...);
     __shared__ int stack_mem[kLdsStack * 64];
     const uint32_t lane = threadIdx.x;
     int* stack = stack_mem + lane;
@@ -216,7 +232,7 @@ constexpr uint32_t kProbeMaxSamples = 4096;
 #ifdef NEB_PROBE_BAKE_FOUR_WAVES
 #define NEB_PROBE_BAKE_OCCUPANCY amdgpu_waves_per_eu(4, 4)
 #else
-#define NEB_PROBE_BAKE_OCCUPANCY amdgpu_waves_per_eu(FAST ? 5 : 4)
+#define NEB_PROBE_BAKE_OCCUPANCY amdgpu_waves_per_eu(TAIL ? 4 : FAST ? 5 : 4)
 #endif
 
 // One lane per ray: ray p * S + s is sample s of probe p, origin and interval the probe's own bits; a probe that is not baked gets S
@@ -250,11 +266,14 @@ __global__ __launch_bounds__(256) void probe_rays_kernel(const float4* __restric
 // which lane 0 adds to the record's words in LDS as well.  After the last round lane 0 multiplies the totals once by `scale` and lanes 0..7 write the record, one 16-byte store
 // each.  Every multiplication and addition of the projection is written with its rounding (no fused multiply-add anywhere in it).
 // A probe that is not baked costs one test and the same eight stores.
-template <uint32_t WHAT, bool FAST>
+// TAIL (neb_gi_bake_probes_tail): ray_path_kernel's.  All 64 lanes of the wave are in every round, so the round's gather is converged.
+template <uint32_t WHAT, bool FAST, int TAIL = 0, typename... Tail>
 __global__ __launch_bounds__(64) __attribute__((NEB_PROBE_BAKE_OCCUPANCY)) void probe_bake_kernel(
     SceneView S, const ShadeHeader* __restrict__ heads, const float4* __restrict__ probes, uint32_t samples, ShadeSun sun, uint32_t max_vertices, float scale,
-    float4* __restrict__ out)
+    float4* __restrict__ out, Tail... tail_pack)
 {
+    static_assert(sizeof...(Tail) == (TAIL != 0), "one TailArgs exactly where TAIL is set");
+    [[maybe_unused]] const auto& tail = the_tail(tail_pack...);
     constexpr bool VERTICES = false;
     constexpr int kWords = WHAT == NEB_BAKE_SH ? 27 : 3;
     __shared__ int stack_mem[kLdsStack * 64];
@@ -555,9 +574,68 @@ extern "C" int neb_gi_shade_rays(neb_ctx* ctx, const neb_ray* rays, uint32_t n, 
     return NEB_OK;
 }
 
-extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, const neb_gi_constants* constants, void* out, void* vertices,
-                                  neb_stream stream_)
+namespace {
+
+// What the two tail calls check of a non-null neb_probe_tail before any pointer is looked up (`who` in front): the grid, the flags, the
+// two pointers, the bias, and that nothing the call writes or reads as its own input (`spans`) overlaps the grid's buffers.
+struct TailSpan {
+    const void* p;
+    size_t bytes;
+    const char* name;
+};
+int tail_shape(neb_ctx* ctx, const char* who, const neb_probe_tail* tail, const TailSpan* spans, int n_spans, uint32_t* count)
 {
+    if (int rc = grid_shape(ctx, who, &tail->grid, count))
+        return rc;
+    if (tail->flags & ~NEB_TAIL_FRAME_WEIGHT)
+        return fail(ctx, who, "unknown tail flag bits (0 or NEB_TAIL_FRAME_WEIGHT)");
+    if (!tail->records)
+        return fail(ctx, who, "null tail records");
+    if (((uintptr_t)tail->records & 31u) || ((uintptr_t)tail->visibility & 31u))
+        return fail(ctx, who, "misaligned pointer (tail records, visibility: 32 bytes)");
+    if (tail->visibility && !(std::isfinite(tail->normal_bias) && tail->normal_bias >= 0.0f))
+        return fail(ctx, who, "normal_bias must be finite and >= 0");
+    const size_t record_bytes = (size_t)*count * sizeof(neb_probe_record), visibility_bytes = (size_t)*count * sizeof(neb_probe_visibility);
+    char msg[160];
+    for (int q = 0; q < n_spans; ++q) {
+        if (!spans[q].p)
+            continue;
+        if (spans_overlap(tail->records, record_bytes, spans[q].p, spans[q].bytes)) {
+            snprintf(msg, sizeof(msg), "tail records overlap %s (bake into a second buffer, then accumulate)", spans[q].name);
+            return fail(ctx, who, msg);
+        }
+        if (tail->visibility && spans_overlap(tail->visibility, visibility_bytes, spans[q].p, spans[q].bytes)) {
+            snprintf(msg, sizeof(msg), "tail visibility overlaps %s", spans[q].name);
+            return fail(ctx, who, msg);
+        }
+    }
+    return NEB_OK;
+}
+// ... and after GI_GUARD: that the device reads them.
+int tail_readable(neb_ctx* ctx, const char* who, const neb_probe_tail* tail, uint32_t count)
+{
+    if (!device_readable(ctx, tail->records, (size_t)count * sizeof(neb_probe_record)))
+        return fail(ctx, who, "tail records is not memory this context's device reads, or the grid's records leave its allocation");
+    if (tail->visibility && !device_readable(ctx, tail->visibility, (size_t)count * sizeof(neb_probe_visibility)))
+        return fail(ctx, who, "tail visibility is not memory this context's device reads, or the grid's records leave its allocation");
+    return NEB_OK;
+}
+TailArgs tail_args(const neb_probe_tail* tail)
+{
+    TailArgs a;
+    a.G = tail->grid;
+    a.records = reinterpret_cast<const float4*>(tail->records);
+    a.visibility = reinterpret_cast<const float2*>(tail->visibility);
+    a.normal_bias = tail->visibility ? tail->normal_bias : 0.0f;
+    a.frame_weight = (tail->flags & NEB_TAIL_FRAME_WEIGHT) ? 1u : 0u;
+    return a;
+}
+
+// neb_gi_trace_paths (tail == nullptr: its kernels, its bits) and neb_gi_trace_paths_tail.
+int trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, const neb_gi_constants* constants, const neb_probe_tail* tail, void* out,
+                void* vertices, neb_stream stream_)
+{
+    static const char who_tail[] = "neb_gi_trace_paths_tail";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -586,6 +664,12 @@ extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n,
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_trace_paths: out overlaps rays");
     if (vertices && (ranges_overlap(rays, ray_bytes, vertices, vertex_bytes) || ranges_overlap(out, out_bytes, vertices, vertex_bytes)))
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_trace_paths: vertices overlaps rays or out");
+    uint32_t tail_count = 0;
+    if (tail) {
+        const TailSpan spans[3] = {{out, out_bytes, "out"}, {vertices, vertex_bytes, "vertices"}, {rays, ray_bytes, "rays"}};
+        if (int rc = tail_shape(ctx, who_tail, tail, spans, 3, &tail_count))
+            return rc;
+    }
     GI_GUARD(ctx);
     if (!device_readable(ctx, rays, ray_bytes))
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_trace_paths: rays is not memory this context's device reads, or n rays leave its allocation");
@@ -594,6 +678,9 @@ extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n,
     if (vertices && !device_readable(ctx, vertices, vertex_bytes))
         return gi_fail(ctx, NEB_ERR_INVALID_ARG,
                        "neb_gi_trace_paths: vertices is not memory this context's device reads, or n * (maxPathVertices - 1) records leave its allocation");
+    if (tail)
+        if (int rc = tail_readable(ctx, who_tail, tail, tail_count))
+            return rc;
     hipStream_t stream = (hipStream_t)stream_;
     ShadeSun sun = {}; // (neb_gi_trace refuses no value of the sun fields, so none is refused here: they act as they act on the frame)
     sun_frame(constants->sunLightDirection, sun.L, sun.B, sun.T);
@@ -618,8 +705,23 @@ extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n,
                                                  {ray_path_kernel<false, true, false>, ray_path_kernel<false, true, true>}},
                                                 {{ray_path_kernel<true, false, false>, ray_path_kernel<true, false, true>},
                                                  {ray_path_kernel<true, true, false>, ray_path_kernel<true, true, true>}}};
-        hipLaunchKernelGGL(kernels[sorted][!g->exact_shade][vertices != nullptr], dim3((n + 63u) / 64u), dim3(64), 0, stream, g->view, g->shade_heads, r4, n, order,
-                           sun, max_vertices, static_cast<float4*>(out), static_cast<float4*>(vertices));
+        if (!tail) {
+            hipLaunchKernelGGL(kernels[sorted][!g->exact_shade][vertices != nullptr], dim3((n + 63u) / 64u), dim3(64), 0, stream, g->view, g->shade_heads, r4, n,
+                               order, sun, max_vertices, static_cast<float4*>(out), static_cast<float4*>(vertices));
+            return hipGetLastError();
+        }
+        // {visible, sorted, fast, vertices}
+        using TailKernel = void (*)(SceneView, const ShadeHeader*, const float4*, uint32_t, const uint32_t*, ShadeSun, uint32_t, float4*, float4*, TailArgs);
+        static const TailKernel tail_kernels[2][2][2][2] = {{{{ray_path_kernel<false, false, false, 1, TailArgs>, ray_path_kernel<false, false, true, 1, TailArgs>},
+                                                              {ray_path_kernel<false, true, false, 1, TailArgs>, ray_path_kernel<false, true, true, 1, TailArgs>}},
+                                                             {{ray_path_kernel<true, false, false, 1, TailArgs>, ray_path_kernel<true, false, true, 1, TailArgs>},
+                                                              {ray_path_kernel<true, true, false, 1, TailArgs>, ray_path_kernel<true, true, true, 1, TailArgs>}}},
+                                                            {{{ray_path_kernel<false, false, false, 2, TailArgs>, ray_path_kernel<false, false, true, 2, TailArgs>},
+                                                              {ray_path_kernel<false, true, false, 2, TailArgs>, ray_path_kernel<false, true, true, 2, TailArgs>}},
+                                                             {{ray_path_kernel<true, false, false, 2, TailArgs>, ray_path_kernel<true, false, true, 2, TailArgs>},
+                                                              {ray_path_kernel<true, true, false, 2, TailArgs>, ray_path_kernel<true, true, true, 2, TailArgs>}}}};
+        hipLaunchKernelGGL(tail_kernels[tail->visibility != nullptr][sorted][!g->exact_shade][vertices != nullptr], dim3((n + 63u) / 64u), dim3(64), 0, stream,
+                           g->view, g->shade_heads, r4, n, order, sun, max_vertices, static_cast<float4*>(out), static_cast<float4*>(vertices), tail_args(tail));
         return hipGetLastError();
     };
     const hipError_t launched = enqueue();
@@ -630,6 +732,20 @@ extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n,
     }
     GI_HIP(ctx, launched);
     return NEB_OK;
+}
+
+} // namespace
+
+extern "C" int neb_gi_trace_paths(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, const neb_gi_constants* constants, void* out, void* vertices,
+                                  neb_stream stream)
+{
+    return trace_paths(ctx, rays, n, flags, constants, nullptr, out, vertices, stream);
+}
+
+extern "C" int neb_gi_trace_paths_tail(neb_ctx* ctx, const neb_ray* rays, uint32_t n, uint32_t flags, const neb_gi_constants* constants,
+                                       const neb_probe_tail* tail, void* out, void* vertices, neb_stream stream)
+{
+    return trace_paths(ctx, rays, n, flags, constants, tail, out, vertices, stream);
 }
 
 namespace {
@@ -688,9 +804,13 @@ extern "C" int neb_gi_probe_rays(neb_ctx* ctx, const neb_probe* probes, uint32_t
     return NEB_OK;
 }
 
-extern "C" int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags,
-                                  const neb_gi_constants* constants, neb_probe_record* out, neb_stream stream_)
+namespace {
+
+// neb_gi_bake_probes (tail == nullptr: its kernels, its bits) and neb_gi_bake_probes_tail.
+int bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags, const neb_gi_constants* constants,
+                const neb_probe_tail* tail, neb_probe_record* out, neb_stream stream_)
 {
+    static const char who_tail[] = "neb_gi_bake_probes_tail";
     if (!ctx)
         return NEB_ERR_INVALID_ARG;
     GiState* g = ctx->gi;
@@ -715,11 +835,20 @@ extern "C" int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: misaligned pointer (probes: 16 bytes; out: 32 bytes)");
     if (ranges_overlap(probes, probe_bytes, out, out_bytes))
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: out overlaps probes");
+    uint32_t tail_count = 0;
+    if (tail) {
+        const TailSpan spans[2] = {{out, out_bytes, "out"}, {probes, probe_bytes, "probes"}};
+        if (int rc = tail_shape(ctx, who_tail, tail, spans, 2, &tail_count))
+            return rc;
+    }
     GI_GUARD(ctx);
     if (!device_readable(ctx, probes, probe_bytes))
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: probes is not memory this context's device reads, or n probes leave its allocation");
     if (!device_readable(ctx, out, out_bytes))
         return gi_fail(ctx, NEB_ERR_INVALID_ARG, "neb_gi_bake_probes: out is not memory this context's device reads, or n records leave its allocation");
+    if (tail)
+        if (int rc = tail_readable(ctx, who_tail, tail, tail_count))
+            return rc;
     hipStream_t stream = (hipStream_t)stream_;
     ShadeSun sun = {}; // (as neb_gi_trace_paths: no value of the sun fields is refused)
     sun_frame(constants->sunLightDirection, sun.L, sun.B, sun.T);
@@ -737,8 +866,34 @@ extern "C" int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_
     using Kernel = void (*)(SceneView, const ShadeHeader*, const float4*, uint32_t, ShadeSun, uint32_t, float, float4*);
     static const Kernel kernels[2][2] = {{probe_bake_kernel<NEB_BAKE_SH, false>, probe_bake_kernel<NEB_BAKE_SH, true>},
                                          {probe_bake_kernel<NEB_BAKE_IRRADIANCE, false>, probe_bake_kernel<NEB_BAKE_IRRADIANCE, true>}};
-    hipLaunchKernelGGL(kernels[what == NEB_BAKE_IRRADIANCE][!g->exact_shade], dim3(n), dim3(64), 0, stream, g->view, g->shade_heads,
-                       reinterpret_cast<const float4*>(probes), samples, sun, max_vertices, scale, reinterpret_cast<float4*>(out));
+    if (!tail) {
+        hipLaunchKernelGGL(kernels[what == NEB_BAKE_IRRADIANCE][!g->exact_shade], dim3(n), dim3(64), 0, stream, g->view, g->shade_heads,
+                           reinterpret_cast<const float4*>(probes), samples, sun, max_vertices, scale, reinterpret_cast<float4*>(out));
+    } else { // {visible, what, fast}
+        using TailKernel = void (*)(SceneView, const ShadeHeader*, const float4*, uint32_t, ShadeSun, uint32_t, float, float4*, TailArgs);
+        static const TailKernel tail_kernels[2][2][2] = {
+            {{probe_bake_kernel<NEB_BAKE_SH, false, 1, TailArgs>, probe_bake_kernel<NEB_BAKE_SH, true, 1, TailArgs>},
+             {probe_bake_kernel<NEB_BAKE_IRRADIANCE, false, 1, TailArgs>, probe_bake_kernel<NEB_BAKE_IRRADIANCE, true, 1, TailArgs>}},
+            {{probe_bake_kernel<NEB_BAKE_SH, false, 2, TailArgs>, probe_bake_kernel<NEB_BAKE_SH, true, 2, TailArgs>},
+             {probe_bake_kernel<NEB_BAKE_IRRADIANCE, false, 2, TailArgs>, probe_bake_kernel<NEB_BAKE_IRRADIANCE, true, 2, TailArgs>}}};
+        hipLaunchKernelGGL(tail_kernels[tail->visibility != nullptr][what == NEB_BAKE_IRRADIANCE][!g->exact_shade], dim3(n), dim3(64), 0, stream, g->view,
+                           g->shade_heads, reinterpret_cast<const float4*>(probes), samples, sun, max_vertices, scale, reinterpret_cast<float4*>(out),
+                           tail_args(tail));
+    }
     GI_HIP(ctx, hipGetLastError());
     return NEB_OK;
+}
+
+} // namespace
+
+extern "C" int neb_gi_bake_probes(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags,
+                                  const neb_gi_constants* constants, neb_probe_record* out, neb_stream stream)
+{
+    return bake_probes(ctx, probes, n, samples, what, flags, constants, nullptr, out, stream);
+}
+
+extern "C" int neb_gi_bake_probes_tail(neb_ctx* ctx, const neb_probe* probes, uint32_t n, uint32_t samples, uint32_t what, uint32_t flags,
+                                       const neb_gi_constants* constants, const neb_probe_tail* tail, neb_probe_record* out, neb_stream stream)
+{
+    return bake_probes(ctx, probes, n, samples, what, flags, constants, tail, out, stream);
 }

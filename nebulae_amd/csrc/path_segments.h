@@ -5,12 +5,20 @@
 // Reads: S, heads, sun, L, Bv, T (the sun frame), last (segments a path can have), stack, i (the index that seeds the stream), the template
 // parameters FAST and VERTICES, vrec (VERTICES).  Takes over o, dir, tmin, tmax (the first segment).  Leaves: sum, first_t,
 // first_geometry, first_primitive, path_flags, segments.
+// TAIL (0: none of it is compiled): the path's last possible vertex, where no further segment is sampled, ends in the
+// probe grid `tail` (TailArgs) instead.  The loop only leaves behind what that vertex knows -- tail_live, its point (tail_p, tail_n), the
+// weight tail_k, its direct term tail_added, its flags and pdiff (tail_flags, tail_pd), and `sum` WITHOUT that vertex -- and the gather
+// runs after the loop, where the loop-carried state is dead and every lane of the wave arrives together (gather_wave ballots).
     bool alive = ray_walkable(o, dir, tmin, tmax);
     uint32_t rng = jenkins(i ^ jenkins(sun.frame_index));
     float3 throughput = f3(1.0f, 1.0f, 1.0f), sum = f3(0.0f, 0.0f, 0.0f);
     float first_t = __builtin_inff();
     uint32_t first_geometry = kNoId, first_primitive = kNoId, path_flags = alive ? 0u : (uint32_t)NEB_HIT_NOT_WALKED, segments = 0u;
     uint32_t k = 1u;
+    [[maybe_unused]] bool tail_live = false;
+    [[maybe_unused]] float3 tail_p = f3(0.0f, 0.0f, 0.0f), tail_n = tail_p, tail_k = tail_p, tail_added = tail_p;
+    [[maybe_unused]] float tail_pd = 0.0f;
+    [[maybe_unused]] uint32_t tail_flags = 0u;
     for (; k <= last; ++k) {
         if (__ballot(alive) == 0ull)
             break;
@@ -71,8 +79,10 @@
                 flags |= NEB_HIT_SUN_VISIBLE;
             }
         }
+        const bool ends_in_grid = TAIL != 0 && shaded && k == last; // (its `added` enters the sum after the loop, with the tail)
         if (alive) {
-            sum = k == 1u ? added : sum + added;
+            if (!ends_in_grid)
+                sum = k == 1u ? added : sum + added;
             ++segments;
         }
         if (k == 1u) {
@@ -99,6 +109,24 @@
                 flags |= NEB_PATH_DIVIDED;
             }
         }
+        if constexpr (TAIL != 0) {
+            if (ends_in_grid) {
+                // the point: the hit as the path forms it, the shading normal turned toward the ray (a terminal backface hit is lit too)
+                const float sd = __fadd_rn(__fadd_rn(rounded_mul(surf.SN.x, dir.x), rounded_mul(surf.SN.y, dir.y)), rounded_mul(surf.SN.z, dir.z));
+                tail_live = true;
+                tail_p = hitP;
+                tail_n = sd <= 0.0f ? surf.SN : -surf.SN;
+                tail_k = throughput_in * (surf.albedo * (1.0f - surf.metalness)); // the two products of :613, had the path gone on
+                tail_added = added;
+                tail_flags = flags;
+                if (tail.frame_weight) { // the pdiff of the bounce that is not taken, and NEB_INDIRECT_FRAME_WEIGHT's reasoning: E[factor] = 2 - pd
+                    const float3 SNn = normalize3<FAST>(surf.SN);
+                    tail_pd = 1.0f - specular_probability<FAST>(saturate1(dot3(V, SNn)), specular_f0(surf.albedo, surf.metalness), surf.albedo);
+                    const float factor = tail_pd > 0.0f ? __fsub_rn(2.0f, tail_pd) : 1.0f;
+                    tail_k = f3(rounded_mul(tail_k.x, factor), rounded_mul(tail_k.y, factor), rounded_mul(tail_k.z, factor));
+                }
+            }
+        }
         if constexpr (VERTICES) {
             float4* rec = vrec + 6 * (size_t)(k - 1u);
             if (alive) {
@@ -119,4 +147,28 @@
         for (; k <= last; ++k) // (the wave left the loop early: every record is written)
             for (int q = 0; q < 6; ++q)
                 vrec[6 * (size_t)(k - 1u) + q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if constexpr (TAIL != 0) {
+        // every lane that entered the loop is here: one gather for the wave, its uniform or its per-lane route as the points fall
+        GatherPoint tail_point;
+        const bool tail_usable = locate_point(tail.G, make_float4(tail_p.x, tail_p.y, tail_p.z, 0.0f), make_float4(tail_n.x, tail_n.y, tail_n.z, 0.0f), tail_live,
+                                              tail_point);
+        float3 tail_E;
+        float tail_W;
+        uint32_t tail_corners;
+        gather_wave<TAIL == 2>(tail.G, tail.records, tail_point, tail_usable, tail_E, tail_W, tail_corners, tail.visibility, tail.normal_bias);
+        if (tail_live) {
+            if (tail_usable && tail_W > 0.0f) { // (else NEB_GATHER_NOT_GATHERED or NEB_GATHER_NO_PROBE: the plain call's record)
+                tail_added = f3(__fadd_rn(tail_added.x, rounded_mul(rounded_mul(tail_k.x, tail_E.x), kPiInv)),
+                                __fadd_rn(tail_added.y, rounded_mul(rounded_mul(tail_k.y, tail_E.y), kPiInv)),
+                                __fadd_rn(tail_added.z, rounded_mul(rounded_mul(tail_k.z, tail_E.z), kPiInv)));
+                path_flags |= NEB_PATH_TAIL;
+                if constexpr (VERTICES) {
+                    float4* rec = vrec + 6 * (size_t)(last - 1u);
+                    rec[3] = make_float4(tail_added.x, tail_added.y, tail_added.z, __uint_as_float(tail_flags | NEB_PATH_TAIL));
+                    reinterpret_cast<float*>(rec + 5)[1] = tail_pd;
+                }
+            }
+            sum = last == 1u ? tail_added : sum + tail_added;
+        }
     }

@@ -43,6 +43,18 @@ class RenderInfo:  # src/DeferredRenderer.h:56-63
     timestep: float = 0.0
 
 
+@dataclass
+class ProbeTail:
+    """The probe grid a path ends in (neb_probe_tail; trace_paths / bake_probes, `tail=`): probe_grid's `grid`, the [nx * ny * nz, 32]
+    "sh" `records` baked (and accumulated) for it, optionally bake_visibility's `visibility` records with the `normal_bias` the visible
+    gather takes, and whether the tail is weighted as the frame weights its diffuse bounce (frame_weight)."""
+    grid: object
+    records: object
+    visibility: object = None
+    normal_bias: float = 0.0
+    frame_weight: bool = True
+
+
 class DeferredRenderer:
     def __init__(self):
         self.svgf = SVGFDenoiser()
@@ -223,7 +235,34 @@ class DeferredRenderer:
                 "primitive": ids[:, 11], "albedo": out[:, 12:15], "roughness": out[:, 15], "metalness": out[:, 16], "texcoord": out[:, 17:19],
                 "material": ids[:, 19], "u": out[:, 20], "v": out[:, 21], "flags": ids[:, 22], "records": out}
 
-    def trace_paths(self, rays, constants=None, max_path_vertices=None, sort=False, vertices=False, out=None, stream=None):
+    def _tail_arg(self, who, tail, device, written):
+        """ProbeTail -> _lib.ProbeTailDesc (None -> None), checked in the style of gather_probes; `written`: (name, tensor) the call
+        writes or reads as its own input, which the grid's buffers must not share memory with."""
+        if tail is None:
+            return None
+        if not isinstance(tail, ProbeTail):
+            raise NebError(f"{who}: tail must be a ProbeTail or None")
+        count = self._grid_arg(who, tail.grid)
+        self._records_arg(who, "tail.records", tail.records, count)
+        normal_bias = self._bias_arg(who, tail.normal_bias)
+        if tail.visibility is None:
+            if normal_bias != 0.0:
+                raise NebError(f"{who}: tail.normal_bias is read only with tail.visibility")
+        else:
+            self._visibility_arg(who, "tail.visibility", tail.visibility, count)
+        for name, t in (("tail.records", tail.records), ("tail.visibility", tail.visibility)):
+            if t is None:
+                continue
+            if t.device != device:
+                raise NebError(f"{who}: {name} must lie on the device of the call's other tensors")
+            a0, a1 = t.data_ptr(), t.data_ptr() + t.numel() * 4
+            for wname, w in written:
+                if w is not None and w.numel() and a0 < w.data_ptr() + w.numel() * 4 and w.data_ptr() < a1:
+                    raise NebError(f"{who}: {name} overlaps {wname} (bake into a second buffer, then accumulate)")
+        return _lib.ProbeTailDesc(tail.grid, tail.records.data_ptr(), tail.visibility.data_ptr() if tail.visibility is not None else None, normal_bias,
+                                  _lib.TAIL_FRAME_WEIGHT if tail.frame_weight else 0)
+
+    def trace_paths(self, rays, constants=None, max_path_vertices=None, sort=False, vertices=False, out=None, stream=None, tail=None):
         """Cast n rays as cast_rays does and follow each as the frame follows a pixel's path (neb_gi_trace_paths): up to
         K - 1 segments, K = max_path_vertices (2..8; default: the constants' maxPathVertices), the sun's direct light at every vertex and
         the sky where a segment misses.  Returns views of one [n, 8] float32 buffer (neb_ray_path) -- radiance [n, 3], t, geometry,
@@ -232,7 +271,11 @@ class DeferredRenderer:
         "vertex_records": origin, tmin, direction, vertex_t, throughput, rng, added, vertex_flags, vertex_geometry, vertex_primitive, u, v,
         tmax, pdiff; a record past the path's end is zero.  `constants` (default: global_constants() of the frame) is not changed.  With
         K = 2 the records are shade_rays("radiance")'s.  sort=True reorders the rays for coherence; the answers are the same bits.  The
-        call only enqueues on `stream`, behind every update enqueued before it; nothing is copied to the host."""
+        call only enqueues on `stream`, behind every update enqueued before it; nothing is copied to the host.
+        `tail` (a ProbeTail; neb_gi_trace_paths_tail): a path that reaches its last possible vertex on a surface with a
+        material ends in the tail's probe grid -- the vertex adds throughput * albedo * (1 - metalness) / pi * E(hit point, normal turned
+        toward the ray), E being gather_probes' answer there, and the vertex and the path gain _lib.PATH_TAIL.  Everything before that
+        vertex is the plain call's bits; tail=None is the plain call."""
         import torch
         if not (isinstance(rays, torch.Tensor) and rays.is_cuda and rays.dtype == torch.float32 and rays.dim() == 2 and rays.shape[1] == 8
                 and rays.is_contiguous()):
@@ -261,9 +304,16 @@ class DeferredRenderer:
                     and vert.is_contiguous()):
                 raise NebError(f"trace_paths: vertices must be a bool or a contiguous torch.float32 CUDA tensor of shape {(n, K - 1, 24)}")
         st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
-        rc = self._lib.neb_gi_trace_paths(self._ctx, C.c_void_p(rays.data_ptr() if n else 0), n, _lib.RAYS_SORT if sort else 0, C.byref(constants),
-                                          C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(vert.data_ptr() if vert is not None and n else 0), st)
-        self._check(rc, "neb_gi_trace_paths")
+        desc = self._tail_arg("trace_paths", tail, rays.device, (("out", out), ("vertices", vert), ("rays", rays)))
+        if desc is None:
+            rc = self._lib.neb_gi_trace_paths(self._ctx, C.c_void_p(rays.data_ptr() if n else 0), n, _lib.RAYS_SORT if sort else 0, C.byref(constants),
+                                              C.c_void_p(out.data_ptr() if n else 0), C.c_void_p(vert.data_ptr() if vert is not None and n else 0), st)
+            self._check(rc, "neb_gi_trace_paths")
+        else:
+            rc = self._lib.neb_gi_trace_paths_tail(self._ctx, C.c_void_p(rays.data_ptr() if n else 0), n, _lib.RAYS_SORT if sort else 0, C.byref(constants),
+                                                   C.byref(desc), C.c_void_p(out.data_ptr() if n else 0),
+                                                   C.c_void_p(vert.data_ptr() if vert is not None and n else 0), st)
+            self._check(rc, "neb_gi_trace_paths_tail")
         ids = out.view(torch.int32)
         res = {"radiance": out[:, 0:3], "t": out[:, 3], "geometry": ids[:, 4], "primitive": ids[:, 5], "flags": ids[:, 6], "segments": ids[:, 7], "records": out}
         if vert is not None:
@@ -311,7 +361,7 @@ class DeferredRenderer:
         self._check(rc, "neb_gi_probe_rays")
         return out
 
-    def bake_probes(self, probes, samples=64, what="sh", constants=None, max_path_vertices=None, out=None, stream=None):
+    def bake_probes(self, probes, samples=64, what="sh", constants=None, max_path_vertices=None, out=None, stream=None, tail=None):
         """Bake n probes on the device (neb_gi_bake_probes): `samples` path samples per probe (a multiple of 64 in
         64..4096), each followed as trace_paths follows ray p * samples + s of probe_rays(probes, samples, what, constants.frameIndex),
         and reduced to one record per probe.  what="sh": the nine second-order spherical-harmonics coefficients of the incoming
@@ -321,7 +371,10 @@ class DeferredRenderer:
         under "records" (`out`, when given).  `constants` (default: global_constants() of the frame) is not changed;
         max_path_vertices (2..8) overrides its maxPathVertices.  The result equals the documented float32 reduction of trace_paths over
         probe_rays bit for bit and needs none of their buffers.  The call only enqueues on `stream`, behind every update enqueued
-        before it; nothing is copied to the host."""
+        before it; nothing is copied to the host.
+        `tail` (a ProbeTail; neb_gi_bake_probes_tail): every sample ends in the tail's grid as trace_paths(tail=) ends
+        it, so that bake -> accumulate_probes -> bake(tail=ProbeTail(grid, the accumulated records)) gains one bounce per round with a
+        bake as short as two path vertices.  `out` must not be the tail's records: bake into a second buffer, then accumulate."""
         import torch
         n, samples, what_id = self._probe_args("bake_probes", probes, samples, what)
         if constants is None:
@@ -337,9 +390,15 @@ class DeferredRenderer:
         elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.float32 and tuple(out.shape) == (n, 32) and out.is_contiguous()):
             raise NebError(f"bake_probes: out must be a contiguous torch.float32 CUDA tensor of shape {(n, 32)}")
         st = C.c_void_p((self.info.stream if self.info else 0) if stream is None else stream)
-        rc = self._lib.neb_gi_bake_probes(self._ctx, C.c_void_p(probes.data_ptr() if n else 0), n, samples, what_id, 0, C.byref(constants),
-                                          C.c_void_p(out.data_ptr() if n else 0), st)
-        self._check(rc, "neb_gi_bake_probes")
+        desc = self._tail_arg("bake_probes", tail, probes.device, (("out", out), ("probes", probes)))
+        if desc is None:
+            rc = self._lib.neb_gi_bake_probes(self._ctx, C.c_void_p(probes.data_ptr() if n else 0), n, samples, what_id, 0, C.byref(constants),
+                                              C.c_void_p(out.data_ptr() if n else 0), st)
+            self._check(rc, "neb_gi_bake_probes")
+        else:
+            rc = self._lib.neb_gi_bake_probes_tail(self._ctx, C.c_void_p(probes.data_ptr() if n else 0), n, samples, what_id, 0, C.byref(constants),
+                                                   C.byref(desc), C.c_void_p(out.data_ptr() if n else 0), st)
+            self._check(rc, "neb_gi_bake_probes_tail")
         ids = out.view(torch.int32)
         return {"sh": out[:, 0:27].view(n, 9, 3), "irradiance": out[:, 0:3], "samples": ids[:, 27], "hits": ids[:, 28], "backfaces": ids[:, 29],
                 "segments": ids[:, 30], "flags": ids[:, 31], "records": out}
